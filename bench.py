@@ -11,10 +11,15 @@ and carries the collective's own latency either way).  Workload at every N: BASE
 SURVEY 8(e): rank r owns contig r; per-site rows are disjoint by construction and only the genome-wide LPMD
 counters are exchanged.
 
-Usage:  python bench.py --gpus N --steps K --warmup W
+Usage:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 works both ways: started under torch.distributed.run (RANK/WORLD_SIZE in the environment) this process is one
 rank; started plainly it re-launches itself as N ranks (one per GPU, 127.0.0.1 rendezvous) and relays rank 0's line.
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs and nothing more: input, warm-up, the K timed steps, the line.
+--full adds every secondary figure behind it (roofline with traffic, soak, two contexts, the WGBS-depth legs, end to end
+from a BAM file, CPU baseline, the collective's own latency).  --dump-outputs DIR writes what the last timed step computed
+(the rows and totals a caller of the path fetches) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -68,6 +73,11 @@ def parse_args(argv=None):
     ap.add_argument("--traffic-probe", default="", help="INTERNAL: run a few steps on the arrays saved in this .npz and exit (the process rocprofv3 wraps)")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="no GPU work: run only the N-rank scaffolding (spawn, rendezvous, barrier, max over ranks, one JSON line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary leg (roofline + traffic, soak, two contexts, WGBS-depth legs, end to end, "
+                         "CPU baseline, collective latency; the --no-* switches above pick among them).  Off: the headline figure only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's results (PDR rows, LPMD totals) as DIR/<name>.npy, float32 / float64, <= 64 MB in all")
     a = ap.parse_args(argv)
     if a.steps is None:
         a.steps = 20 if a.scaling == "strong" else 2000
@@ -906,6 +916,9 @@ def main():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if args.selftest_launcher:
         return selftest(args, rank, world)
+    if args.dump_outputs and (args.scaling == "strong" or args.legs):
+        sys.stderr.write("bench.py: --dump-outputs writes the weak-scaling steps' results; not with --scaling strong or --legs\n")
+        return 2
     if args.scaling == "strong":
         return strong_main(args, rank, world, local_rank, in_rank)
     if args.legs:
@@ -1037,6 +1050,18 @@ def main():
             out["ms_per_step_before_closing_barrier"] = round(dt_before_barrier / args.steps * 1e3, 4)
         if shared:
             out["valid"] = False
+
+    if args.dump_outputs and rank == 0:
+        d = dump_outputs(args.dump_outputs, eng.pdr_fetch(), lg)
+        sys.stderr.write("bench.py: last timed step's outputs -> %s (%d of %d PDR rows)\n" % (args.dump_outputs, d["rows_written"], d["rows"]))
+    if not args.full:
+        # a plain run ends here: nothing below goes into the headline figure (--full runs the secondary legs)
+        if rank == 0:
+            print(json.dumps(order_line(out)), flush=True)
+        eng.close()
+        if use_dist:
+            dist.destroy_process_group()
+        return 0
 
     # ---- roofline leg: dominant kernel timed with HIP events on its own stream ---------------------
     eng.timing_enable(True)
@@ -1257,6 +1282,30 @@ def main():
     if use_dist:
         dist.destroy_process_group()
     return 0
+
+
+DUMP_BYTES = 64_000_000
+PDR_DUMP = (("tid", "tid", np.float64), ("pos", "pos", np.float64), ("value", "pdr", np.float32),
+            ("n_concordant", "n_concordant", np.float64), ("n_discordant", "n_discordant", np.float64))
+LPMD_COUNTS = ("n_concordant", "n_discordant", "n_read", "n_valid_read")
+
+
+def dump_outputs(path, rows, totals):
+    """--dump-outputs: what the last timed step computed, as a caller of the path receives it -- Engine.pdr_fetch()'s rows and
+    Engine.lpmd_global()'s totals -- one .npy per array: integers as float64 (exact), the f32 values as float32.  Past DUMP_BYTES
+    in all, a fixed seeded sample of the rows is written (the same row count always picks the same rows)."""
+    n = len(rows["pos"])
+    cap = (DUMP_BYTES - 4096) // sum(np.dtype(t).itemsize for _, _, t in PDR_DUMP)
+    sel = np.sort(np.random.default_rng(0).choice(n, cap, replace=False)) if n > cap else slice(None)
+    if not os.path.isdir(path):
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as f:     # a directory of build-specific outputs: never source
+            f.write("*\n")
+    for name, key, t in PDR_DUMP:
+        np.save(os.path.join(path, "pdr_%s.npy" % name), np.asarray(rows[key])[sel].astype(t))
+    np.save(os.path.join(path, "lpmd_counts.npy"), np.array([totals[k] for k in LPMD_COUNTS], np.float64))
+    np.save(os.path.join(path, "lpmd_value.npy"), np.array([totals["lpmd"]], np.float32))
+    return {"rows": n, "rows_written": min(n, cap)}
 
 
 def order_line(out):

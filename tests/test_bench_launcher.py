@@ -99,10 +99,7 @@ def test_plan_genome_covers_every_read_once():
 def test_order_line_puts_scalars_first_and_a_summary_last():
     """the bench line carries every secondary figure as a top-level scalar right behind the contract's keys and once
     more in a `summary` object at the END of the line (a driver log keeps the line's tail)"""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
+    bench = _bench_module()
     out = {"metric": "m", "value": 1.0, "unit": "u", "n_gpus": 1, "steps": 2, "warmup": 1, "ms_per_step": 0.1, "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic", "config": {"workload": "w"},
            "roofline": {"frac": 0.43, "frac_l3_resident": 0.48}, "timed_region_s": 1.0,
@@ -116,3 +113,61 @@ def test_order_line_puts_scalars_first_and_a_summary_last():
     for k in ("e2e_10M_median", "e2e_100M_median", "all7_ms", "all7_prepared_ms", "all7_fdrp_pass_ms", "fdrp_pairs_ms", "roofline_frac_two_batches"):
         assert k in line and keys.index(k) < first_nested and line["summary"][k] == line[k]
     assert line["all7_ms"] == 9.7 and line["e2e_100M_median"] == 60.0 and set(out) <= set(line)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_is_the_headline_only_unless_full():
+    bench = _bench_module()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs == ""
+    assert bench.parse_args(["--full"]).full is True
+
+
+def _rows(n, seed=5):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    return dict(tid=np.zeros(n, np.int32), pos=np.sort(rng.choice(58_000_000, n, replace=False)).astype(np.int32),
+                pdr=rng.random(n, dtype=np.float32), n_concordant=rng.integers(0, 60, n).astype(np.uint32),
+                n_discordant=rng.integers(0, 60, n).astype(np.uint32))
+
+
+def test_dump_outputs_writes_float_arrays_of_the_rows(tmp_path):
+    import numpy as np
+    bench = _bench_module()
+    rows = _rows(1000)
+    totals = dict(n_concordant=123, n_discordant=45, n_read=10_000_000, n_valid_read=9_000_001, lpmd=np.float32(0.2678))
+    d = tmp_path / "out"
+    assert bench.dump_outputs(str(d), rows, totals) == {"rows": 1000, "rows_written": 1000}
+    got = {p.name[:-4]: np.load(p) for p in d.glob("*.npy")}
+    assert sorted(got) == ["lpmd_counts", "lpmd_value", "pdr_n_concordant", "pdr_n_discordant", "pdr_pos", "pdr_tid", "pdr_value"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    for name, key in (("pdr_tid", "tid"), ("pdr_pos", "pos"), ("pdr_n_concordant", "n_concordant"), ("pdr_n_discordant", "n_discordant")):
+        assert got[name].dtype == np.float64 and (got[name] == rows[key]).all(), name
+    assert got["pdr_value"].dtype == np.float32 and (got["pdr_value"].view(np.uint32) == rows["pdr"].view(np.uint32)).all()
+    assert got["lpmd_counts"].tolist() == [123, 45, 10_000_000, 9_000_001]
+    assert got["lpmd_value"].dtype == np.float32 and got["lpmd_value"][0] == np.float32(0.2678)
+    assert (d / ".gitignore").read_text() == "*\n"          # a directory the run created holds outputs, never source
+
+
+def test_dump_outputs_samples_the_same_rows_past_the_size_cap(tmp_path, monkeypatch):
+    import numpy as np
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 36 * 200)          # 36 bytes a row: room for 200 rows
+    rows = _rows(5000)
+    totals = dict(n_concordant=1, n_discordant=2, n_read=3, n_valid_read=4, lpmd=np.float32(0.5))
+    for k in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / k), rows, totals) == {"rows": 5000, "rows_written": 200}
+    size = sum(p.stat().st_size - 128 for p in (tmp_path / "a").glob("*.npy"))      # (128: an .npy header)
+    assert size <= bench.DUMP_BYTES
+    for name in ("pdr_pos", "pdr_value", "pdr_n_concordant"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert len(a) == 200 and (a == b).all(), name
+    pos = np.load(tmp_path / "a" / "pdr_pos.npy")
+    assert (np.diff(pos) > 0).all() and np.isin(pos, rows["pos"]).all()      # a subset of the rows, in row order

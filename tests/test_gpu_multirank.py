@@ -18,7 +18,7 @@ BENCH = os.path.join(ROOT, "bench.py")
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_two_processes_on_the_device(scaling):
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--share-devices", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-e2e", "--no-wgbs",
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--share-devices", "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-e2e", "--no-wgbs",
            "--no-traffic", "--soak-seconds", "0", "--preheat-seconds", "0"]
     cmd += ["--reads", "5000000"] if scaling == "weak" else ["--scaling", "strong", "--strong-reads", "4000000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)

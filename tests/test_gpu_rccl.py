@@ -204,7 +204,7 @@ def test_cli_two_shards_on_two_devices(tmp_path, sub, extra):
 def test_bench_two_gpus(scaling):
     """the driver's own launch shape at N = 2: one rank per device, RCCL for the counters, ONE line, `world_seen` 2, nothing marking it invalid"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29633",
-           BENCH, "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-e2e", "--no-wgbs", "--no-traffic", "--soak-seconds", "0",
+           BENCH, "--gpus", "2", "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-e2e", "--no-wgbs", "--no-traffic", "--soak-seconds", "0",
            "--preheat-seconds", "0"]
     cmd += ["--reads", "2000000"] if scaling == "weak" else ["--scaling", "strong", "--strong-reads", "4000000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))

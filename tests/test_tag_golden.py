@@ -17,13 +17,13 @@ def chr19(golden_dir):
                 n_interior=n_interior, n_letters=n_letters)
 
 
-def test_fixture_is_what_the_reference_ships(chr19):
-    # 1000 reads, single-end (flags 0 / 16), all-M CIGARs; the noXM text is the XM file minus its XM:Z field
+def test_fixture_is_what_the_reference_ships(chr19, golden_dir):
+    # 1000 reads, single-end (flags 0 / 16), all-M CIGARs; the noXM text is the XM file minus its XM:Z field, and equals the
+    # reference's own noXM fixture (tests/golden/test.chr19.noXM.sam, copied data)
     assert len(chr19["reads"]) == 1000
     assert {r.flag for r in chr19["reads"]} == {0, 16}
-    ref_noxm = "/root/reference/tests/test.chr19.noXM.sam"
-    if os.path.exists(ref_noxm):                         # only in the build container
-        assert open(ref_noxm).read() == chr19["noxm"]
+    with open(os.path.join(golden_dir, "test.chr19.noXM.sam")) as f:
+        assert f.read() == chr19["noxm"]
     # 8864 of the 9544 context letters are decided by MD-derived bases alone; the others sit in a read's last two
     # columns and look at one of the 29 inferred flank bases
     assert (chr19["n_interior"], chr19["n_letters"], chr19["n_inferred"]) == (8864, 9544, 29)

@@ -5,7 +5,7 @@
 tag=${1:-rXX}; commit=${2:-unknown}
 out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
-B="python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-wgbs --no-traffic --soak-seconds 0"
+B="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-wgbs --no-traffic --soak-seconds 0"
 # Per-kernel durations and counters need launches that do not overlap: the engine's batch pipeline (round 4) runs one batch's
 # kernels beside the next one's, and a profiler then charges each kernel the time it shared the chip.  The three profiled
 # passes switch it off (MTH_PIPELINE=0: the same kernels, one after the other on one stream -- what bench.py's own roofline leg
@@ -81,5 +81,5 @@ for leg in ("all7", "fdrp_pairs"):
     print(leg, "PMC kernels:", sorted(rows))
 PY
 unset MTH_PIPELINE
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 cut -c1-400 $out/bench.json
