@@ -288,6 +288,39 @@ int  mth_fdrp_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_fdr
 int  mth_fdrp_fetch(mth_ctx_t *ctx, uint64_t *n_rows, int32_t *tid, int32_t *pos, float *fdrp, float *qfdrp,
                     uint32_t *n_reads);
 
+/* ---- several measures over one batch (`metheor all`) ------------------------------------------------------------------------------
+ * One call accumulates ONE batch (plain, device-resident or prepared) into the result store of every measure `want` names; the
+ * getters above return the results, bit-identical to calling the single entry points on the same batch (rows, row order where it is
+ * defined, the LPMD counters).  A batch that is not prepared is prepared inside the call and released before it returns, so the read
+ * index is built once for all the measures.  Synchronous: the call returns after a synchronising step, and data errors of the batch
+ * (MTH_ERR_UNSORTED, MTH_ERR_SPAN, ...) are its return value.
+ * pdr_lpmd.want_pdr / want_lpmd are ignored: taken from `want`.  `form`: with ME / PM and PDR and / or LPMD requested, MTH_MULTI_AUTO
+ * runs them as ONE fused tile pass where the PDR + LPMD pass would take its wide (sparse-batch) form and as the two existing passes on
+ * dense batches; MTH_MULTI_FUSED takes the fused pass on every batch; MTH_MULTI_SPLIT always the existing passes.  A fused tile the
+ * pass cannot hold (more distinct quartets than its table, > 65 535 candidate reads, CpGs >= 2048 bp apart) is handed back: the batch's
+ * ME / PM side is redone by mth_quartet_accumulate.  MHL, FDRP / qFDRP and the pairs table always run their own passes.
+ * mth_multi_stats: out[0] batches run in the fused form, out[1] batches run in the split form, out[2] tiles of the fused pass,
+ * out[3] of those handed back (their batch's ME / PM side redone) -- since the context's creation or its last mth_reset.
+ * The test knob MTH_MULTI_FORCE_HANDBACK (environment) hands back every fused tile. */
+#define MTH_MULTI_PDR     1u
+#define MTH_MULTI_LPMD    2u
+#define MTH_MULTI_QUARTET 4u    /* ME and PM: one histogram */
+#define MTH_MULTI_MHL     8u
+#define MTH_MULTI_FDRP    16u   /* FDRP and qFDRP: one pass */
+#define MTH_MULTI_PAIRS   32u   /* the LPMD per-pair table */
+enum { MTH_MULTI_AUTO = 0, MTH_MULTI_FUSED = 1, MTH_MULTI_SPLIT = 2 };
+typedef struct {
+    uint32_t want;                     /* MTH_MULTI_* bits, at least one */
+    mth_pdr_lpmd_params_t   pdr_lpmd;
+    mth_quartet_params_t    quartet;
+    mth_mhl_params_t        mhl;
+    mth_fdrp_params_t       fdrp;
+    mth_lpmd_pairs_params_t pairs;
+    int32_t form;                      /* MTH_MULTI_AUTO / _FUSED / _SPLIT */
+} mth_multi_params_t;
+int  mth_multi_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_multi_params_t *params);
+int  mth_multi_stats(mth_ctx_t *ctx, uint64_t out[4]);
+
 /* ---- BAM record + XM decode on the device (the step before the hot path) ----------
  * Replaces, per record, BismarkRead::new (readutil.rs:24-53: start/end = first/last aligned reference
  * position) and get_cpgs (readutil.rs:323-345: XM z/Z at aligned query offsets, abspos for flags in

@@ -15,7 +15,7 @@ SYMBOLS = [
     "mth_strerror", "mth_last_error", "mth_notes", "mth_batch_prepare", "mth_batch_release", "mth_reset", "mth_pdr_lpmd_accumulate", "mth_pdr_count",
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
-    "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
+    "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
     "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
@@ -70,6 +70,18 @@ class mth_fileorder_params_t(C.Structure):
 
 class mth_lpmd_pairs_params_t(C.Structure):
     _fields_ = [("min_distance", C.c_int32), ("max_distance", C.c_int32), ("min_qual", C.c_uint8)]
+
+
+MTH_MULTI_PDR, MTH_MULTI_LPMD, MTH_MULTI_QUARTET, MTH_MULTI_MHL, MTH_MULTI_FDRP, MTH_MULTI_PAIRS = 1, 2, 4, 8, 16, 32
+MTH_MULTI_AUTO, MTH_MULTI_FUSED, MTH_MULTI_SPLIT = 0, 1, 2
+MULTI_BITS = dict(pdr=MTH_MULTI_PDR, lpmd=MTH_MULTI_LPMD, quartet=MTH_MULTI_QUARTET, mhl=MTH_MULTI_MHL, fdrp=MTH_MULTI_FDRP,
+                  pairs=MTH_MULTI_PAIRS)
+MULTI_FORMS = dict(auto=MTH_MULTI_AUTO, fused=MTH_MULTI_FUSED, split=MTH_MULTI_SPLIT)
+
+
+class mth_multi_params_t(C.Structure):
+    _fields_ = [("want", C.c_uint32), ("pdr_lpmd", mth_pdr_lpmd_params_t), ("quartet", mth_quartet_params_t),
+                ("mhl", mth_mhl_params_t), ("fdrp", mth_fdrp_params_t), ("pairs", mth_lpmd_pairs_params_t), ("form", C.c_int32)]
 
 
 class mth_tag_out_t(C.Structure):
@@ -131,6 +143,8 @@ def lib():
         L.mth_mhl_fetch.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 4
         L.mth_fdrp_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_fdrp_params_t)]
         L.mth_fdrp_fetch.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 5
+        L.mth_multi_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_multi_params_t)]
+        L.mth_multi_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
         L.mth_lpmd_pairs_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_lpmd_pairs_params_t)]
         L.mth_lpmd_pairs_fetch.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 6
         L.mth_decode_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_decoded_t)]
@@ -404,6 +418,31 @@ class Engine:
         self._check(self.L.mth_fdrp_fetch(self.h, C.byref(n), *[out[x].ctypes.data_as(C.c_void_p) for x in
                                                                 ("tid", "pos", "fdrp", "qfdrp", "n_reads")]))
         return out
+
+    def multi_accumulate(self, batch, want=("pdr", "lpmd", "quartet", "mhl", "fdrp"), form="auto", min_depth=10, min_cpgs=4,
+                         min_qual=10, min_distance=2, max_distance=16, max_depth=40, min_overlap=35, seed=0):
+        """every measure of `want` (names of MULTI_BITS) over ONE batch, the read index built once (mth_multi_accumulate): the results are
+        read with the measures' own *_fetch / lpmd_global methods.  The parameters are the CLI's, shared by the measures that have them
+        (`metheor all`); ME / PM take their min_depth at the fetch.  Synchronous."""
+        bits = 0
+        for w in ([want] if isinstance(want, str) else want):
+            bits |= MULTI_BITS[w]
+        p = mth_multi_params_t()
+        p.want = bits
+        p.pdr_lpmd = mth_pdr_lpmd_params_t(min_depth, min_cpgs, min_qual, min_qual, 0, 0, min_distance, max_distance)
+        p.quartet = mth_quartet_params_t(min_qual)
+        p.mhl = mth_mhl_params_t(min_depth, min_cpgs, min_qual)
+        p.fdrp = mth_fdrp_params_t(min_depth, seed, max_depth, min_overlap, min_qual)
+        p.pairs = mth_lpmd_pairs_params_t(min_distance, max_distance, min_qual)
+        p.form = MULTI_FORMS[form] if isinstance(form, str) else int(form)
+        self._check(self.L.mth_multi_accumulate(self.h, C.byref(batch.c), C.byref(p)))
+        self._settled()
+
+    def multi_stats(self):
+        """batches fused / split, tiles fused / handed back by multi_accumulate since the last reset"""
+        out = (C.c_uint64 * 4)()
+        self._check(self.L.mth_multi_stats(self.h, C.byref(out)))
+        return dict(batches_fused=out[0], batches_split=out[1], tiles_fused=out[2], tiles_handed_back=out[3])
 
     def lpmd_pairs_accumulate(self, batch, min_distance=2, max_distance=16, min_qual=10):
         p = mth_lpmd_pairs_params_t(min_distance, max_distance, min_qual)

@@ -93,6 +93,26 @@ const std::vector<Cmd> &commands() {
           {"min-distance", 'm', "MIN_DISTANCE", "Minimum distance between CpG pairs to consider", "2", false, 'I'},
           {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
           {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+        // not in the reference: any subset of the seven measures from ONE decode of the input (the parameters are shared by every
+        // measure that has them, under the single commands' names and defaults; --lpmd-pairs is lpmd's --pairs, whose -p is min-cpgs here)
+        {"all", "(MI355X extension) Compute any of the seven measures from one decode of the input",
+         {O_IN,
+          {"pdr", 0, "PDR", "Output table of PDR", nullptr, false, 's'},
+          {"lpmd", 0, "LPMD", "Output table of LPMD", nullptr, false, 's'},
+          {"lpmd-pairs", 0, "LPMD_PAIRS", "(Optional) Concordance information for all CpG pairs (needs --lpmd)", nullptr, false, 's'},
+          {"mhl", 0, "MHL", "Output table of MHL", nullptr, false, 's'},
+          {"me", 0, "ME", "Output table of methylation entropy", nullptr, false, 's'},
+          {"pm", 0, "PM", "Output table of epipolymorphism", nullptr, false, 's'},
+          {"fdrp", 0, "FDRP", "Output table of FDRP", nullptr, false, 's'},
+          {"qfdrp", 0, "QFDRP", "Output table of qFDRP", nullptr, false, 's'},
+          {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG stretches / quartets / reads mapped to a CpG to consider", "10", false, 'U'},
+          {"min-cpgs", 'p', "MIN_CPGS", "Minimum number of consecutive CpGs in a CpG stretch to consider", "4", false, 'Z'},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'},
+          {"min-distance", 'm', "MIN_DISTANCE", "Minimum distance between CpG pairs to consider", "2", false, 'I'},
+          {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
+          {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
+          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'},
+          O_CPG, O_REGION, O_BAI}},
         {"tag", "Add bismark XM tag to BAM file",
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
           {"genome", 'g', "GENOME", "", nullptr, true, 's'}}},
@@ -116,7 +136,8 @@ std::string usage_line(const Cmd &c) {
 void print_cmd_help(FILE *f, const Cmd &c) {
     fprintf(f, "%s\n\n%s\n\nOptions:\n", c.about, usage_line(c).c_str());
     for (const Opt &o : c.opts) {
-        std::string left = std::string("  -") + o.short_name + ", --" + o.long_name + " <" + o.value_name + ">";
+        std::string left = o.short_name ? std::string("  -") + o.short_name + ", --" + o.long_name + " <" + o.value_name + ">"
+                                        : std::string("      --") + o.long_name + " <" + o.value_name + ">";      // (a long-only option)
         fprintf(f, "%-34s %s%s%s%s\n", left.c_str(), o.help, o.def ? " [default: " : "", o.def ? o.def : "", o.def ? "]" : "");
     }
     fprintf(f, "  -h, --help                       Print help\n");
@@ -279,6 +300,7 @@ struct Input {
     mth_ctx_t *ctx = nullptr;   // set when the records were decoded on the device (the batches live in its HBM)
     bool device = false;
     bool file_order = false;               // pdr / mhl / fdrp / qfdrp on input that is not coordinate-sorted: no batches, the decoded stream itself (mth_fileorder_run)
+    uint32_t dec_flags = 0;                // mth_decoded_contigs' flags of the decoded stream (file_order: whether mth_decoded_sort may take it)
     std::vector<uint8_t> unbatched_mapq;   // mapq of the records that entered no batch (no contig / no aligned base): lpmd.rs:176-179 counts them
 };
 
@@ -440,6 +462,9 @@ bool load_bgzf_on_device(Input &in) {
     return true;
 }
 
+bool batch_decoded(Input &in, const std::vector<int32_t> &tids, const std::vector<uint64_t> &rb, const std::vector<uint64_t> &re,
+                   uint32_t n_runs, uint32_t flags);
+
 bool load_on_device(Input &in, const char *cpg_set, CtxFuture &cf) {
     const uint64_t *keys = nullptr;
     uint64_t n_keys = 0;
@@ -495,9 +520,17 @@ bool load_on_device(Input &in, const char *cpg_set, CtxFuture &cf) {
             // it is (mth_fileorder.hip), no batches
             in.file_order = true;
             in.device = true;
+            in.dec_flags = flags;
             return true;
         }
     }
+    return batch_decoded(in, tids, rb, re, n_runs, flags);
+}
+
+// the decoded stream's contig runs (mth_decoded_contigs) as the batches of the device path: false when the batches cannot hold them
+bool batch_decoded(Input &in, const std::vector<int32_t> &tids, const std::vector<uint64_t> &rb, const std::vector<uint64_t> &re,
+                   uint32_t n_runs, uint32_t flags) {
+    const uint32_t cap = (uint32_t)tids.size();
     if (flags || n_runs > cap) return false;                       // unaligned / contig-less records, or contigs not grouped
     for (uint32_t k = 0; k < n_runs; ++k) {
         for (const Contig &c : in.contigs) if (c.tid == tids[k]) return false;   // the host path reports it
@@ -564,11 +597,11 @@ bool reads_in_order(const int32_t *tid, const int32_t *st, int64_t n) {
     return true;
 }
 
-Input load(const std::string &path, const char *cpg_set) {
+Input load(const std::string &path, const char *cpg_set, bool host_only = false) {
     Phase ph_all("load: open+decode+batch");
     Input in;
     char err[1024];
-    const bool try_device = !getenv("METHEOR_HOST_DECODE");
+    const bool try_device = !getenv("METHEOR_HOST_DECODE") && !host_only;
     if (!try_device && g_shard.planned()) die("--gpus N / --region need the device load path (METHEOR_HOST_DECODE is set)");
     CtxFuture cf;
     if (try_device) cf.start();
@@ -762,9 +795,13 @@ void gang_allreduce_lpmd(mth_ctx_t *ctx) {
     if (g_gang.rc != MTH_OK) check(g_gang.ctxs[0], g_gang.rc);
 }
 
+// ---- the measures' TSV writers (shared by the single commands and `all`) -----------------------------------------------------
+
 // pdr / mhl / fdrp / qfdrp of an input that is not coordinate-sorted: the stream replayed in file order on the device
-// (mth_fileorder.hip); which: 0 = the PDR line (pdr.rs:102-116), 1 = value v0 (mhl.rs:114-132, fdrp.rs:162-173), 2 = value v1 (qfdrp.rs:174-185)
-int run_file_order(const Args &a, Input &in, mth_ctx_t *ctx, const mth_fileorder_params_t &fp, int which) {
+// (mth_fileorder.hip); which: 0 = the PDR line (pdr.rs:102-116), 1 = value v0 (mhl.rs:114-132, fdrp.rs:162-173), 2 = value v1 (qfdrp.rs:174-185).
+// FDRP's replay gives both values: `all` passes both paths (path2: the qFDRP file).
+void file_order_write(Input &in, mth_ctx_t *ctx, const mth_fileorder_params_t &fp, int which, const std::string &path,
+                      const std::string *path2 = nullptr) {
     uint64_t n = 0;
     {
         Phase ph("file-order replay (kernels, sync)");
@@ -776,16 +813,139 @@ int run_file_order(const Args &a, Input &in, mth_ctx_t *ctx, const mth_fileorder
     std::vector<float> v0(n), v1(n);
     std::vector<uint32_t> c0(n), c1(n);
     check(ctx, mth_fileorder_fetch(ctx, &n, tid.data(), pos.data(), v0.data(), v1.data(), c0.data(), c1.data()));
-    FILE *f = open_output(a.s.at("output"));
-    write_rows(f, n, [&](LineWriter &w, uint64_t i) {
-        w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t');
-        if (which == 0) { w.f32(v0[i]); w.ch('\t'); w.u32(c0[i]); w.ch('\t'); w.u32(c1[i]); }
-        else w.f32(which == 2 ? v1[i] : v0[i]);
-        w.eol();
-    });
-    if (fclose(f) != 0) die("Error writing to output file.");
+    auto one = [&](const std::string &out, int w_) {
+        FILE *f = open_output(out);
+        write_rows(f, n, [&](LineWriter &w, uint64_t i) {
+            w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t');
+            if (w_ == 0) { w.f32(v0[i]); w.ch('\t'); w.u32(c0[i]); w.ch('\t'); w.u32(c1[i]); }
+            else w.f32(w_ == 2 ? v1[i] : v0[i]);
+            w.eol();
+        });
+        if (fclose(f) != 0) die("Error writing to output file.");
+    };
+    if (!path.empty()) one(path, which);
+    if (path2) one(*path2, 2);
+}
+
+int run_file_order(const Args &a, Input &in, mth_ctx_t *ctx, const mth_fileorder_params_t &fp, int which) {
+    file_order_write(in, ctx, fp, which, a.s.at("output"));
     return finish(ctx, in.h);
 }
+
+// pdr.rs:102-116: the PDR rows accumulated so far
+void pdr_write(mth_ctx_t *ctx, const Input &in, const std::string &path) {
+    uint64_t n = 0;
+    check(ctx, mth_pdr_count(ctx, &n));
+    Phase ph3("fetch + TSV write");
+    // the five columns in one page-locked allocation (device-to-host at the link's rate; nothing to zero-fill)
+    void *pin = nullptr;
+    check(ctx, mth_result_buffer_alloc(ctx, (size_t)n * 20, &pin));
+    int32_t *tid = (int32_t *)pin, *pos = tid + n;
+    float *pdr = (float *)(pos + n);
+    uint32_t *nc = (uint32_t *)(pdr + n), *nd = nc + n;
+    { Phase pf("  fetch"); check(ctx, mth_pdr_fetch(ctx, tid, pos, pdr, nc, nd)); }
+    Phase pw("  format + write");
+    FILE *f = open_output(path);
+    write_rows(f, n, [&](LineWriter &w, uint64_t i) {   // pdr.rs:102-116
+        w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t');
+        w.f32(pdr[i]); w.ch('\t'); w.u32(nc[i]); w.ch('\t'); w.u32(nd[i]); w.eol();
+    });
+    if (fclose(f) != 0) die("Error writing to output file.");
+    if (getenv("METHEOR_TEARDOWN")) check(ctx, mth_result_buffer_free(ctx, pin));   // (unpinning is a few ms: left to the process's end otherwise)
+}
+
+// lpmd.rs:145-147: the LPMD line, after the records that entered no batch are counted (and, --gpus N, the counters all-reduced)
+void lpmd_write(mth_ctx_t *ctx, const Input &in, const std::string &input, uint8_t min_qual, const std::string &path) {
+    if (!in.unbatched_mapq.empty()) {                            // lpmd.rs:176-179: every record counts, also those without a position
+        uint64_t nv = 0;
+        for (uint8_t q : in.unbatched_mapq) nv += q >= min_qual ? 1u : 0u;
+        check(ctx, mth_lpmd_add_unbatched(ctx, in.unbatched_mapq.size(), nv));
+    }
+    if (g_shard.world > 1) gang_allreduce_lpmd(ctx);             // every shard now holds the genome-wide counters
+    int64_t g[4] = {0, 0, 0, 0};
+    float lp = 0.f;
+    check(ctx, mth_lpmd_global(ctx, g, &lp));
+    if (getenv("METHEOR_DEBUG_COUNTS")) fprintf(stderr, "[metheor counts] n_concordant=%lld n_discordant=%lld n_read=%lld n_valid_read=%lld\n", (long long)g[0], (long long)g[1], (long long)g[2], (long long)g[3]);
+    // records that never enter a batch only move n_read / n_valid_read (not part of the TSV)
+    FILE *f = open_output(path);
+    char fb[64];
+    mth_host_format_f32(lp, fb);
+    if (g_shard.rank == 0) fprintf(f, "name\tlpmd\n%s\t%s\n", input.c_str(), fb);   // lpmd.rs:145-147
+    if (fclose(f) != 0) die("Error writing to output file.");
+}
+
+// lpmd.rs:149-151, 89-122: the per-pair table accumulated so far
+void lpmd_pairs_write(mth_ctx_t *ctx, const Input &in, const std::string &path) {
+    uint64_t n = 0;
+    check(ctx, mth_lpmd_pairs_fetch(ctx, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    std::vector<int32_t> tid(n), p1(n), p2(n);
+    std::vector<float> v(n);
+    std::vector<uint32_t> nc(n), nd(n);
+    check(ctx, mth_lpmd_pairs_fetch(ctx, &n, tid.data(), p1.data(), p2.data(), v.data(), nc.data(), nd.data()));
+    FILE *g = open_output(path, true);
+    if (g_shard.rank == 0) fprintf(g, "chrom\tcpg1\tcpg2\tlpmd\tn_concordant\tn_discordant\n");
+    fflush(g);
+    write_rows(g, n, [&](LineWriter &w, uint64_t i) {
+        w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(p1[i]); w.ch('\t'); w.i32(p2[i]); w.ch('\t');
+        w.f32(v[i]); w.ch('\t'); w.u32(nc[i]); w.ch('\t'); w.u32(nd[i]); w.eol();
+    });
+    if (fclose(g) != 0) die("Error writing to output file.");
+}
+
+// me.rs:68-88 / pm.rs:63-83: one line per quartet with depth >= min_depth,
+// chrom, pos1..pos4, value (me.rs:57-65).  The reference iterates a HashMap (random order).
+void quartet_write(mth_ctx_t *ctx, const Input &in, uint32_t min_depth, bool want_me, const std::string &path) {
+    Phase ph("fetch + TSV write");
+    uint64_t n = 0;
+    check(ctx, mth_quartet_fetch(ctx, min_depth, &n, nullptr, nullptr, nullptr, nullptr, nullptr));
+    std::vector<int32_t> tid(n), pos(n * 4);
+    std::vector<float> val(n);
+    check(ctx, mth_quartet_fetch(ctx, min_depth, &n, tid.data(), pos.data(), nullptr, want_me ? val.data() : nullptr,
+                                 want_me ? nullptr : val.data()));
+    FILE *f = open_output(path);
+    write_rows(f, n, [&](LineWriter &w, uint64_t i) {
+        w.str(mth_host_ref_name(in.h, tid[i]));
+        for (int k = 0; k < 4; ++k) { w.ch('\t'); w.i32(pos[4 * i + k]); }
+        w.ch('\t'); w.f32(val[i]); w.eol();
+    });
+    if (fclose(f) != 0) die("Error writing to output file.");
+}
+
+// mhl.rs:101-133: chrom, pos, pos+2, mhl -- sorted by (tid,pos)
+void mhl_write(mth_ctx_t *ctx, const Input &in, const std::string &path) {
+    uint64_t n = 0;
+    check(ctx, mth_mhl_fetch(ctx, &n, nullptr, nullptr, nullptr, nullptr));
+    std::vector<int32_t> tid(n), pos(n);
+    std::vector<float> val(n);
+    check(ctx, mth_mhl_fetch(ctx, &n, tid.data(), pos.data(), val.data(), nullptr));
+    FILE *f = open_output(path);
+    write_rows(f, n, [&](LineWriter &w, uint64_t i) {
+        w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t'); w.f32(val[i]); w.eol();
+    });
+    if (fclose(f) != 0) die("Error writing to output file.");
+}
+
+// fdrp.rs:148-174 / qfdrp.rs:160-186: chrom, pos, pos+2, value -- sorted by (tid,pos); either path may be empty
+void fdrp_write(mth_ctx_t *ctx, const Input &in, const std::string &fdrp_path, const std::string &qfdrp_path) {
+    uint64_t n = 0;
+    check(ctx, mth_fdrp_fetch(ctx, &n, nullptr, nullptr, nullptr, nullptr, nullptr));
+    std::vector<int32_t> tid(n), pos(n);
+    std::vector<float> fv(fdrp_path.empty() ? 0 : n), qv(qfdrp_path.empty() ? 0 : n);
+    check(ctx, mth_fdrp_fetch(ctx, &n, tid.data(), pos.data(), fdrp_path.empty() ? nullptr : fv.data(),
+                              qfdrp_path.empty() ? nullptr : qv.data(), nullptr));
+    for (int q = 0; q < 2; ++q) {
+        const std::string &path = q ? qfdrp_path : fdrp_path;
+        if (path.empty()) continue;
+        const std::vector<float> &val = q ? qv : fv;
+        FILE *f = open_output(path);
+        write_rows(f, n, [&](LineWriter &w, uint64_t i) {
+            w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t'); w.f32(val[i]); w.eol();
+        });
+        if (fclose(f) != 0) die("Error writing to output file.");
+    }
+}
+
+// ---- the single commands ----------------------------------------------------------------------------------------------------------
 
 int run_pdr(const Args &a) {
     Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
@@ -802,30 +962,13 @@ int run_pdr(const Args &a) {
         fp.measure = MTH_FO_PDR; fp.min_depth = p.pdr_min_depth; fp.min_cpgs = p.pdr_min_cpgs; fp.min_qual = p.pdr_min_qual;
         return run_file_order(a, in, ctx, fp, 0);
     }
-    uint64_t n = 0;
     {
         Phase ph("H2D + kernels (sync)");
         submit(ctx, in, p);
+        uint64_t n = 0;
         check(ctx, mth_pdr_count(ctx, &n));
     }
-    {
-        Phase ph3("fetch + TSV write");
-        // the five columns in one page-locked allocation (device-to-host at the link's rate; nothing to zero-fill)
-        void *pin = nullptr;
-        check(ctx, mth_result_buffer_alloc(ctx, (size_t)n * 20, &pin));
-        int32_t *tid = (int32_t *)pin, *pos = tid + n;
-        float *pdr = (float *)(pos + n);
-        uint32_t *nc = (uint32_t *)(pdr + n), *nd = nc + n;
-        { Phase pf("  fetch"); check(ctx, mth_pdr_fetch(ctx, tid, pos, pdr, nc, nd)); }
-        Phase pw("  format + write");
-        FILE *f = open_output(a.s.at("output"));
-        write_rows(f, n, [&](LineWriter &w, uint64_t i) {   // pdr.rs:102-116
-            w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t');
-            w.f32(pdr[i]); w.ch('\t'); w.u32(nc[i]); w.ch('\t'); w.u32(nd[i]); w.eol();
-        });
-        if (fclose(f) != 0) die("Error writing to output file.");
-        if (getenv("METHEOR_TEARDOWN")) check(ctx, mth_result_buffer_free(ctx, pin));   // (unpinning is a few ms: left to the process's end otherwise)
-    }
+    pdr_write(ctx, in, a.s.at("output"));
     return finish(ctx, in.h);
 }
 
@@ -844,22 +987,7 @@ int run_lpmd(const Args &a) {
     p.lpmd_min_distance = mind; p.lpmd_max_distance = maxd;
     p.want_lpmd = 1;
     submit(ctx, in, p);
-    if (!in.unbatched_mapq.empty()) {                            // lpmd.rs:176-179: every record counts, also those without a position
-        uint64_t nv = 0;
-        for (uint8_t q : in.unbatched_mapq) nv += q >= p.lpmd_min_qual ? 1u : 0u;
-        check(ctx, mth_lpmd_add_unbatched(ctx, in.unbatched_mapq.size(), nv));
-    }
-    if (g_shard.world > 1) gang_allreduce_lpmd(ctx);             // every shard now holds the genome-wide counters
-    int64_t g[4] = {0, 0, 0, 0};
-    float lp = 0.f;
-    check(ctx, mth_lpmd_global(ctx, g, &lp));
-    if (getenv("METHEOR_DEBUG_COUNTS")) fprintf(stderr, "[metheor counts] n_concordant=%lld n_discordant=%lld n_read=%lld n_valid_read=%lld\n", (long long)g[0], (long long)g[1], (long long)g[2], (long long)g[3]);
-    // records that never enter a batch only move n_read / n_valid_read (not part of the TSV)
-    FILE *f = open_output(a.s.at("output"));
-    char fb[64];
-    mth_host_format_f32(lp, fb);
-    if (g_shard.rank == 0) fprintf(f, "name\tlpmd\n%s\t%s\n", input.c_str(), fb);   // lpmd.rs:145-147
-    if (fclose(f) != 0) die("Error writing to output file.");
+    lpmd_write(ctx, in, input, p.lpmd_min_qual, a.s.at("output"));
     if (a.has("pairs")) {                                       // lpmd.rs:149-151, 89-122
         mth_lpmd_pairs_params_t pp;
         pp.min_distance = mind; pp.max_distance = maxd; pp.min_qual = p.lpmd_min_qual;
@@ -867,26 +995,11 @@ int run_lpmd(const Args &a) {
             const mth_batch_t b = make_batch(in, c);
             check(ctx, mth_lpmd_pairs_accumulate(ctx, &b, &pp));
         }
-        uint64_t n = 0;
-        check(ctx, mth_lpmd_pairs_fetch(ctx, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-        std::vector<int32_t> tid(n), p1(n), p2(n);
-        std::vector<float> v(n);
-        std::vector<uint32_t> nc(n), nd(n);
-        check(ctx, mth_lpmd_pairs_fetch(ctx, &n, tid.data(), p1.data(), p2.data(), v.data(), nc.data(), nd.data()));
-        FILE *g = open_output(a.s.at("pairs"), true);
-        if (g_shard.rank == 0) fprintf(g, "chrom\tcpg1\tcpg2\tlpmd\tn_concordant\tn_discordant\n");
-        fflush(g);
-        write_rows(g, n, [&](LineWriter &w, uint64_t i) {
-            w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(p1[i]); w.ch('\t'); w.i32(p2[i]); w.ch('\t');
-            w.f32(v[i]); w.ch('\t'); w.u32(nc[i]); w.ch('\t'); w.u32(nd[i]); w.eol();
-        });
-        if (fclose(g) != 0) die("Error writing to output file.");
+        lpmd_pairs_write(ctx, in, a.s.at("pairs"));
     }
     return finish(ctx, in.h);
 }
 
-// me.rs:68-88 / pm.rs:63-83: one line per quartet with depth >= min_depth,
-// chrom, pos1..pos4, value (me.rs:57-65).  The reference iterates a HashMap (random order).
 int run_quartet(const Args &a, bool want_me) {
     g_shard.order_free = true;
     Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
@@ -900,27 +1013,10 @@ int run_quartet(const Args &a, bool want_me) {
             check(ctx, mth_quartet_accumulate(ctx, &b, &p));
         }
     }
-    {
-        Phase ph("fetch + TSV write");
-        const uint32_t min_depth = (uint32_t)a.n.at("min-depth");
-        uint64_t n = 0;
-        check(ctx, mth_quartet_fetch(ctx, min_depth, &n, nullptr, nullptr, nullptr, nullptr, nullptr));
-        std::vector<int32_t> tid(n), pos(n * 4);
-        std::vector<float> val(n);
-        check(ctx, mth_quartet_fetch(ctx, min_depth, &n, tid.data(), pos.data(), nullptr, want_me ? val.data() : nullptr,
-                                     want_me ? nullptr : val.data()));
-        FILE *f = open_output(a.s.at("output"));
-        write_rows(f, n, [&](LineWriter &w, uint64_t i) {
-            w.str(mth_host_ref_name(in.h, tid[i]));
-            for (int k = 0; k < 4; ++k) { w.ch('\t'); w.i32(pos[4 * i + k]); }
-            w.ch('\t'); w.f32(val[i]); w.eol();
-        });
-        if (fclose(f) != 0) die("Error writing to output file.");
-    }
+    quartet_write(ctx, in, (uint32_t)a.n.at("min-depth"), want_me, a.s.at("output"));
     return finish(ctx, in.h);
 }
 
-// mhl.rs:101-133: chrom, pos, pos+2, mhl -- sorted by (tid,pos)
 int run_mhl(const Args &a) {
     Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
     mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
@@ -938,20 +1034,10 @@ int run_mhl(const Args &a) {
         const mth_batch_t b = make_batch(in, c);
         check(ctx, mth_mhl_accumulate(ctx, &b, &p));
     }
-    uint64_t n = 0;
-    check(ctx, mth_mhl_fetch(ctx, &n, nullptr, nullptr, nullptr, nullptr));
-    std::vector<int32_t> tid(n), pos(n);
-    std::vector<float> val(n);
-    check(ctx, mth_mhl_fetch(ctx, &n, tid.data(), pos.data(), val.data(), nullptr));
-    FILE *f = open_output(a.s.at("output"));
-    write_rows(f, n, [&](LineWriter &w, uint64_t i) {
-        w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t'); w.f32(val[i]); w.eol();
-    });
-    if (fclose(f) != 0) die("Error writing to output file.");
+    mhl_write(ctx, in, a.s.at("output"));
     return finish(ctx, in.h);
 }
 
-// fdrp.rs:148-174 / qfdrp.rs:160-186: chrom, pos, pos+2, value -- sorted by (tid,pos)
 int run_fdrp(const Args &a, bool quantitative) {
     Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
     mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
@@ -974,17 +1060,115 @@ int run_fdrp(const Args &a, bool quantitative) {
         const mth_batch_t b = make_batch(in, c);
         check(ctx, mth_fdrp_accumulate(ctx, &b, &p));
     }
-    uint64_t n = 0;
-    check(ctx, mth_fdrp_fetch(ctx, &n, nullptr, nullptr, nullptr, nullptr, nullptr));
-    std::vector<int32_t> tid(n), pos(n);
-    std::vector<float> val(n);
-    check(ctx, mth_fdrp_fetch(ctx, &n, tid.data(), pos.data(), quantitative ? nullptr : val.data(),
-                              quantitative ? val.data() : nullptr, nullptr));
-    FILE *f = open_output(a.s.at("output"));
-    write_rows(f, n, [&](LineWriter &w, uint64_t i) {
-        w.str(mth_host_ref_name(in.h, tid[i])); w.ch('\t'); w.i32(pos[i]); w.ch('\t'); w.i32(pos[i] + 2); w.ch('\t'); w.f32(val[i]); w.eol();
-    });
-    if (fclose(f) != 0) die("Error writing to output file.");
+    const std::string none;
+    fdrp_write(ctx, in, quantitative ? none : a.s.at("output"), quantitative ? a.s.at("output") : none);
+    return finish(ctx, in.h);
+}
+
+// ---- metheor all: any subset of the seven measures from ONE decode ----------------------------------------------------------------
+// Each output file is byte for byte what the matching single command writes with the same parameters (`metheor pdr -i IN -o F -d ..
+// -p .. -q ..` and so on).  What the single commands do differently on the way is taken care of here:
+//   * the XM rule: lpmd alone decodes with its mapq-first rule (lpmd.rs:176-181), every other measure with the strict one -- `all` takes
+//     the strict rule unless lpmd (and its pairs table) is all it was asked for: where that refuses a file, one of the requested single
+//     runs refuses it too (exit 101);
+//   * unsorted input: pdr / mhl / fdrp / qfdrp replay the decoded stream in file order (one replay per measure; FDRP's gives both
+//     tables), then lpmd / me / pm sort the same decoded stream on the device (mth_decoded_sort) and take the batches -- or, where the
+//     device sort cannot take the stream (records without a contig or an aligned base), a host decode of the file, as their single
+//     runs do.
+// On sorted input every batch (contig group) is accumulated once for all the requested measures (mth_multi_accumulate: one prepared
+// batch, one read index).
+int run_all(const Args &a) {
+    const std::string input = a.s.at("input");
+    const char *cpg_set = a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr;
+    const bool w_pdr = a.has("pdr"), w_lpmd = a.has("lpmd"), w_pairs = a.has("lpmd-pairs"), w_mhl = a.has("mhl"), w_me = a.has("me"),
+               w_pm = a.has("pm"), w_fdrp = a.has("fdrp"), w_qfdrp = a.has("qfdrp");
+    const uint32_t min_depth = (uint32_t)a.n.at("min-depth");
+    const uint32_t min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
+    const uint8_t min_qual = (uint8_t)a.n.at("min-qual");
+    const int32_t mind = (int32_t)a.n.at("min-distance"), maxd = (int32_t)a.n.at("max-distance");
+    if (w_lpmd)   // lpmd.rs:161-164
+        fprintf(stderr, "Computing subset-LPMD with parameters input=%s, min_distance=%d, max_distance=%d\n", input.c_str(), mind, maxd);
+    const bool any_flush = w_pdr || w_mhl || w_fdrp || w_qfdrp;          // the measures whose result depends on the record order
+    const bool any_free = w_lpmd || w_me || w_pm;
+    g_shard.xm_min_mapq = (any_flush || w_me || w_pm) ? 0 : (int)min_qual;
+    g_shard.order_free = !any_flush;
+    Input in = load(input, cpg_set);
+    mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
+
+    mth_multi_params_t mp;
+    memset(&mp, 0, sizeof mp);
+    mp.pdr_lpmd.pdr_min_depth = min_depth; mp.pdr_lpmd.pdr_min_cpgs = min_cpgs; mp.pdr_lpmd.pdr_min_qual = min_qual;
+    mp.pdr_lpmd.lpmd_min_qual = min_qual; mp.pdr_lpmd.lpmd_min_distance = mind; mp.pdr_lpmd.lpmd_max_distance = maxd;
+    mp.quartet.min_qual = min_qual;
+    mp.mhl.min_depth = min_depth; mp.mhl.min_cpgs = min_cpgs; mp.mhl.min_qual = min_qual;
+    mp.fdrp.min_qual = min_qual; mp.fdrp.min_depth = min_depth;
+    mp.fdrp.max_depth = (uint32_t)std::min<int64_t>(a.n.at("max-depth"), UINT32_MAX);
+    mp.fdrp.min_overlap = (int32_t)a.n.at("min-overlap");
+    const char *seed = getenv("METHEOR_SEED");       // reservoir draws (the reference's are OS-seeded)
+    mp.fdrp.seed = seed ? strtoull(seed, nullptr, 10) : 0;
+    mp.pairs.min_distance = mind; mp.pairs.max_distance = maxd; mp.pairs.min_qual = min_qual;
+    mp.form = MTH_MULTI_AUTO;
+    const std::string none;
+
+    Input host_in;                                   // (unsorted input the device sort cannot take: the order-free measures' host decode)
+    Input *bin = &in;
+    if (in.file_order) {
+        mth_fileorder_params_t fp;
+        memset(&fp, 0, sizeof fp);
+        fp.min_qual = min_qual;
+        if (w_pdr) {
+            fp.measure = MTH_FO_PDR; fp.min_depth = min_depth; fp.min_cpgs = min_cpgs;
+            file_order_write(in, ctx, fp, 0, a.s.at("pdr"));
+        }
+        if (w_mhl) {
+            fp.measure = MTH_FO_MHL; fp.min_depth = min_depth; fp.min_cpgs = min_cpgs;
+            file_order_write(in, ctx, fp, 1, a.s.at("mhl"));
+        }
+        if (w_fdrp || w_qfdrp) {
+            fp.measure = MTH_FO_FDRP; fp.min_depth = min_depth; fp.min_cpgs = 0; fp.max_depth = mp.fdrp.max_depth;
+            fp.min_overlap = mp.fdrp.min_overlap; fp.seed = mp.fdrp.seed;
+            file_order_write(in, ctx, fp, 1, w_fdrp ? a.s.at("fdrp") : none, w_qfdrp ? &a.s.at("qfdrp") : nullptr);
+        }
+        if (!any_free) return finish(ctx, in.h);
+        if (!(in.dec_flags & 3u)) {
+            Phase ps("  device sort by (tid, start)");
+            check(ctx, mth_decoded_sort(ctx));
+            const uint32_t cap = (uint32_t)std::max(1, mth_host_n_refs(in.h)) + 1;
+            std::vector<int32_t> tids(cap);
+            std::vector<uint64_t> rb(cap), re(cap);
+            uint32_t n_runs = 0, flags = 0;
+            check(ctx, mth_decoded_contigs(ctx, cap, tids.data(), rb.data(), re.data(), &n_runs, &flags));
+            in.file_order = false;
+            if (!batch_decoded(in, tids, rb, re, n_runs, flags))
+                die("metheor (MI355X path): the decoded stream could not be batched after the device sort");
+        } else {
+            g_shard.order_free = true;
+            host_in = load(input, cpg_set, true);
+            bin = &host_in;
+        }
+        mp.want = (w_lpmd ? MTH_MULTI_LPMD : 0u) | ((w_me || w_pm) ? MTH_MULTI_QUARTET : 0u) | (w_pairs ? MTH_MULTI_PAIRS : 0u);
+    } else {
+        mp.want = (w_pdr ? MTH_MULTI_PDR : 0u) | (w_lpmd ? MTH_MULTI_LPMD : 0u) | ((w_me || w_pm) ? MTH_MULTI_QUARTET : 0u) |
+                  (w_mhl ? MTH_MULTI_MHL : 0u) | ((w_fdrp || w_qfdrp) ? MTH_MULTI_FDRP : 0u) | (w_pairs ? MTH_MULTI_PAIRS : 0u);
+    }
+    {
+        Phase ph("H2D + kernels (sync)");
+        for (const Contig &c : bin->contigs) {
+            const mth_batch_t b = make_batch(*bin, c);
+            mth_batch_t pb;
+            check(ctx, mth_batch_prepare(ctx, &b, &pb));      // one device copy and one read index for every measure of the batch
+            check(ctx, mth_multi_accumulate(ctx, &pb, &mp));
+            check(ctx, mth_batch_release(ctx, &pb));
+        }
+    }
+    if (mp.want & MTH_MULTI_PDR) pdr_write(ctx, *bin, a.s.at("pdr"));
+    if (w_lpmd) lpmd_write(ctx, *bin, input, min_qual, a.s.at("lpmd"));
+    if (w_pairs) lpmd_pairs_write(ctx, *bin, a.s.at("lpmd-pairs"));
+    if (w_me) quartet_write(ctx, *bin, min_depth, true, a.s.at("me"));
+    if (w_pm) quartet_write(ctx, *bin, min_depth, false, a.s.at("pm"));
+    if (mp.want & MTH_MULTI_MHL) mhl_write(ctx, *bin, a.s.at("mhl"));
+    if (mp.want & MTH_MULTI_FDRP) fdrp_write(ctx, *bin, w_fdrp ? a.s.at("fdrp") : none, w_qfdrp ? a.s.at("qfdrp") : none);
+    if (host_in.h) { mth_host_close(host_in.h); host_in.h = nullptr; }      // (the order-free measures' own decode of the file)
     return finish(ctx, in.h);
 }
 
@@ -1117,12 +1301,23 @@ int main(int argc, char **argv) {
         if (sub == "qfdrp") return run_fdrp(a, true);
         if (sub == "me") return run_quartet(a, true);
         if (sub == "pm") return run_quartet(a, false);
+        if (sub == "all") return run_all(a);
         return -1;
     };
     if (sub == "tag") {
         if (const char *dev = getenv("METHEOR_DEVICE")) g_shard.device = atoi(dev);
         return run_tag(a);
     }
+    if (sub == "all") {      // clap-style: an ArgGroup of the outputs (required, multiple) and `requires` on --lpmd-pairs
+        static const char *outs[] = {"pdr", "lpmd", "mhl", "me", "pm", "fdrp", "qfdrp"};
+        bool any = false;
+        for (const char *o : outs) any |= a.has(o);
+        if (!any)
+            usage_error(cmd, "the following required arguments were not provided:\n  <--pdr <PDR>|--lpmd <LPMD>|--mhl <MHL>|--me <ME>|--pm <PM>|--fdrp <FDRP>|--qfdrp <QFDRP>>");
+        if (a.has("lpmd-pairs") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
+    }
+    // (`all` has no --gpus: one device)
+    const int64_t gpus = a.n.count("gpus") ? a.n.at("gpus") : 1;
     int64_t halo = 65536;
     if (const char *e = getenv("METHEOR_SHARD_HALO")) { const long long k = atoll(e); if (k >= 0) halo = k; }
     if (a.has("region")) {       // chr | chr:beg-end (1-based, inclusive, commas allowed; as samtools view takes it)
@@ -1139,9 +1334,9 @@ int main(int argc, char **argv) {
             else if (k == 2 || reg.find('-', c) != std::string::npos) usage_error(cmd, "invalid value '" + reg + "' for '--region <REGION>': want chr or chr:beg-end with 1 <= beg <= end");
         }
         if (a.has("bai")) g_shard.bai = a.s.at("bai");
-        if (a.n.at("gpus") > 1) usage_error(cmd, "the argument '--region <REGION>' cannot be used with '--gpus <GPUS>' above 1");
+        if (gpus > 1) usage_error(cmd, "the argument '--region <REGION>' cannot be used with '--gpus <GPUS>' above 1");
     } else if (a.has("bai")) usage_error(cmd, "the argument '--bai <BAI>' needs '--region <REGION>'");
-    const int world = (int)std::min<int64_t>(a.n.at("gpus"), 4096);
+    const int world = (int)std::min<int64_t>(gpus, 4096);
     if (world < 1) usage_error(cmd, "invalid value '0' for '--gpus <GPUS>': at least one GPU");
     if (world == 1) {
         if (const char *dev = getenv("METHEOR_DEVICE")) g_shard.device = atoi(dev);

@@ -483,6 +483,7 @@ int mth_reset(mth_ctx_t *ctx) {
     ctx->p_meta.clear();
     ctx->p_pending.clear();
     ctx->p_rows = 0;
+    for (uint64_t &k : ctx->multi_stats) k = 0;
     return MTH_OK;
 }
 

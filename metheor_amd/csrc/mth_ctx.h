@@ -44,7 +44,7 @@ struct PdrLane {
 }  // namespace mth
 
 struct mth_ctx;
-namespace mth { int quartet_resolve(mth_ctx *ctx); int pairs_resolve(mth_ctx *ctx); }
+namespace mth { int quartet_resolve(mth_ctx *ctx); int pairs_resolve(mth_ctx *ctx); struct FusedQuartet; }
 
 namespace mth {
 // a prepared batch (include/metheor_hip.h, "prepared batches"): the device-resident batch, the buffers it owns when it was made
@@ -197,6 +197,11 @@ struct mth_ctx {
     hipEvent_t red_ready[RED_RING] = {}, red_done[RED_RING] = {};
     uint64_t red_head = 0;
     int red_slot = -1;
+
+    // mth_multi_accumulate (mth_multi.hip): batches fused / split, tiles fused / handed back since the last mth_reset
+    uint64_t multi_stats[4] = {0, 0, 0, 0};
+    // set by mth_multi_accumulate around its PDR + LPMD call: the wide form of that pass then runs as the fused tile pass (nullptr always else)
+    mth::FusedQuartet *fuse_q = nullptr;
 
     bool timing = false;
     std::vector<mth::TimedLaunch> timed;

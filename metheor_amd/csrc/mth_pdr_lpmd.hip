@@ -1616,7 +1616,8 @@ static int pipe_begin(mth_ctx *ctx, int &li) {
 }
 
 int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_params_t &p, const TileSink *sink, bool pipelined) {
-    if (sink) pipelined = false;
+    FusedQuartet *const fq = sink ? nullptr : ctx->fuse_q;       // (mth_multi_accumulate only: the quartet tables ride along, mth_multi.hip)
+    if (sink || fq) pipelined = false;
     int li = 0;
     if (pipelined) { const int rc = pipe_begin(ctx, li); if (rc) return rc; }
     PdrLane *L = pipelined ? &ctx->lane[li] : nullptr;
@@ -1667,6 +1668,7 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
         }
     }
     if (const char *e = getenv("MTH_PDR_WIDE")) { const int k = atoi(e); wide_shift = k >= 14 && k <= 16 ? k : 0; }
+    if (fq && fq->force && wide_shift == 0) wide_shift = 14;       // MTH_MULTI_FUSED on a dense batch
     const int tile_w = wide_shift ? 1 << wide_shift : 4096;
     // Wide form: the tile need not be as wide as its slice.  A chr1-sized contig is 2.12 rounds of 65536-position tiles over the chip's
     // 1 792 resident workgroups (7 on each of 256 CUs) and ends on a nearly empty third round; tiles of region / (3 x 1 792) positions
@@ -1767,7 +1769,8 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
     {
         LaunchTimer lt(ctx, wide_shift ? K_WIDE : K_TILE);
         const bool r8 = b.cpg_rel != nullptr;
-        if (wide_shift) launch_tile_wide(a, ntiles, wide_shift, r8, s);
+        if (wide_shift && fq && ntiles <= fq->max_tiles) { launch_tile_fused(a, *fq, ntiles, wide_shift, r8, s); fq->taken = true; fq->ntiles = ntiles; }
+        else if (wide_shift) launch_tile_wide(a, ntiles, wide_shift, r8, s);
         else if (runs) launch_runs(a, ra, ntiles, G, s);
         else if (r8) launch_tile<(1 << DENSE_TILE_SHIFT), 256, uint8_t>(a, ntiles, s); else launch_tile<(1 << DENSE_TILE_SHIFT), 256, uint16_t>(a, ntiles, s);
     }

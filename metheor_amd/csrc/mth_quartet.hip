@@ -25,10 +25,10 @@
 #include "mth_ctx.h"
 #include "mth_scan.h"
 #include "mth_tile_dev.h"
+#include "mth_quartet_dev.h"
 
 namespace mth {
 
-constexpr unsigned long long QKEY_EMPTY = ~0ull;
 // tile kernel: reference positions per tile, LDS table slots, threads.  Measured on S-chr19-10M (profiles/r01_quartet_tile.md):
 // wider tiles re-read fewer halo reads and clear LDS less often, a smaller table lets more tiles share a CU (25 KB each).
 constexpr int QT_NC = 8;   // calls of a read held in registers
@@ -44,11 +44,7 @@ __device__ __forceinline__ unsigned long long qhash(unsigned long long x) {
 }
 
 // slot of a key in the tile kernel's LDS table: two 32-bit multiplies (the 64-bit mixer above costs ~30 VALU)
-__device__ __forceinline__ uint32_t qslot(unsigned long long key) {
-    uint32_t h = (uint32_t)(key >> 33) * 0x9E3779B1u ^ (uint32_t)key * 0x85EBCA6Bu;
-    h ^= h >> 15;
-    return h & (QT_S - 1);
-}
+__device__ __forceinline__ uint32_t qslot(unsigned long long key) { return quartet_slot(key, QT_S - 1); }
 
 // global path: upper bound of the number of (read, window) updates: sum over passing reads of max(0, n - 3)
 __global__ __launch_bounds__(256) void k_quartet_bound(const uint32_t *__restrict__ cpg_off,
@@ -162,31 +158,6 @@ __global__ __launch_bounds__(256) void k_quartet_blockcount(const unsigned long 
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) blk[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// me.rs:42-55 and pm.rs:42-51 with the reference's operation order.  Plain operators, and the whole
-// engine is compiled with -ffp-contract=off: with hipcc's default (contract=fast) `pm - p*p` became an
-// FMA -- HIP's __fmul_rn/__fsub_rn header functions did not prevent it -- and 2.8 % of PM values were
-// one ulp off the reference expression (measured; tools/pm_probe.py).
-__device__ __forceinline__ void quartet_values(const uint32_t *c, float &me, float &pm, uint32_t &total) {
-#pragma clang fp contract(off)
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) total += c[k];
-    const float tf = (float)total;
-    me = 0.0f;
-    pm = 1.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const float p = (float)c[k] / tf;
-        if (c[k] > 0) {
-            const float t = p * log2f(p);
-            me = me + t;
-        }
-        const float sq = p * p;
-        pm = pm - sq;
-    }
-    me = me * -0.25f;
 }
 
 __global__ __launch_bounds__(256) void k_quartet_emit(const unsigned long long *__restrict__ keys,

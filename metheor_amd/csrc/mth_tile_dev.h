@@ -73,6 +73,25 @@ typedef uint32_t u32x4_a2 __attribute__((ext_vector_type(4), aligned(2)));
 // hashed-site form for sparse batches (mth_pdr_wide.hip): shift = log2 of the tile width (14 or 15)
 void launch_tile_wide(const TileArgs &a, uint32_t ntiles, int shift, bool rel8, hipStream_t s);
 
+// The fused PDR + LPMD + ME / PM tile pass (mth_multi.hip): k_pdr_lpmd_wide's outputs plus k_quartet_tile's per-tile quartet rows.
+// Filled in by mth_multi_accumulate and handed to launch_pdr_lpmd through ctx->fuse_q; launch_pdr_lpmd sets taken / ntiles when its
+// wide form ran as the fused pass.
+struct FusedQuartet {
+    uint8_t force;                 // MTH_MULTI_FUSED: the wide form even where launch_pdr_lpmd would take the dense one
+    uint8_t force_heavy;           // tests: every tile is handed back
+    uint8_t min_qual;              // me.rs:115 / pm.rs:110
+    unsigned long long *qs;        // the quartet state words: [1] rows claimed so far, [5] tiles handed back, [6] rows beyond row_cap
+    unsigned long long row_cap;    // rows the quartet outputs hold
+    uint32_t max_tiles;            // tiles the per-tile arrays below hold
+    uint32_t *tile_flag;           // per tile of the batch: 1 = handed back
+    unsigned long long *tile_row0; // per tile: first row ...
+    uint32_t *tile_rows;           // ... and the number of rows
+    int32_t *out_pos; uint32_t *out_cnt; float *out_me, *out_pm; uint32_t *out_depth;
+    bool taken;                    // out: the fused pass ran
+    uint32_t ntiles;               // out: its tiles
+};
+void launch_tile_fused(const TileArgs &a, const FusedQuartet &q, uint32_t ntiles, int shift, bool rel8, hipStream_t s);
+
 struct SlotTabs {
     uint32_t mtab[9][8];
     uint32_t dtab[9][8];
