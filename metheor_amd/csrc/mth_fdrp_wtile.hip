@@ -11,8 +11,9 @@
 //      of the passing reads set bits in a position bitmap of the tile + max_span on either side -- the tile's SITES.
 //   B  prefix popcount over the bitmap: a position's RANK among the window's sites; the core sites' positions.
 //   C1 per call: its rank -> the read's three 32-bit masks (calls, covered calls, methylated covered calls; bit = rank mod 32: a
-//      stored read spans <= 16 ranks here -- else its sites are handed back -- so two reads that share a site never alias) and
-//      the site's reader count, all by LDS atomics.
+//      stored read spans <= 16 ranks here -- else its sites are handed back -- so two reads that share a site never alias), the
+//      read's first and last call rank (the span test takes those, never the folded mask) and the site's reader count, all by
+//      LDS atomics.
 //   C2 per read: the finished row; the flush rule (fdrp.rs:212-223) as an exclusive prefix maximum of the passing reads'
 //      first-call ranks: a reader that has a passing read with a first call beyond the site before it may sit behind a flush
 //      -> the site is handed back.
@@ -29,8 +30,10 @@
 // Only the common shape is computed here; everything else is handed back and stays bit-identical (k_fdrp_walk, call-by-call path):
 // a reader with > 16 calls or spanning > 16 window sites, more readers than min(max_depth, 64) (reservoir: fdrp.rs:87-94), a
 // possible flush between two readers, a site whose terms do not fit the term array.  Spans > 200 bp never come here (host side;
-// add_read's window test, fdrp.rs:58-63).  A stretch with more candidate reads / calls / sites than the LDS arrays hold is redone
-// in halves (down to 192 positions; beyond that every site of the stretch is handed back).
+// add_read's window test, fdrp.rs:58-63).  A stretch with more candidate reads / calls than the LDS arrays hold is redone in halves
+// (down to 192 positions; beyond that every site of the stretch is handed back); one with more sites than FW_SC, in halves down to
+// FW_SC positions, which can hold no more (sites may lie ONE position apart: readutil.rs:332-340 shifts the calls of every flag but
+// 0, 99 and 147 by -1, so a forward read flagged 97 or 1024 | 99 reports the C of a CpG at p - 1, next to its neighbours' p).
 // How it got here, step by step with counters: profiles/r06_wtile_pmc.md.
 #include <algorithm>
 #include <cstdio>
@@ -58,7 +61,7 @@ struct FwArgs {
     uint8_t min_qual;
     uint8_t force_sub;            // tests: start every tile with 192-position stretches
     uint8_t force_heavy;          // tests: every stretch takes the count-only path (all sites handed back)
-    FdRec *scratch;               // rows_per_tile rows per tile
+    FdRec *scratch;               // rows_per_tile (= tile_w) rows per tile
     uint32_t rows_per_tile;
     uint32_t *tile_cnt;
     unsigned long long *bucket;   // rows per 256 tiles
@@ -82,6 +85,7 @@ constexpr int FW_LCAP = 64;                             // stored reads of a sit
 constexpr int FW_NZCAP = 1024;                           // non-zero qFDRP terms of a stretch's sites (more: the site is handed back)
 constexpr int FW_QC = 17 * 18 / 2;                      // codes ncpg (ncpg + 1) / 2 + ham, ham <= ncpg <= 16 (a reader's calls span <= 16 window sites)
 constexpr uint32_t FW_PASS = 1u, FW_BAD = 2u;           // per-read flags
+static_assert(FW_RCAP < 256, "s_owner holds read slot + 1 in a byte");
 
 __global__ void k_fw_quot(float *q) {   // ham / ncpg by the same f32 division the reference does (qfdrp.rs:152); ncpg = 0 is never looked up
     const uint32_t t = threadIdx.x;
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(64, 8) void k_fdrp_wtile(const FwArgs a) {
     constexpr int U = FW_U;
     // 5 KB of LDS per wave: 32 waves per CU (the kernel is bound by each wave's own chain of round trips: what counts is waves in flight)
     __shared__ uint2 s_bp[64 * FW_WPT];                       // {site bits, sites in the words before}; lane l owns words FW_WPT l ..
-    __shared__ __attribute__((aligned(16))) uint32_t s_row[FW_RCAP * 4];   // {start | end << 16, mC, first-call rank -> mA, mM}
+    __shared__ __attribute__((aligned(16))) uint32_t s_row[FW_RCAP * 4];   // {start | end << 16, mC, first | last call rank << 16 -> mA, mM}
     __shared__ uint16_t s_list[FW_LCAP];                      // D1: the readers of the site in hand (byte offsets of their rows, file order)
     __shared__ float s_quot[FW_QC];                           // [ncpg (ncpg + 1) / 2 + ham] = ham / ncpg (a division is ten vector instructions)
     __shared__ __attribute__((aligned(4))) uint8_t s_nz[FW_NZCAP];   // D: the sites' non-zero terms as codes, each site's in the reference's loop order
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(64, 8) void k_fdrp_wtile(const FwArgs a) {
         }
         FW_SYNC();
         // ---- A2: the calls, one per lane (coalesced): its read (the latest owner mark at or before it), the bitmap bit ----
-        uint32_t cwv[FW_V], cown[FW_V];                                              // the call word; read slot + 1 | head << 8 | passing << 9
+        uint32_t cwv[FW_V], cown[FW_V];                                              // the call word; read slot + 1 | head << 8 | passing << 9 | tail << 10
         {
             uint32_t own_carry = 0;
 #pragma unroll
@@ -249,11 +253,12 @@ __global__ __launch_bounds__(64, 8) void k_fdrp_wtile(const FwArgs a) {
                 const bool valid = c < C_n;
                 const uint32_t w = a.cpg_pos[ofirst + (valid ? c : 0u)];
                 const uint32_t own = valid ? (uint32_t)s_owner[c] : 0u;
+                const bool tail = valid && (c + 1u >= C_n || s_owner[c + 1u] != 0u);   // the read's last call: the next call opens another read
                 const uint32_t r1 = max(fw_wave_scan_max_incl(own), own_carry);
                 own_carry = (uint32_t)__builtin_amdgcn_readlane(r1, 63);
                 const uint32_t se = valid ? s_row[(r1 - 1u) * 4u] : 0u;             // (every call has an owner: r1 >= 1)
                 cwv[v] = w;
-                cown[v] = valid ? (r1 | (own ? 1u << 8 : 0u) | (se ? 1u << 9 : 0u)) : 0u;
+                cown[v] = valid ? (r1 | (own ? 1u << 8 : 0u) | (se ? 1u << 9 : 0u) | (tail ? 1u << 10 : 0u)) : 0u;
                 if (se) mark(w, (se & 0xffffu) - 1u);
             }
         }
@@ -275,7 +280,10 @@ __global__ __launch_bounds__(64, 8) void k_fdrp_wtile(const FwArgs a) {
         };
         const uint32_t k0 = __builtin_amdgcn_readfirstlane(rank_of(c_lo)), k1 = __builtin_amdgcn_readfirstlane(rank_of(c_hi));
         const uint32_t ncore = k1 - k0;
-        if (ncore > (uint32_t)FW_SC) { sub_w = max((min(sub_w, Wp) >> 1) & ~15u, 48u); continue; }   // (48 positions hold <= 24 sites)
+        // Too many sites: the same P0 again, narrower.  Progress: a site is a position, so ncore > FW_SC means Wp > FW_SC, and the new
+        // width max(Wp / 2 rounded down to 16, FW_SC) is < Wp; at <= FW_SC positions a stretch holds <= FW_SC sites and goes on.  (The
+        // floor was 48 once -- "sites lie two positions apart" -- and 33 sites in 48 positions never left this loop.)
+        if (ncore > (uint32_t)FW_SC) { sub_w = max((min(sub_w, Wp) >> 1) & ~15u, (uint32_t)FW_SC); continue; }
         // core site positions, rank order
 #pragma unroll
         for (int q = 0; q < FW_WPT; ++q) {
@@ -300,7 +308,7 @@ __global__ __launch_bounds__(64, 8) void k_fdrp_wtile(const FwArgs a) {
             P0l = P1;
             continue;
         }
-        // ---- C1: per call: its rank -> the read's masks (bit = rank mod 32), first-call rank, highest rank ----
+        // ---- C1: per call: its rank -> the read's masks (bit = rank mod 32), first- and last-call rank ----
 #pragma unroll
         for (int v = 0; v < FW_V; ++v) {
             if ((uint32_t)(v * 64) >= C_n) continue;                                // wave-uniform
@@ -312,8 +320,11 @@ __global__ __launch_bounds__(64, 8) void k_fdrp_wtile(const FwArgs a) {
                 atomicOr(&s_row[r * 4 + 1], bit);
                 if (rk - k0 < ncore) atomicAdd(&s_sflag[rk - k0], 1u);                // a core site's passing readers (fdrp.rs:226-231)
                 if (cwv[v] >> 31) atomicOr(&s_row[r * 4 + 3], bit);
-                // the read's first call: its rank; the one call that can lie outside the covered bases, at start - 1 (readutil.rs:332-340)
-                if ((cown[v] >> 8) & 1u) s_row[r * 4 + 2] = rk | ((rel < (s_row[r * 4] & 0xffffu)) ? 0x80000000u : 0u);
+                // the read's first call: its rank, and whether it is the one call that can lie outside the covered bases, at start - 1
+                // (readutil.rs:332-340); its last call: its rank << 16 (ranks < 2^15: the window bitmap has 2048 FW_WPT positions)
+                const uint32_t ends = (((cown[v] >> 8) & 1u) ? rk | ((rel < (s_row[r * 4] & 0xffffu)) ? 0x80000000u : 0u) : 0u) |
+                                      (((cown[v] >> 10) & 1u) ? rk << 16 : 0u);
+                if (ends) atomicOr(&s_row[r * 4 + 2], ends);
             }
         }
         FW_SYNC();
@@ -328,10 +339,10 @@ __global__ __launch_bounds__(64, 8) void k_fdrp_wtile(const FwArgs a) {
             uint32_t mC = 0, r0 = 0;
             if (fl[u] & FW_PASS) {
                 const uint4 row = *reinterpret_cast<const uint4 *>(&s_row[r * 4]);
-                mC = row.y; r0 = row.z & 0x7fffffffu;
-                // its highest rank from the mask (bit = rank mod 32): exact while its ranks span < 32 -- and if they do not, two of its
-                // calls may share a bit: fewer bits than calls
-                const uint32_t span = 31u - (uint32_t)__builtin_clz(__builtin_amdgcn_alignbit(mC, mC, r0 & 31u) | 1u);
+                mC = row.y; r0 = row.z & 0xffffu;
+                // the span from its true first and last call rank (a span read off the folded mask takes calls 33..47 or 65..79 ranks
+                // apart for 1..15); within 16 ranks the bits are distinct, so fewer bits than calls means two calls at one position
+                const uint32_t span = ((row.z >> 16) & 0x7fffu) - r0;
                 if (span > 15u || (uint32_t)__builtin_popcount(mC) != ncall[u]) fl[u] |= FW_BAD;
                 const uint32_t mA = (row.z >> 31) ? mC & ~(1u << (r0 & 31u)) : mC;
                 const uint32_t mM = row.w & mA;
@@ -577,7 +588,8 @@ int launch_fdrp_wtile(mth_ctx *ctx, const mth_batch_t &d, const mth_fdrp_params_
     int rc = build_read_index(ctx, d, W, idx_base, ntiles);
     if (rc) return rc;
     const uint32_t nbk = (ntiles + (1u << TILE_BUCKET_SHIFT) - 1) >> TILE_BUCKET_SHIFT;
-    const uint32_t rows_per_tile = (uint32_t)W / 2u;                                 // CpG sites lie at least two positions apart
+    // a row per core site and a site per position: W rows hold any tile (sites may lie one position apart; W / 2 overflowed)
+    const uint32_t rows_per_tile = (uint32_t)W;
     MTH_HIP(ctx, ctx->tile_cnt.reserve((size_t)ntiles * 4, s));
     MTH_HIP(ctx, ctx->tile_bucket.reserve((size_t)nbk * 5 * sizeof(unsigned long long), s));
     MTH_HIP(ctx, hipMemsetAsync(ctx->tile_bucket.p, 0, (size_t)nbk * sizeof(unsigned long long), s));

@@ -44,6 +44,46 @@ def drop_calls(c, rng, frac):
     return d
 
 
+def pdr_env_forms(seed):
+    """the PDR + LPMD forms a case runs in besides the engine's own choice: the hashed-site form for sparse batches (mth_pdr_wide.hip,
+    a tile width by seed), the dense tile form forced, and its persistent run form (round 5: k_pdr_lpmd_runs + k_gather_runs,
+    MTH_TILE_RUNS=1; it takes the batches with 8-bit relative positions, the others fall back to the tile form)"""
+    return ({"MTH_PDR_WIDE": str(14 + seed % 3)}, {"MTH_PDR_WIDE": "0"}, {"MTH_PDR_WIDE": "0", "MTH_TILE_RUNS": "1"})
+
+
+# the flush rule of MHL looked at per finished row (k_mhl_rowcheck: the host's choice for sparse calls) and per read (position bitmap in
+# the tile kernel), whatever the batch's density, from 256-position sub-ranges and on 32 768-position tiles
+MHL_ENV_FORMS = ({"MTH_MHL_ROWCHK": "1"}, {"MTH_MHL_ROWCHK": "0"}, {"MTH_MHL_ROWCHK": "1", "MTH_MHL_FORCE_SUB": "1"},
+                 {"MTH_MHL_ROWCHK": "1", "MTH_MHL_TILE_SHIFT": "15"})
+
+
+def pdr_forms_same(eng, cs, p, regions, rel16, d, l, forms):
+    """every form of `forms` (environment settings) gives the rows d and the LPMD counters l of the engine's own choice"""
+    import os
+    for envs in forms:
+        os.environ.update(envs)
+        try:
+            d2, l2 = T_pdr.run_device(eng, cs, p, regions=regions, rel16=rel16)
+        finally:
+            for k_ in envs:
+                del os.environ[k_]
+        assert all((d[k].view(np.uint32) == d2[k].view(np.uint32)).all() for k in d) and all(l[k] == l2[k] for k in l if k != "lpmd"), envs
+
+
+def mhl_forms_same(eng, cs, mk, regions, m0, forms=MHL_ENV_FORMS):
+    """every form of `forms` gives the rows m0 of the engine's own choice, bit for bit"""
+    import os
+    for envs in forms:
+        os.environ.update(envs)
+        try:
+            m1 = T_mhl.run_device(eng, cs, mk, regions=regions)
+        finally:
+            for k_ in envs:
+                del os.environ[k_]
+        assert len(m0["pos"]) == len(m1["pos"]), envs
+        assert all((m0[k] == m1[k]).all() for k in ("tid", "pos", "cov")) and (m0["mhl"].view(np.uint32) == m1["mhl"].view(np.uint32)).all(), envs
+
+
 def scenario(seed):
     from metheor_amd import synth
     rng = np.random.default_rng(10_000 + seed)
@@ -111,19 +151,9 @@ def test_random_scenario_all_measures(eng, seed):
     rel16 = bool(rng.integers(0, 2))
     d, l = T_pdr.run_device(eng, cs, p, regions=regions, rel16=rel16)
     T_pdr.check_against_oracle(d, l, reads, pk, lk)
-    # the same through the hashed-site form for sparse batches (mth_pdr_wide.hip) whatever the batch's density, and through the dense
-    # form forced: identical rows and counters
-    import os
-    # ... and through the persistent run form of the dense kernel (round 5: k_pdr_lpmd_runs + k_gather_runs, MTH_TILE_RUNS=1; it takes
-    # the batches with 8-bit relative positions, the others fall back to the tile form)
-    for envs in ({"MTH_PDR_WIDE": str(14 + seed % 3)}, {"MTH_PDR_WIDE": "0"}, {"MTH_PDR_WIDE": "0", "MTH_TILE_RUNS": "1"}):
-        os.environ.update(envs)
-        try:
-            d2, l2 = T_pdr.run_device(eng, cs, p, regions=regions, rel16=rel16)
-        finally:
-            for k_ in envs:
-                del os.environ[k_]
-        assert all((d[k].view(np.uint32) == d2[k].view(np.uint32)).all() for k in d) and all(l[k] == l2[k] for k in l if k != "lpmd"), envs
+    # the same through the hashed-site form for sparse batches whatever the batch's density, the dense form forced and its run form:
+    # identical rows and counters
+    pdr_forms_same(eng, cs, p, regions, rel16, d, l, pdr_env_forms(seed))
 
     # LPMD per-pair table
     T_pairs.check(T_pairs.run_device(eng, cs, lk, regions=regions), reads, lk)
@@ -136,18 +166,7 @@ def test_random_scenario_all_measures(eng, seed):
     mk = dict(min_depth=int(rng.choice([0, 1, 5, 10])), min_cpgs=int(rng.choice([1, 2, 4])), min_qual=mq)
     m0 = T_mhl.run_device(eng, cs, mk, regions=regions)
     T_mhl.check(m0, reads, mk)
-    # ... with the flush rule looked at per finished row (k_mhl_rowcheck: the host's choice for sparse calls) and per read (position
-    # bitmap in the tile kernel), whatever the batch's density: the same rows bit for bit
-    for envs in ({"MTH_MHL_ROWCHK": "1"}, {"MTH_MHL_ROWCHK": "0"}, {"MTH_MHL_ROWCHK": "1", "MTH_MHL_FORCE_SUB": "1"},
-                 {"MTH_MHL_ROWCHK": "1", "MTH_MHL_TILE_SHIFT": "15"}):
-        os.environ.update(envs)
-        try:
-            m1 = T_mhl.run_device(eng, cs, mk, regions=regions)
-        finally:
-            for k_ in envs:
-                del os.environ[k_]
-        assert len(m0["pos"]) == len(m1["pos"]), envs
-        assert all((m0[k] == m1[k]).all() for k in ("tid", "pos", "cov")) and (m0["mhl"].view(np.uint32) == m1["mhl"].view(np.uint32)).all(), envs
+    mhl_forms_same(eng, cs, mk, regions, m0)
 
     # FDRP / qFDRP (a reverse read spanning >= 202 bp can index -1 in the reference and panics there: forward only then)
     fcs, freads = cs, reads
