@@ -106,8 +106,10 @@ def xm_for(pos, flag, ops, site_set, level, rng, drop=None):
     return "".join(out)
 
 
-def make_records(seed, n_contigs=1, length=12_000, n_reads=1_500, density=0.02, **knobs):
-    """-> (Records coordinate-sorted, contig names).  knobs: any of KNOBS set False switches that input class off."""
+def make_records(seed, n_contigs=1, length=12_000, n_reads=1_500, density=0.02, unaligned=False, **knobs):
+    """-> (Records coordinate-sorted, contig names).  knobs: any of KNOBS set False switches that input class off.  unaligned:
+    per contig, also a few records without an aligned base (all-S CIGAR, calls on clipped bases only) and a few without a call
+    (off by default: the draws of every existing seed stay as they were)."""
     k = {n: bool(knobs.get(n, True)) for n in KNOBS}
     unknown = set(knobs) - set(KNOBS)
     assert not unknown, unknown
@@ -138,6 +140,12 @@ def make_records(seed, n_contigs=1, length=12_000, n_reads=1_500, density=0.02, 
             drop = int(rng.integers(4, 60)) if (k["drops"] and rng.random() < 0.3) else None
             xm = xm_for(int(s), fl, ops, site_set, level, rng, drop)
             rows.append((tid, int(s), fl, mq, ops, xm))
+        if unaligned:
+            for s in rng.integers(50, length - 400, size=6):
+                q = int(rng.integers(20, 160))
+                rows.append((tid, int(s), int(rng.choice(FLAGS_PLAIN)), 42, [("S", q)], "".join(rng.choice(list("Zz.."), size=q))))
+            for s in rng.integers(50, length - 400, size=6):
+                rows.append((tid, int(s), int(rng.choice(FLAGS_PLAIN)), 42, [("M", 100)], "." * 100))
     rows.sort(key=lambda r: (r[0], r[1]))                       # stable: ties keep their drawing order
     rec = records_from_rows(refs, rows)
     return rec, [n for n, _ in refs]
@@ -237,3 +245,156 @@ def lpmd_bound_pairs(reads, min_distance, max_distance):
         n_min += int(((dr >= min_distance) != (dp >= min_distance))[up].sum())
         n_max += int(((dr <= max_distance) != (dp <= max_distance))[up].sum())
     return n_min, n_max
+
+
+# ---- file orders: what the unsorted paths replay (tests/test_gpu_irregular_paths.py) -----------------------------------------------
+ORDERS = ("shuffled", "strides", "moved", "nearly", "flush_trap")
+TRAPS = ("far", "low_mapq", "no_call", "other_contig")
+
+
+def rows_of(rec):
+    """bamio.Records -> rows (records_from_rows' input)"""
+    return [(int(rec.tid[i]), int(rec.pos[i]), int(rec.flag[i]), int(rec.mapq[i]), ops_of(rec, i), rec.xms[i].decode()) for i in range(len(rec))]
+
+
+def read_calls(rec):
+    """-> (soa, calls per record, first reported call position per record (-1: none))"""
+    soa = pyoracle.Reads.decode(rec).soa()
+    off = soa["cpg_off"].astype(np.int64)
+    n = np.diff(off)
+    first = np.full(len(n), -1, np.int64)
+    first[n > 0] = (soa["cpg_pos"][off[:-1][n > 0]] & 0x7fffffff).astype(np.int64)
+    return soa, n, first
+
+
+def flush_traps(rec, rng, kinds=TRAPS, per_kind=12, min_qual=10):
+    """the coordinate order of `rec` with, between two consecutive passing readers A, B of a site s, one record moved there from
+    elsewhere -- each a case where flushing by the wrong key or at the wrong step changes what the reference computes:
+      far           passing, same contig, start <= s + 150 < first call: flushes s for PDR (margin 150), MHL and FDRP; by its start it would not
+      low_mapq      below min_qual, calls beyond s: flushes s for MHL only (mhl.rs:162 comes before the filters of :176-183)
+      no_call       no call, same contig, start > s + 150: flushes nothing (by its start it would)
+      other_contig  passing, a later contig: flushes every site of s's contig
+    -> (permutation, [(kind, tid, s, moved record)])"""
+    soa, n, first = read_calls(rec)
+    start, mq, tid = soa["start"].astype(np.int64), soa["mapq"].astype(np.int64), rec.tid.astype(np.int64)
+    off = soa["cpg_off"].astype(np.int64)
+    site = (soa["cpg_pos"] & 0x7fffffff).astype(np.int64)
+    rd = np.repeat(np.arange(len(n)), n)
+    ok = mq[rd] >= min_qual
+    key = tid[rd] << 32 | site
+    o = np.lexsort((rd[ok], key[ok]))
+    k_, r_ = key[ok][o], rd[ok][o]
+    pairs = np.nonzero((k_[1:] == k_[:-1]) & (r_[1:] != r_[:-1]))[0]         # (A, B) = (r_[j], r_[j + 1]): consecutive readers of k_[j]
+    rng.shuffle(pairs)
+    used, after, traps = set(), {}, []
+    want = {kd: per_kind for kd in kinds}
+    for j in pairs:
+        a, b, t, s = int(r_[j]), int(r_[j + 1]), int(k_[j] >> 32), int(k_[j] & 0xffffffff)
+        if a in used or b in used or not any(want.values()):
+            continue
+        for kd in kinds:
+            if not want[kd]:
+                continue
+            if kd == "far":
+                m = (tid == t) & (mq >= 42) & (n >= 4) & (first > s + 150) & (start <= s + 150)
+            elif kd == "low_mapq":
+                m = (tid == t) & (mq < min_qual) & (n >= 1) & (first > s)
+            elif kd == "no_call":
+                m = (tid == t) & (n == 0) & (start > s + 150)
+            else:
+                m = (tid > t) & (mq >= 42) & (n >= 1)
+            c = [int(x) for x in np.nonzero(m)[0] if int(x) not in used]
+            if not c:
+                continue
+            x = c[int(rng.integers(0, len(c)))]
+            used.update((a, b, x))
+            after.setdefault(a, []).append(x)
+            traps.append((kd, t, s, x))
+            want[kd] -= 1
+            break
+    moved = set(x for _, _, _, x in traps)
+    perm = []
+    for i in range(len(n)):
+        if i not in moved:
+            perm.append(i)
+            perm += after.get(i, [])
+    assert sorted(perm) == list(range(len(n)))
+    return np.array(perm), traps
+
+
+def shuffle(rec, kind, rng):
+    """`rec` (coordinate-sorted) in one of ORDERS: the four of tests/test_gpu_fileorder.py (fully shuffled, interleaved sorted
+    strides, blocks of the sorted file moved, nearly sorted with the contigs mixed) and flush_traps -> (Records, permutation)"""
+    n = len(rec)
+    if kind == "shuffled":
+        perm = rng.permutation(n)
+    elif kind == "strides":
+        perm = np.argsort(np.arange(n) % int(rng.integers(2, 9)), kind="stable")
+    elif kind == "moved":
+        perm = np.arange(n)
+        for _ in range(int(rng.integers(2, 6))):
+            a, b = sorted(rng.integers(0, n, size=2))
+            perm = np.concatenate([perm[:a], perm[b:], perm[a:b]])
+    elif kind == "nearly":
+        perm = np.argsort(rec.pos + rng.integers(-60, 60, size=n), kind="stable")
+    elif kind == "flush_trap":
+        perm, _ = flush_traps(rec, rng)
+    else:
+        raise ValueError(kind)
+    return rec.subset(perm), perm
+
+
+def shifted_starts(rec):
+    """the records whose first reported call is at start - 1 (a shifted flag on a read starting at a CpG's C, or a reverse-strand
+    read starting at its G): a shard cut / region end at such a record's start p leaves it a call on the other side"""
+    soa, n, first = read_calls(rec)
+    return np.nonzero((n > 0) & (first == soa["start"].astype(np.int64) - 1))[0]
+
+
+REGION_END = 16384          # a multiple of the .bai's 16-kb leaf bins: a record starting there opens a bin that [.., end) misses
+PILE_AT = 23001
+
+
+def forced_records(seed=3):
+    """two contigs of irregular reads, plus, on the first: a reverse-strand read starting at REGION_END whose first base is the G
+    of the CpG at REGION_END - 1 (reported REGION_END - 1), and a pile of 240 reads starting at PILE_AT, a third of them such
+    readers of PILE_AT - 1; without the reads the reference's FDRP panics on (fdrp_safe) -> (Records coordinate-sorted, names,
+    index of the read at REGION_END)"""
+    rec, names = make_records(seed, n_contigs=2, length=24_000, n_reads=2_400, density=0.03)
+    rng = np.random.default_rng(seed)
+    e = REGION_END
+    planted = [(0, e, 16, 42, [("M", 100)], "z" + "." * 49 + "Z" + "." * 49), (0, e - 1, 0, 42, [("M", 60)], "Z" + "." * 59)]
+    for k in range(240):
+        xm = ["."] * 120
+        if k % 3 == 0:                                             # flag 16: the call at PILE_AT reports PILE_AT - 1
+            xm[0] = "Zz"[k % 2]
+        for q in (11, 12, 40, 41, 90):
+            xm[q] = "Z" if rng.random() < 0.7 else "z"
+        planted.append((0, PILE_AT, 16 if k % 3 == 0 else int(rng.choice([0, 99, 65])), 42, [("M", 120)], "".join(xm)))
+    rows = planted + rows_of(rec)
+    rows.sort(key=lambda r: (r[0], r[1]))
+    out = fdrp_safe(records_from_rows(rec.refs, rows))
+    at = int(np.nonzero((out.tid == 0) & (out.pos == e) & (out.flag == 16))[0][0])
+    return out, names, at
+
+
+def record_blocks(bam):
+    """BGZF block index (from the top of the file, as mth_host_bgzf_blocks counts) of every record of a block-aligned BAM"""
+    recs, _ = bamio.bam_record_offsets(bam)
+    return np.array([r[5] for r in recs], np.int64)
+
+
+def readers(rec, beg, end):
+    """records that report a call at a site in [beg, end) or start in it; beg / end are (tid, pos), compared as tuples"""
+    soa, n, _ = read_calls(rec)
+    site = (soa["cpg_pos"] & 0x7fffffff).astype(np.int64)
+    rd = np.repeat(np.arange(len(n)), n)
+    t = rec.tid.astype(np.int64)
+    lin = lambda tt, p: tt * (1 << 33) + p
+    lo, hi = lin(*beg), lin(*end)
+    c = lin(t[rd], site)
+    s = lin(t, soa["start"].astype(np.int64))
+    keep = np.zeros(len(n), bool)
+    keep[rd[(c >= lo) & (c < hi)]] = True
+    keep |= (s >= lo) & (s < hi) & (soa["start"] >= 0)
+    return np.nonzero(keep)[0]

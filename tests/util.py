@@ -73,31 +73,40 @@ def subset_reads(c, mask):
     return out
 
 
-def reblock_aligned(src, dst):
+def reblock_aligned(src, dst, cut_before=None):
     """rewrite a BAM so that every BGZF block holds whole records (what htslib writes): the header in blocks of its own,
-    then records packed greedily into <= 0xff00-byte blocks"""
+    then records packed greedily into <= 0xff00-byte blocks.  cut_before (record indices, or a predicate on the index): a
+    block is opened before those records too, and otherwise only where the next record would not fit.  -> the index of the
+    first record of every record block"""
     import gzip
     import struct
+    cut = cut_before if (cut_before is None or callable(cut_before)) else set(int(i) for i in cut_before).__contains__
     raw = gzip.decompress(open(src, "rb").read())
     l_text, = struct.unpack_from("<i", raw, 4)
     o = 8 + l_text
     n_ref, = struct.unpack_from("<i", raw, o); o += 4
     for _ in range(n_ref):
         l_name, = struct.unpack_from("<i", raw, o); o += 8 + l_name
+    firsts = []
     with open(dst, "wb") as fh:
         for k in range(0, o, 0xff00):
             fh.write(_bamio()._bgzf_block(raw[k:min(k + 0xff00, o)]))
         blk = bytearray()
+        i = 0
         while o < len(raw):
             bs, = struct.unpack_from("<i", raw, o)
             r = raw[o:o + 4 + bs]
-            if blk and len(blk) + len(r) > 0xff00:
+            if blk and (len(blk) + len(r) > 0xff00 or (cut is not None and cut(i))):
                 fh.write(_bamio()._bgzf_block(bytes(blk))); blk = bytearray()
+            if not blk:
+                firsts.append(i)
             blk += r
             o += 4 + bs
+            i += 1
         if blk:
             fh.write(_bamio()._bgzf_block(bytes(blk)))
         fh.write(_bamio()._bgzf_block(b""))
+    return firsts
 
 
 def _bamio():
