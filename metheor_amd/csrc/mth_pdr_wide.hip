@@ -22,7 +22,11 @@
 // A stretch with more distinct sites than slots is redone in halves (its LPMD sums are only committed when the stretch is done).
 // Same outputs as k_pdr_lpmd_tile (scratch slices, tile_cnt, bucket sums): k_gather and every caller (PDR result columns, site
 // discovery for FDRP) are unchanged.  launch_pdr_lpmd picks the form per batch from its call density.
+//
+// The pass is ONE device body, tile_pass, behind two kernels: k_pdr_lpmd_wide (the above) and k_multi_tile, the same body with the
+// ME / PM quartet side on (the fused pass of `metheor all`; what it adds and when a tile is handed back: mth_multi.hip).
 #include "mth_ctx.h"
+#include "mth_quartet_dev.h"
 #include "mth_tile_dev.h"
 
 namespace mth {
@@ -32,26 +36,37 @@ namespace mth {
 #ifndef MTH_PW_QCAP
 #define MTH_PW_QCAP 3072
 #endif
-constexpr int PW_S = 1024, PW_B = 256, PW_U = 2, PW_NB = 8, PW_QCAP = MTH_PW_QCAP;
-constexpr uint32_t PW_EMPTY = 0xffffffffu;
-
-template <int SHIFT, typename RelT>
 #ifndef MTH_PW_OCC
 #define MTH_PW_OCC 7
 #endif
-__global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileArgs a, const uint32_t ntiles) {
+constexpr int PW_S = 1024, PW_B = 256, PW_U = 2, PW_NB = 8, PW_QCAP = MTH_PW_QCAP;
+constexpr uint32_t PW_EMPTY = 0xffffffffu;
+// the fused form (k_multi_tile): a 512-slot quartet table and a 2048-read queue.  LDS per workgroup ~37.7 KiB (site table 12, quartet
+// table 20, queue 4) -> four workgroups per CU
+constexpr int FQ_S = 512, FQ_OCC = 4, FQ_QCAP = 2048;
+
+// One tile of the pass.  QUARTET: the ME / PM side (k_multi_tile) on top of PDR + LPMD; QCAP: candidate reads per fill of the queue.
+template <int SHIFT, typename RelT, bool QUARTET, int QCAP>
+__device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet &q, const uint32_t ntiles) {
     constexpr int W = 1 << SHIFT;
     constexpr bool PACKED = sizeof(RelT) == 1;                 // 8-bit relpos: the packed pair form
     __shared__ uint32_t tkey[PW_S], tcov[PW_S], tdisc[PW_S];   // the site table; in the row phase: keys / counters in bucket order
     __shared__ uint32_t bcnt[PW_B];
     // the work queue of the read phases shares its LDS with the row phase's bucket bases
-    __shared__ uint32_t q_or_sort[PW_QCAP / 2];
-    static_assert(PW_QCAP / 2 >= PW_B, "bbase fits under the queue");
+    __shared__ uint32_t q_or_sort[QCAP / 2];
+    static_assert(QCAP / 2 >= PW_B, "bbase fits under the queue");
     uint16_t *const rq = reinterpret_cast<uint16_t *>(q_or_sort);
     uint32_t *const bbase = q_or_sort;
     __shared__ uint32_t red[4][PW_B / 64], ws[PW_B / 64 + 1];
     __shared__ __attribute__((aligned(16))) SlotTabs tabs;
     __shared__ uint32_t s_over, s_qn;
+    // QUARTET: the quartet table (k_quartet_tile's: 64-bit key, sixteen 16-bit bins in 8 words); it lives for the whole tile.  (Without
+    // QUARTET nothing refers to these arrays and they take no LDS.)
+    __shared__ unsigned long long qkeys[FQ_S];
+    __shared__ uint32_t qbins[FQ_S * 8];
+    __shared__ uint32_t s_qheavy;
+    static_assert(!QUARTET || QCAP / 2 >= PW_B + FQ_S / 2, "the quartet row phase's bucket bases and source slots fit under the queue");
+    static_assert(QCAP <= 65536, "queue entries are 16-bit read numbers");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // block b runs on XCD b % 8 (observed; speed only): give each XCD a contiguous run of tiles
     const uint32_t per_xcd = (ntiles + 7) / 8;
@@ -64,6 +79,20 @@ __global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileAr
     const RelT *__restrict__ rel = reinterpret_cast<const RelT *>(a.cpg_rel);
     SiteRec *__restrict__ out = a.scratch + (size_t)t * W;
     slot_tabs_init(tabs, tid);
+    if constexpr (QUARTET) {
+        for (int i = tid; i < FQ_S; i += PW_B) qkeys[i] = QKEY_EMPTY;
+        for (int i = tid; i < FQ_S * 8; i += PW_B) qbins[i] = 0u;
+        // the tile's candidate reads (the first stretch is the whole tile): a bin counts at most one update per read -> 16 bits hold
+        // 65535 candidates (k_quartet_tile's rule); beyond that, or on a test's request, the tile is handed back
+        const uint32_t lo = min(a.idx[((uint32_t)T0 - (uint32_t)a.max_span + 1u - (uint32_t)a.idx_base) >> IDX_QSHIFT], a.n_reads);
+        const uint32_t hi = min(a.idx[(((uint32_t)T1 - (uint32_t)a.idx_base) >> IDX_QSHIFT) + 1], a.n_reads);
+        if (tid == 0) s_qheavy = (hi > lo && hi - lo > 65535u) || q.force_heavy ? 1u : 0u;
+    }
+    // one window of four consecutive calls into the tile's quartet table
+    auto window = [&](const uint32_t x, const uint32_t y, const uint32_t z, const uint32_t w) {
+        if (quartet_window<FQ_S>(x, y, z, w, T0, T1, qkeys, qbins) == QW_HAND_BACK) s_qheavy = 1u;
+    };
+    bool q_on = QUARTET;                                     // block-uniform: the quartet side is fed by the tile's first stretch only
     // (distances between live calls are < 2^16, so capping max_distance keeps dead-slot differences outside)
     const int32_t maxd = PACKED ? min(a.max_dist, 255) : min(a.max_dist, 1 << 20);   // 8-bit relpos: no distance beyond 255
     const int32_t mind = max(a.min_dist, 0);
@@ -83,8 +112,8 @@ __global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileAr
         if (tid == 0) { s_over = 0u; s_qn = 0u; }
         __syncthreads();
         uint32_t a_c = 0, a_d = 0, a_r = 0, a_v = 0;           // this attempt's LPMD sums
-        for (uint32_t c0 = lo; c0 < hi; c0 += PW_QCAP) {
-            const uint32_t c1 = min(c0 + (uint32_t)PW_QCAP, hi);
+        for (uint32_t c0 = lo; c0 < hi; c0 += QCAP) {
+            const uint32_t c1 = min(c0 + (uint32_t)QCAP, hi);
             if (c0 != lo) {
                 __syncthreads();                               // the previous stretch's queue is done with
                 if (tid == 0) s_qn = 0u;
@@ -118,7 +147,8 @@ __global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileAr
                     if (a.want_lpmd && owned) { a_r += 1; a_v += lp_ok ? 1u : 0u; }
                     // pdr.rs:147-157
                     const bool pdr_ok = a.want_pdr && n >= a.min_cpgs && mq[u] >= a.pdr_min_qual && n > 0;
-                    const bool work = (lp_ok && lp_possible && n > 1) || pdr_ok;
+                    const bool q_ok = q_on && in && n >= 4 && mq[u] >= q.min_qual;       // readutil.rs:101, me.rs:115
+                    const bool work = (lp_ok && lp_possible && n > 1) || pdr_ok || q_ok;
                     const unsigned long long bal = __ballot(work);
                     if (bal) {
                         uint32_t base = 0;
@@ -291,11 +321,29 @@ __global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileAr
                     if (any_long && go && n > (uint32_t)PW_NB)
                         for (uint32_t k = PW_NB; k < n; ++k) insert(a.cpg_pos[o0 + k]);
                 }
+                // ME / PM from the same calls: the live slots of v[] are the read's own words (dead slots were overwritten above)
+                const bool q_ok = q_on && act && n >= 4 && mq >= q.min_qual;
+                if (QUARTET && __any(q_ok)) {
+#pragma unroll
+                    for (int k = 3; k < PW_NB; ++k) {
+                        if (!__any(q_ok && (uint32_t)k < n)) break;        // wave-uniform
+                        if (q_ok && (uint32_t)k < n) window(v[k - 3], v[k - 2], v[k - 1], v[k]);
+                    }
+                    if (any_long && q_ok && n > (uint32_t)PW_NB) {
+                        uint32_t x = v[PW_NB - 3], y = v[PW_NB - 2], z = v[PW_NB - 1];
+                        for (uint32_t k = PW_NB; k < n; ++k) {
+                            const uint32_t w = a.cpg_pos[o0 + k];
+                            window(x, y, z, w);
+                            x = y; y = z; z = w;
+                        }
+                    }
+                }
             }
         }
         __syncthreads();
         const uint32_t over = s_over;
         __syncthreads();                                    // (s_over is cleared at the top of the next trip; the queue is done with)
+        q_on = false;                                       // the whole tile's quartets are in the table (the first stretch is the tile)
         if (over && sub_shift > 8) { --sub_shift; continue; }      // more distinct sites than slots: the same stretch again in halves
         if (over) bad |= 2u;                                // cannot happen: 256 positions, 1024 slots
         lp_c += a_c; lp_d += a_d; n_read += a_r; n_valid += a_v;
@@ -342,6 +390,26 @@ __global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileAr
         P0l = P1;
         __syncthreads();                                    // the table is cleared by the next trip
     }
+    // ---- quartet rows (k_quartet_tile's row phase, 256 buckets of the slice): one claim per tile; a handed-back tile is only counted
+    if constexpr (QUARTET) {
+        bcnt[tid] = 0u;
+        __syncthreads();
+        const bool heavy = s_qheavy != 0u;                  // block-uniform
+        uint16_t *const sslot = reinterpret_cast<uint16_t *>(q_or_sort + PW_B);
+        auto claim_rows = [&](const uint32_t n_all) {
+            unsigned long long r0 = 0ull;
+            if (heavy) atomicAdd(q.qs + 5, 1ull);
+            else if (n_all) {
+                r0 = atomicAdd(q.qs + 1, (unsigned long long)n_all);
+                if (r0 + n_all > q.row_cap) atomicAdd(q.qs + 6, 1ull);      // (cannot happen: the host sizes for every call of the batch)
+            }
+            q.tile_flag[t] = heavy ? 1u : 0u; q.tile_rows[t] = n_all; q.tile_row0[t] = r0;
+            return r0;
+        };
+        quartet_rows<FQ_S, PW_B, SHIFT - 8>(qkeys, qbins, bcnt, bbase, sslot, ws, T0, !heavy, claim_rows, q.row_cap, q.out_pos, q.out_cnt,
+                                            q.out_me, q.out_pm, q.out_depth);
+        __syncthreads();
+    }
     if (bad & 1u) atomicOr(const_cast<uint32_t *>(&a.st->err), (uint32_t)ERRB_SPAN);
     if (bad & 2u) atomicOr(const_cast<uint32_t *>(&a.st->err), (uint32_t)ERRB_CAPACITY);
     // LPMD partials: wave sums -> LDS -> one atomic per counter into the tile's bucket
@@ -361,18 +429,31 @@ __global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileAr
     }
 }
 
-void launch_tile_wide(const TileArgs &a, uint32_t ntiles, int shift, bool rel8, hipStream_t s) {
+template <int SHIFT, typename RelT>
+__global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileArgs a, const uint32_t ntiles) {
+    tile_pass<SHIFT, RelT, false, PW_QCAP>(a, FusedQuartet{}, ntiles);
+}
+template <int SHIFT, typename RelT>
+__global__ __launch_bounds__(PW_B, FQ_OCC) void k_multi_tile(const TileArgs a, const FusedQuartet q, const uint32_t ntiles) {
+    tile_pass<SHIFT, RelT, true, FQ_QCAP>(a, q, ntiles);
+}
+
+// the shift x rel8 switch of both forms (q: the fused form's quartet side)
+template <bool QUARTET, int SHIFT, typename RelT>
+static void launch_tile_as(const TileArgs &a, const FusedQuartet *q, uint32_t ntiles, hipStream_t s) {
     const uint32_t grid = ((ntiles + 7) / 8) * 8;   // whole rows of 8 XCDs (remap in the kernel)
-    if (shift == 14) {
-        if (rel8) hipLaunchKernelGGL((k_pdr_lpmd_wide<14, uint8_t>), dim3(grid), dim3(PW_B), 0, s, a, ntiles);
-        else hipLaunchKernelGGL((k_pdr_lpmd_wide<14, uint16_t>), dim3(grid), dim3(PW_B), 0, s, a, ntiles);
-    } else if (shift == 16) {
-        if (rel8) hipLaunchKernelGGL((k_pdr_lpmd_wide<16, uint8_t>), dim3(grid), dim3(PW_B), 0, s, a, ntiles);
-        else hipLaunchKernelGGL((k_pdr_lpmd_wide<16, uint16_t>), dim3(grid), dim3(PW_B), 0, s, a, ntiles);
-    } else {
-        if (rel8) hipLaunchKernelGGL((k_pdr_lpmd_wide<15, uint8_t>), dim3(grid), dim3(PW_B), 0, s, a, ntiles);
-        else hipLaunchKernelGGL((k_pdr_lpmd_wide<15, uint16_t>), dim3(grid), dim3(PW_B), 0, s, a, ntiles);
-    }
+    if constexpr (QUARTET) hipLaunchKernelGGL((k_multi_tile<SHIFT, RelT>), dim3(grid), dim3(PW_B), 0, s, a, *q, ntiles);
+    else hipLaunchKernelGGL((k_pdr_lpmd_wide<SHIFT, RelT>), dim3(grid), dim3(PW_B), 0, s, a, ntiles);
+}
+template <bool QUARTET>
+static void launch_tile(const TileArgs &a, const FusedQuartet *q, uint32_t ntiles, int shift, bool rel8, hipStream_t s) {
+    if (shift == 14) rel8 ? launch_tile_as<QUARTET, 14, uint8_t>(a, q, ntiles, s) : launch_tile_as<QUARTET, 14, uint16_t>(a, q, ntiles, s);
+    else if (shift == 16) rel8 ? launch_tile_as<QUARTET, 16, uint8_t>(a, q, ntiles, s) : launch_tile_as<QUARTET, 16, uint16_t>(a, q, ntiles, s);
+    else rel8 ? launch_tile_as<QUARTET, 15, uint8_t>(a, q, ntiles, s) : launch_tile_as<QUARTET, 15, uint16_t>(a, q, ntiles, s);
+}
+void launch_tile_wide(const TileArgs &a, uint32_t ntiles, int shift, bool rel8, hipStream_t s) { launch_tile<false>(a, nullptr, ntiles, shift, rel8, s); }
+void launch_tile_fused(const TileArgs &a, const FusedQuartet &q, uint32_t ntiles, int shift, bool rel8, hipStream_t s) {
+    launch_tile<true>(a, &q, ntiles, shift, rel8, s);
 }
 
 }  // namespace mth

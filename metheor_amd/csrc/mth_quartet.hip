@@ -43,9 +43,6 @@ __device__ __forceinline__ unsigned long long qhash(unsigned long long x) {
     return x;
 }
 
-// slot of a key in the tile kernel's LDS table: two 32-bit multiplies (the 64-bit mixer above costs ~30 VALU)
-__device__ __forceinline__ uint32_t qslot(unsigned long long key) { return quartet_slot(key, QT_S - 1); }
-
 // global path: upper bound of the number of (read, window) updates: sum over passing reads of max(0, n - 3)
 __global__ __launch_bounds__(256) void k_quartet_bound(const uint32_t *__restrict__ cpg_off,
                                                        const uint8_t *__restrict__ mapq, uint32_t n_reads,
@@ -251,7 +248,6 @@ __global__ __launch_bounds__(QT_B, QT_OCC) void k_quartet_tile(const QTileArgs a
     __shared__ uint32_t s_qn;
     __shared__ uint32_t bins[QT_S * 8];        // bin 2w in the low half of word w, bin 2w+1 in the high half
     __shared__ uint32_t s_heavy, ws[QT_B / 64 + 1];
-    __shared__ unsigned long long s_row0;
     __shared__ unsigned long long s_chunk_pos, s_chunk_end;   // rows claimed from the global counter, handed out tile by tile
     const int tid = threadIdx.x;
     if (tid == 0) { s_chunk_pos = 0; s_chunk_end = 0; }
@@ -276,28 +272,9 @@ __global__ __launch_bounds__(QT_B, QT_OCC) void k_quartet_tile(const QTileArgs a
     __syncthreads();
     if (!s_heavy) {
         uint32_t bad = 0;
-        // one window of four consecutive calls (readutil.rs:105-129) into the tile's table; the quartet belongs to the tile of p1
+        // one window of four consecutive calls into the tile's table
         auto window = [&](const uint32_t x, const uint32_t y, const uint32_t z, const uint32_t w) {
-            const int32_t p1 = (int32_t)(x & 0x7fffffffu);
-            if (p1 < T0 || p1 >= T1) return;
-            const uint32_t d2 = (y & 0x7fffffffu) - (x & 0x7fffffffu), d3 = (z & 0x7fffffffu) - (y & 0x7fffffffu),
-                           d4 = (w & 0x7fffffffu) - (z & 0x7fffffffu);
-            const unsigned long long key = ((unsigned long long)(uint32_t)p1 << 33) | ((unsigned long long)d2 << 22) |
-                                           ((unsigned long long)d3 << 11) | (unsigned long long)d4;
-            if (d2 - 1u >= 2047u || d3 - 1u >= 2047u || d4 - 1u >= 2047u || key == QKEY_EMPTY) {
-                s_heavy = 1u;                                        // CpGs >= 2048 bp apart (or out of order): the global path sorts it out
-                return;
-            }
-            const uint32_t pat = ((x >> 31) << 3) | ((y >> 31) << 2) | ((z >> 31) << 1) | (w >> 31);
-            uint32_t h = qslot(key), probes = 0;
-            bool placed = false;
-            while (probes++ < (uint32_t)QT_S) {
-                const unsigned long long cur = atomicCAS(&keys[h], QKEY_EMPTY, key);
-                if (cur == QKEY_EMPTY || cur == key) { placed = true; break; }
-                h = (h + 1) & (QT_S - 1);
-            }
-            if (placed) atomicAdd(&bins[h * 8 + (pat >> 1)], (pat & 1u) ? 0x10000u : 1u);      // me.rs:121-125
-            else s_heavy = 1u;                                   // more distinct quartets than slots
+            if (quartet_window<QT_S>(x, y, z, w, T0, T1, keys, bins) == QW_HAND_BACK) s_heavy = 1u;
         };
         // Two phases per stretch of QT_QCAP candidate reads.  Phase 1, every candidate (offsets one round ahead, mapq): the reads with
         // >= 4 CpGs that pass mapq (readutil.rs:101, me.rs:115) -- a third of config 2's reads, a twentieth at WGBS density -- are
@@ -393,36 +370,8 @@ __global__ __launch_bounds__(QT_B, QT_OCC) void k_quartet_tile(const QTileArgs a
         if (tid == 0) { a.tile_flag[t] = 1u; a.tile_rows[t] = 0u; a.tile_row0[t] = 0ull; atomicAdd(a.n_heavy, 1ull); }
         continue;
     }
-    // Rows go out sorted by key = (p1, d2, d3, d4) = (p1, p2, p3, p4).  Bucket sort on p1: QT_B buckets of QT_W / QT_B
-    // positions, a few keys each.  Every thread holds its slots in registers, so the table is rebuilt in place in bucket
-    // order; a key's final rank = start of its bucket + the keys of that bucket below it.  (Before: an all-pairs rank
-    // sort / bitonic network over the tile's keys -- most of the kernel's time on sparse WGBS.)
-    static_assert(QT_S % QT_B == 0 && QT_B == 256, "each thread owns QT_S / QT_B slots and one bucket");
-    constexpr int PER = QT_S / QT_B;
-    constexpr int BSHIFT = __builtin_ctz((unsigned)QT_W) - 8;
-    unsigned long long kk[PER];
-    uint32_t pib[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        kk[k] = keys[tid * PER + k];
-        pib[k] = 0;
-        if (kk[k] != QKEY_EMPTY) pib[k] = atomicAdd(&bcnt[((uint32_t)(kk[k] >> 33) - (uint32_t)T0) >> BSHIFT], 1u);
-    }
-    __syncthreads();                                    // every slot is in registers now: the table can be overwritten
-    const int lane = tid & 63, wave = tid >> 6;
-    const uint32_t m = bcnt[tid];
-    uint32_t incl = m;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) ws[wave + 1] = incl;
-    __syncthreads();
-    if (tid == 0) {
-        ws[0] = 0;
-        for (int w = 1; w <= QT_B / 64; ++w) ws[w] += ws[w - 1];
-        const uint32_t n_all = ws[QT_B / 64];
+    // thread 0 hands the tile its rows out of the workgroup's chunk
+    auto claim_rows = [&](const uint32_t n_all) {
         a.tile_flag[t] = 0u; a.tile_rows[t] = n_all;
         if (n_all && s_chunk_pos + n_all > s_chunk_end) {       // next chunk (what is left of the old one stays unused)
             // enough for this workgroup's remaining tiles if they are like this one, at most QT_CHUNK rows: the gaps stay
@@ -433,52 +382,17 @@ __global__ __launch_bounds__(QT_B, QT_OCC) void k_quartet_tile(const QTileArgs a
             s_chunk_end = s_chunk_pos + claim;
             if (s_chunk_end > a.row_cap) atomicAdd(a.unfit, 1ull);
         }
-        s_row0 = s_chunk_pos;
+        const unsigned long long row0 = s_chunk_pos;
         s_chunk_pos += n_all;
-        a.tile_row0[t] = s_row0;
-    }
-    __syncthreads();
-    const uint32_t n = ws[QT_B / 64];
-    if (n == 0 || s_row0 + n > a.row_cap) continue;      // block-uniform
-    bbase[tid] = ws[wave] + incl - m;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        if (kk[k] == QKEY_EMPTY) continue;
-        const uint32_t dst = bbase[((uint32_t)(kk[k] >> 33) - (uint32_t)T0) >> BSHIFT] + pib[k];
-        keys[dst] = kk[k];
-        sslot[dst] = (uint16_t)(tid * PER + k);
-    }
-    __syncthreads();
-    for (uint32_t j = tid; j < n; j += QT_B) {
-        const unsigned long long key = keys[j];
-        const uint32_t bk = ((uint32_t)(key >> 33) - (uint32_t)T0) >> BSHIFT, b0 = bbase[bk], b1 = b0 + bcnt[bk];
-        uint32_t r = b0;
-        for (uint32_t i = b0; i < b1; ++i) r += keys[i] < key ? 1u : 0u;
-        const uint32_t h = sslot[j];
-        const unsigned long long o = s_row0 + r;
-        const int32_t p1 = (int32_t)(key >> 33);
-        const int32_t p2 = p1 + (int32_t)((key >> 22) & 2047u), p3 = p2 + (int32_t)((key >> 11) & 2047u),
-                      p4 = p3 + (int32_t)(key & 2047u);
-        reinterpret_cast<int4 *>(a.out_pos)[o] = make_int4(p1, p2, p3, p4);
-        uint32_t c[16];
-#pragma unroll
-        for (int w = 0; w < 8; ++w) {
-            const uint32_t v = bins[h * 8 + w];
-            c[2 * w] = v & 0xffffu; c[2 * w + 1] = v >> 16;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            reinterpret_cast<uint4 *>(a.out_cnt + o * 16)[q] = make_uint4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]);
-        float me, pm;
-        uint32_t total;
-        quartet_values(c, me, pm, total);
-        a.out_me[o] = me; a.out_pm[o] = pm; a.out_depth[o] = total;
-    }
+        a.tile_row0[t] = row0;
+        return row0;
+    };
+    quartet_rows<QT_S, QT_B, __builtin_ctz((unsigned)QT_W) - 8>(keys, bins, bcnt, bbase, sslot, ws, T0, true, claim_rows, a.row_cap, a.out_pos,
+                                                                a.out_cnt, a.out_me, a.out_pm, a.out_depth);
     }
 }
 
-// (re)start of a batch: back to the row count before it
+// (re)start of a batch: back to the row count before it (also the start of a fused batch, mth_multi.hip)
 __global__ void k_quartet_rewind(unsigned long long *qs, unsigned long long rows_before) { qs[1] = rows_before; qs[5] = 0; qs[6] = 0; }
 
 // a queued batch's state words as its tile kernel left them ([1] rows so far, [5] tiles for the global path and [6] tiles that did not

@@ -1,4 +1,5 @@
-// mth_tile_dev.h -- device helpers shared by the PDR + LPMD kernels (mth_pdr_lpmd.hip: dense tile kernel, mth_pdr_wide.hip: hashed-site form).
+// mth_tile_dev.h -- device helpers shared by the PDR + LPMD kernels (mth_pdr_lpmd.hip: dense tile kernel, mth_pdr_wide.hip: hashed-site form
+// and, from the same body, the fused PDR + LPMD + ME / PM kernel).
 #pragma once
 #include "mth_common.h"
 
@@ -73,7 +74,8 @@ typedef uint32_t u32x4_a2 __attribute__((ext_vector_type(4), aligned(2)));
 // hashed-site form for sparse batches (mth_pdr_wide.hip): shift = log2 of the tile width (14 or 15)
 void launch_tile_wide(const TileArgs &a, uint32_t ntiles, int shift, bool rel8, hipStream_t s);
 
-// The fused PDR + LPMD + ME / PM tile pass (mth_multi.hip): k_pdr_lpmd_wide's outputs plus k_quartet_tile's per-tile quartet rows.
+// The fused PDR + LPMD + ME / PM tile pass (k_multi_tile, mth_pdr_wide.hip: the wide form's body with the quartet side on; host side in
+// mth_multi.hip): k_pdr_lpmd_wide's outputs plus k_quartet_tile's per-tile quartet rows.
 // Filled in by mth_multi_accumulate and handed to launch_pdr_lpmd through ctx->fuse_q; launch_pdr_lpmd sets taken / ntiles when its
 // wide form ran as the fused pass.
 struct FusedQuartet {
