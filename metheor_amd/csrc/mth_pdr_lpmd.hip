@@ -392,7 +392,7 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
         const bool more = inext < hi;
         uint32_t v[NB];
         int32_t r[NB];
-        uint32_t rraw0 = 0, rraw1 = 0;                         // PACKED, !CLAMP: the 8 relpos bytes as loaded
+        uint32_t rraw0 = 0, rraw1 = 0;                         // PACKED: the 8 relpos bytes as they lie in memory
         uint32_t o0n = 0, o1n = 0;
         if constexpr (PF) {
             n = o1 - o0;
@@ -442,7 +442,11 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
                 for (int k = 0; k < NB; ++k) v[k] = cp[min((uint32_t)k, n - 1)];
                 if (any_lp) {
 #pragma unroll
-                    for (int k = 0; k < NB; ++k) r[k] = (int32_t)rp[min((uint32_t)k, n - 1)];
+                    for (int k = 0; k < NB; ++k) {
+                        const uint32_t rv = (uint32_t)rp[min((uint32_t)k, n - 1)];
+                        if constexpr (PACKED) { if (k < 4) rraw0 |= rv << (8 * k); else rraw1 |= rv << (8 * (k - 4)); }      // (the repeated last byte sits in dead slots)
+                        else r[k] = (int32_t)rv;
+                    }
                 }
             }
         // Every instruction type issues from the same few waves here (profiles/r01_tile_variants.md: the
@@ -508,53 +512,7 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
         // walk the pair matrix by diagonals g = 1, 2, .. and stop once NO lane of the wave has a pair
         // within max_distance on the current diagonal (wave-uniform break).
         if constexpr (PACKED) {
-            if (any_lp) {
-                // packed call states (bit 15 of each field; the other bits of the top bytes are ignored by the masks below)
-                uint32_t SQ[4], SO[4], Q[4], O[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) SQ[e] = __builtin_amdgcn_perm(v[2 * e + 1], v[2 * e], 0x070c030cu);
-#pragma unroll
-                for (int e = 0; e < 3; ++e) SO[e] = __builtin_amdgcn_perm(v[2 * e + 2], v[2 * e + 1], 0x070c030cu);
-                SO[3] = __builtin_amdgcn_perm(0u, v[7], 0x070c030cu);
-                if (!CLAMP) {
-                    Q[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c010c00u); Q[1] = __builtin_amdgcn_perm(0u, rraw0, 0x0c030c02u);
-                    Q[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c010c00u); Q[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c030c02u);
-                    O[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c020c01u); O[1] = __builtin_amdgcn_perm(rraw1, rraw0, 0x0c040c03u);
-                    O[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c020c01u); O[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c0c0c03u);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) Q[e] = (uint32_t)r[2 * e] | ((uint32_t)r[2 * e + 1] << 16);
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) O[e] = (uint32_t)r[2 * e + 1] | ((uint32_t)r[2 * e + 2] << 16);
-                    O[3] = (uint32_t)r[7];
-                }
-                {
-                    const uint4 da = reinterpret_cast<const uint4 *>(&tabs.dtab[n_lp][0])[0], db = reinterpret_cast<const uint4 *>(&tabs.dtab[n_lp][0])[1];
-                    Q[0] += da.x; Q[1] += da.y; Q[2] += da.z; Q[3] += da.w; O[0] += db.x; O[1] += db.y; O[2] += db.z; O[3] += db.w;
-                }
-                const uint32_t KA = (0x8000u - (uint32_t)mind) * 0x10001u, KB = (0x8000u + (uint32_t)maxd) * 0x10001u;
-                uint32_t accIN = 0, accDD = 0;
-#pragma unroll
-                for (int g = 1; g < 8; ++g) {
-                    uint32_t orB = 0;
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const int li = (g & 1) ? (g - 1) / 2 + m : g / 2 + m;      // index of the later operand in O (g odd) / Q (g even)
-                        if (li > 3) break;
-                        const uint32_t later = (g & 1) ? O[li] : Q[li], sl = (g & 1) ? SO[li] : SQ[li];
-                        const uint32_t D = later - Q[m];
-                        const uint32_t Bw = KB - D;
-                        const uint32_t IN = __builtin_amdgcn_bitop3_b32(D + KA, Bw, 0x80008000u, 0x80);   // min <= distance <= max (readutil.rs:184, 196)
-                        const uint32_t DD = IN & (sl ^ SQ[m]);
-                        accIN += __builtin_popcount(IN);        // v_bcnt_u32_b32 adds its second operand: one instruction per count
-                        accDD += __builtin_popcount(DD);
-                        orB |= Bw;
-                    }
-                    if (!__any((orB & 0x80008000u) != 0u)) break;      // no lane has a pair within max_distance on this diagonal
-                }
-                lp_c += accIN - accDD;
-                lp_d += accDD;
-            }
+            if (any_lp) lpmd_pairs8(v, rraw0, rraw1, n_lp, tabs, mind, maxd, lp_c, lp_d);
         } else if (any_lp) {
             const uint32_t span_ok = (uint32_t)(maxd - a.min_dist);
             uint32_t lp_n = 0, lp_dd = 0;
@@ -926,7 +884,6 @@ __global__ __launch_bounds__(256, MTH_RUNS_OCC) void k_pdr_lpmd_runs(const TileA
     const int32_t maxd = min(a.max_dist, 255);
     const int32_t mind = max(a.min_dist, 0);
     const bool lp_range = maxd >= a.min_dist && maxd >= 0;
-    const uint32_t KA = (0x8000u - (uint32_t)mind) * 0x10001u, KB = (0x8000u + (uint32_t)maxd) * 0x10001u;
 
     // per-thread LPMD counters across the run.  nrv: reads owned (bits 0-14), of them with mapq >= min_qual (bits 15-29), a span
     // violation seen (bit 31).  Moved to the wave's 64-bit sums in LDS when a lane nears its field's top.
@@ -1047,7 +1004,7 @@ __global__ __launch_bounds__(256, MTH_RUNS_OCC) void k_pdr_lpmd_runs(const TileA
                         }
                     }
                     nrv |= bad_it << 31;
-                    if (any_lp) {       // windowed pair counts, two pairs per instruction (see tile_pass)
+                    if (any_lp) {       // windowed pair counts (see tile_pass)
                         if (__any(o0 + 8u > a.n_cpgs)) {      // the batch's last few reads: the bounds check drops whole dwords of a window that crosses the end
                             if (o0 + 8u > a.n_cpgs) {
                                 const uint8_t *__restrict__ rel = reinterpret_cast<const uint8_t *>(a.cpg_rel);
@@ -1059,41 +1016,7 @@ __global__ __launch_bounds__(256, MTH_RUNS_OCC) void k_pdr_lpmd_runs(const TileA
                                 }
                             }
                         }
-                        uint32_t SQ[4], SO[4], Q[4], O[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) SQ[e] = __builtin_amdgcn_perm(v[2 * e + 1], v[2 * e], 0x070c030cu);
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) SO[e] = __builtin_amdgcn_perm(v[2 * e + 2], v[2 * e + 1], 0x070c030cu);
-                        SO[3] = __builtin_amdgcn_perm(0u, v[7], 0x070c030cu);
-                        Q[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c010c00u); Q[1] = __builtin_amdgcn_perm(0u, rraw0, 0x0c030c02u);
-                        Q[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c010c00u); Q[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c030c02u);
-                        O[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c020c01u); O[1] = __builtin_amdgcn_perm(rraw1, rraw0, 0x0c040c03u);
-                        O[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c020c01u); O[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c0c0c03u);
-                        {
-                            const uint4 da = reinterpret_cast<const uint4 *>(&tabs.dtab[n_lp][0])[0], db = reinterpret_cast<const uint4 *>(&tabs.dtab[n_lp][0])[1];
-                            Q[0] += da.x; Q[1] += da.y; Q[2] += da.z; Q[3] += da.w; O[0] += db.x; O[1] += db.y; O[2] += db.z; O[3] += db.w;
-                        }
-                        uint32_t accIN = 0, accDD = 0;
-#pragma unroll
-                        for (int g = 1; g < 8; ++g) {
-                            uint32_t orB = 0;
-#pragma unroll
-                            for (int m = 0; m < 4; ++m) {
-                                const int li = (g & 1) ? (g - 1) / 2 + m : g / 2 + m;
-                                if (li > 3) break;
-                                const uint32_t later = (g & 1) ? O[li] : Q[li], sl = (g & 1) ? SO[li] : SQ[li];
-                                const uint32_t D = later - Q[m];
-                                const uint32_t Bw = KB - D;
-                                const uint32_t IN = __builtin_amdgcn_bitop3_b32(D + KA, Bw, 0x80008000u, 0x80);   // readutil.rs:184, 196
-                                const uint32_t DD = IN & (sl ^ SQ[m]);
-                                accIN += __builtin_popcount(IN);
-                                accDD += __builtin_popcount(DD);
-                                orB |= Bw;
-                            }
-                            if (!__any((orB & 0x80008000u) != 0u)) break;
-                        }
-                        lp_c += accIN - accDD;
-                        lp_d += accDD;
+                        lpmd_pairs8(v, rraw0, rraw1, n_lp, tabs, mind, maxd, lp_c, lp_d);
                     }
                     if (any_long && lp_ok && n > (uint32_t)NB) {      // pairs whose later call is the 9th or beyond: from memory (rare)
                         const uint8_t *__restrict__ rel = reinterpret_cast<const uint8_t *>(a.cpg_rel);

@@ -16,7 +16,7 @@
 //             owns, and the reads that have work -- LPMD pairs (>= 2 calls, mapq) or PDR (>= min_cpgs calls, mapq; pdr.rs:147-157)
 //             -- into a queue of 16-bit read numbers.  At WGBS depth that is 40 % of the reads.
 //   phase 2   the queue with every lane live: the read's first 8 calls as two 16-byte loads + its relative positions, the
-//             concordance state, the windowed pair counts two pairs per instruction (the tile kernel's packed form) and, for a
+//             concordance state, the windowed pair counts (lpmd_pairs8, mth_tile_dev.h: the tile kernel's form) and, for a
 //             PDR-passing read, one compare-and-swap + one or two LDS adds per call.
 //   rows      slots with coverage >= min_depth, bucket sort by position, straight into the tile's scratch slice.
 // A stretch with more distinct sites than slots is redone in halves (its LPMD sums are only committed when the stretch is done).
@@ -227,42 +227,7 @@ __device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet 
                 if (__any(lp_ok)) {
                     const uint32_t n_lp = lp_ok ? min(n, (uint32_t)PW_NB) : 0u;
                     if constexpr (PACKED) {
-                        uint32_t SQ[4], SO[4], Q[4], O[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) SQ[e] = __builtin_amdgcn_perm(v[2 * e + 1], v[2 * e], 0x070c030cu);
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) SO[e] = __builtin_amdgcn_perm(v[2 * e + 2], v[2 * e + 1], 0x070c030cu);
-                        SO[3] = __builtin_amdgcn_perm(0u, v[7], 0x070c030cu);
-                        Q[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c010c00u); Q[1] = __builtin_amdgcn_perm(0u, rraw0, 0x0c030c02u);
-                        Q[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c010c00u); Q[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c030c02u);
-                        O[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c020c01u); O[1] = __builtin_amdgcn_perm(rraw1, rraw0, 0x0c040c03u);
-                        O[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c020c01u); O[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c0c0c03u);
-                        {
-                            const uint4 da = reinterpret_cast<const uint4 *>(&tabs.dtab[n_lp][0])[0], db = reinterpret_cast<const uint4 *>(&tabs.dtab[n_lp][0])[1];
-                            Q[0] += da.x; Q[1] += da.y; Q[2] += da.z; Q[3] += da.w; O[0] += db.x; O[1] += db.y; O[2] += db.z; O[3] += db.w;
-                        }
-                        const uint32_t KA = (0x8000u - (uint32_t)mind) * 0x10001u, KB = (0x8000u + (uint32_t)maxd) * 0x10001u;
-                        uint32_t accIN = 0, accDD = 0;
-#pragma unroll
-                        for (int g = 1; g < 8; ++g) {
-                            uint32_t orB = 0;
-#pragma unroll
-                            for (int m = 0; m < 4; ++m) {
-                                const int li = (g & 1) ? (g - 1) / 2 + m : g / 2 + m;      // index of the later operand in O (g odd) / Q (g even)
-                                if (li > 3) break;
-                                const uint32_t later = (g & 1) ? O[li] : Q[li], sl = (g & 1) ? SO[li] : SQ[li];
-                                const uint32_t D = later - Q[m];
-                                const uint32_t Bw = KB - D;
-                                const uint32_t IN = __builtin_amdgcn_bitop3_b32(D + KA, Bw, 0x80008000u, 0x80);   // min <= distance <= max (readutil.rs:184, 196)
-                                const uint32_t DD = IN & (sl ^ SQ[m]);
-                                accIN += __builtin_popcount(IN);
-                                accDD += __builtin_popcount(DD);
-                                orB |= Bw;
-                            }
-                            if (!__any((orB & 0x80008000u) != 0u)) break;      // no lane has a pair within max_distance on this diagonal
-                        }
-                        a_c += accIN - accDD;
-                        a_d += accDD;
+                        lpmd_pairs8(v, rraw0, rraw1, n_lp, tabs, mind, maxd, a_c, a_d);
                     } else {
 #pragma unroll
                         for (int k = 0; k < PW_NB; ++k) r[k] = ((uint32_t)k < n_lp) ? r[k] : (int32_t)((k + 1) << 24);

@@ -2,6 +2,7 @@
 // and, from the same body, the fused PDR + LPMD + ME / PM kernel).
 #pragma once
 #include "mth_common.h"
+#include "mth_lpmd_bytes.h"
 
 namespace mth {
 
@@ -64,13 +65,11 @@ typedef uint32_t u32x4_a2 __attribute__((ext_vector_type(4), aligned(2)));
 //   mtab[n][k]   0xffffffff if k < n else 0                       -> masks for the span check / dead-word insertion
 //   dtab[n][c]   relpos offsets of the packed fields (below) that push every dead slot 0x400 * (k + 1) past the live
 //                ones, so that any distance involving a dead slot is >= 0x400 - 255 and all distances stay >= 0
-// ---- windowed pair counts, two pairs per instruction (8-bit relpos) ----
-// Slots are packed two per register as 16-bit fields: Q_e = (slot 2e, slot 2e+1), O_e = (slot 2e+1, slot 2e+2), slot 8
-// being a dummy that is always dead.  The pairs at call-index gap g are then  later - earlier  with earlier = Q_m and
-// later = O_{(g-1)/2+m} (g odd) or Q_{g/2+m} (g even): one 32-bit subtraction gives two distances (no borrows: relpos
-// ascends with the slot, dead offsets ascend faster).  With A = D + (0x8000 - min) and B = (0x8000 + max) - D per
-// field, bit 15 of A & B says "min <= distance <= max"; the call states sit in bit 15 of a second set of packed words,
-// so one xor + and gives "in the window and discordant".  Only full-rate VALU ops (add / sub / and / xor / or / shift).
+//   m8[n][g]     mth_lpmd_bytes.h: 0x80 in byte j of the two words iff the pair (j, j + g) is live
+// ---- windowed pair counts on 8-bit relpos ----
+// Four pairs per instruction on the bytes as loaded (mth_lpmd_bytes.h) while the window allows it (min <= 128, max <= 127: the
+// command line's 2 / 16 and anything near it); two pairs per instruction on 16-bit fields otherwise (lpmd_pairs_fields16 below).
+// lpmd_pairs8 picks one per launch: the window comes from the kernel arguments.
 // hashed-site form for sparse batches (mth_pdr_wide.hip): shift = log2 of the tile width (14 or 15)
 void launch_tile_wide(const TileArgs &a, uint32_t ntiles, int shift, bool rel8, hipStream_t s);
 
@@ -97,8 +96,10 @@ void launch_tile_fused(const TileArgs &a, const FusedQuartet &q, uint32_t ntiles
 struct SlotTabs {
     uint32_t mtab[9][8];
     uint32_t dtab[9][8];
+    LpMask   m8[9][8];
 };
-__device__ __forceinline__ void slot_tabs_init(SlotTabs &T, const int tid) {
+__device__ __forceinline__ void slot_tabs_init(SlotTabs &T, const int tid) {      // needs >= 144 threads
+    if (tid < 144) (&T.m8[0][0].w0)[tid] = lpmd_bytes_mask((uint32_t)tid >> 4, ((uint32_t)tid >> 1) & 7u, (uint32_t)tid & 1u);
     if (tid < 72) {
         const uint32_t nn = (uint32_t)tid >> 3, c = (uint32_t)tid & 7u;
         T.mtab[nn][c] = c < nn ? 0xffffffffu : 0u;
@@ -108,6 +109,66 @@ __device__ __forceinline__ void slot_tabs_init(SlotTabs &T, const int tid) {
     }
 }
 __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }   // v_bfi_b32
+
+// Windowed pair counts, two pairs per instruction: any window up to the 255 an 8-bit relpos can span.
+// Slots are packed two per register as 16-bit fields: Q_e = (slot 2e, slot 2e+1), O_e = (slot 2e+1, slot 2e+2), slot 8
+// being a dummy that is always dead.  The pairs at call-index gap g are then  later - earlier  with earlier = Q_m and
+// later = O_{(g-1)/2+m} (g odd) or Q_{g/2+m} (g even): one 32-bit subtraction gives two distances (no borrows: relpos
+// ascends with the slot, dead offsets ascend faster).  With A = D + (0x8000 - min) and B = (0x8000 + max) - D per
+// field, bit 15 of A & B says "min <= distance <= max"; the call states sit in bit 15 of a second set of packed words,
+// so one xor + and gives "in the window and discordant".  Only full-rate VALU ops (add / sub / and / xor / or / shift).
+__device__ __forceinline__ void lpmd_pairs_fields16(const uint32_t (&v)[8], const uint32_t rraw0, const uint32_t rraw1, const uint32_t *drow,
+                                                    const uint32_t mind, const uint32_t maxd, uint32_t &lp_c, uint32_t &lp_d) {
+    // packed call states (bit 15 of each field; the other bits of the top bytes are ignored by the masks below)
+    uint32_t SQ[4], SO[4], Q[4], O[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) SQ[e] = __builtin_amdgcn_perm(v[2 * e + 1], v[2 * e], 0x070c030cu);
+#pragma unroll
+    for (int e = 0; e < 3; ++e) SO[e] = __builtin_amdgcn_perm(v[2 * e + 2], v[2 * e + 1], 0x070c030cu);
+    SO[3] = __builtin_amdgcn_perm(0u, v[7], 0x070c030cu);
+    Q[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c010c00u); Q[1] = __builtin_amdgcn_perm(0u, rraw0, 0x0c030c02u);
+    Q[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c010c00u); Q[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c030c02u);
+    O[0] = __builtin_amdgcn_perm(0u, rraw0, 0x0c020c01u); O[1] = __builtin_amdgcn_perm(rraw1, rraw0, 0x0c040c03u);
+    O[2] = __builtin_amdgcn_perm(0u, rraw1, 0x0c020c01u); O[3] = __builtin_amdgcn_perm(0u, rraw1, 0x0c0c0c03u);
+    {
+        const uint4 da = reinterpret_cast<const uint4 *>(drow)[0], db = reinterpret_cast<const uint4 *>(drow)[1];
+        Q[0] += da.x; Q[1] += da.y; Q[2] += da.z; Q[3] += da.w; O[0] += db.x; O[1] += db.y; O[2] += db.z; O[3] += db.w;
+    }
+    const uint32_t KA = (0x8000u - mind) * 0x10001u, KB = (0x8000u + maxd) * 0x10001u;
+    uint32_t accIN = 0, accDD = 0;
+#pragma unroll
+    for (int g = 1; g < 8; ++g) {
+        uint32_t orB = 0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int li = (g & 1) ? (g - 1) / 2 + m : g / 2 + m;      // index of the later operand in O (g odd) / Q (g even)
+            if (li > 3) break;
+            const uint32_t later = (g & 1) ? O[li] : Q[li], sl = (g & 1) ? SO[li] : SQ[li];
+            const uint32_t D = later - Q[m];
+            const uint32_t Bw = KB - D;
+            const uint32_t IN = __builtin_amdgcn_bitop3_b32(D + KA, Bw, 0x80008000u, 0x80);   // min <= distance <= max (readutil.rs:184, 196)
+            const uint32_t DD = IN & (sl ^ SQ[m]);
+            accIN += __builtin_popcount(IN);        // v_bcnt_u32_b32 adds its second operand: one instruction per count
+            accDD += __builtin_popcount(DD);
+            orB |= Bw;
+        }
+        if (!__any((orB & 0x80008000u) != 0u)) break;      // no lane has a pair within max_distance on this diagonal
+    }
+    lp_c += accIN - accDD;
+    lp_d += accDD;
+}
+
+// The pairs among a read's first 8 calls (readutil.rs:166-224): v = its call words (dead slots: any word), rraw0 / rraw1 = its 8
+// relpos bytes as loaded (dead slots: any byte), n_lp = live slots (0: count nothing), [mind, maxd] = the window, 0 <= mind,
+// mind <= maxd <= 255 (the callers have excluded an empty window).  The lanes of a wave that have a read call it together: the early exit is a vote among them.
+__device__ __forceinline__ void lpmd_pairs8(const uint32_t (&v)[8], const uint32_t rraw0, const uint32_t rraw1, const uint32_t n_lp,
+                                            const SlotTabs &T, const int32_t mind, const int32_t maxd, uint32_t &lp_c, uint32_t &lp_d) {
+    if (lpmd_bytes_domain(mind, maxd))
+        lpmd_pairs_bytes(rraw0, rraw1, lpmd_state_bytes(v[0], v[1], v[2], v[3]), lpmd_state_bytes(v[4], v[5], v[6], v[7]), &T.m8[n_lp][0],
+                         (uint32_t)mind, (uint32_t)maxd, lp_c, lp_d);
+    else
+        lpmd_pairs_fields16(v, rraw0, rraw1, &T.dtab[n_lp][0], (uint32_t)mind, (uint32_t)maxd, lp_c, lp_d);
+}
 
 
 }  // namespace mth
