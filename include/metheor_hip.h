@@ -446,6 +446,16 @@ typedef struct {
 int  mth_tag_set_genome(mth_ctx_t *ctx, int32_t n_refs, const int64_t *ref_len, const uint8_t *const *seq, const int64_t *seq_len);
 int  mth_tag_records(mth_ctx_t *ctx, const void *raw, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
                      int is_paired_end, mth_tag_out_t *out);
+/* derive the calls from the genome of mth_tag_set_genome instead of the records' XM:Z (what `metheor tag` followed by
+ * the measure computes): applies to the following mth_decode_records / mth_bgzf_decode calls.  is_paired_end =
+ * bamutil.rs:27-37.  enabled != 0 before mth_tag_set_genome: MTH_ERR_STATE.
+ * The result is the composition of tag.rs:130-384 and readutil.rs:323-345, quirks included (tag.rs walks M, I and D only, the
+ * decode reads letter q for the aligned base at query offset q).  An XM:Z field the records carry is not
+ * looked at and a record is never "without XM" in this mode (mth_decode_set_xm_min_mapq has no effect); a record on which
+ * determine_xm_tag_string panics is MTH_ERR_FORMAT ("tag: ..."), whatever its mapq.  The kernel is k_decode_genome
+ * (mth_decode_genome.hip); METHEOR_GENOME_STAGED=1 in the environment selects the second form, k_tag_xm into HBM and k_decode
+ * reading the strings from there. */
+int  mth_decode_set_genome(mth_ctx_t *ctx, int enabled, int is_paired_end);
 
 /* ---- measurement hooks (bench.py's roofline leg) -------------------------------------- */
 /* when enabled, every kernel launch is bracketed by hipEvents on the launch stream */

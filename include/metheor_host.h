@@ -47,6 +47,9 @@ int  mth_host_n_refs(const mth_host_t *h);
 const char *mth_host_ref_name(const mth_host_t *h, int tid);
 int64_t mth_host_ref_len(const mth_host_t *h, int tid);
 int  mth_host_ref_tid(const mth_host_t *h, const char *name);   /* -1 if unknown */
+/* the FLAG of the file's first record (bamutil.rs:27-37 is_paired_end looks at its bit 0x1), -1 for a file without records:
+ * read through a reader of its own, whatever part of the file the loaders take afterwards (--region, --gpus N) */
+int  mth_host_first_flag(mth_host_t *h, int *flag);
 
 /* the path the loaders read: the input itself for a BAM, the in-memory BAM a SAM text input was converted into otherwise */
 const char *mth_host_path(const mth_host_t *h);

@@ -16,7 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_decode_set_genome",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -156,6 +156,7 @@ def lib():
         L.mth_decode_reserve.argtypes = [vp, C.c_uint64, C.c_uint64]
         L.mth_tag_set_genome.argtypes = [vp, C.c_int32, vp, vp, vp]
         L.mth_tag_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_tag_out_t)]
+        L.mth_decode_set_genome.argtypes = [vp, C.c_int, C.c_int]
         L.mth_decoded_fetch.argtypes = [vp] * 9
         L.mth_decoded_contigs.argtypes = [vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.mth_decoded_sort.argtypes = [vp]
@@ -523,6 +524,11 @@ class Engine:
         xo = np.ctypeslib.as_array(C.cast(t.xm_off, C.POINTER(C.c_uint64)), shape=(n + 1,))
         xl = np.ctypeslib.as_array(C.cast(t.xm_len, C.POINTER(C.c_uint32)), shape=(n,))
         return [C.string_at(t.xm + int(xo[i]), int(xl[i])) for i in range(n)]
+
+    def decode_set_genome(self, enabled, is_paired_end=False):
+        """derive the calls of the following decode_records / bgzf_decode calls from the genome of tag_set_genome instead of
+        the records' XM:Z -- what `metheor tag` followed by the decode computes (mth_decode_set_genome)"""
+        self._check(self.L.mth_decode_set_genome(self.h, int(bool(enabled)), int(bool(is_paired_end))))
 
     def decoded_fetch(self):
         d = self._decoded

@@ -49,6 +49,8 @@ const Opt O_CPG = {"cpg-set", 'c', "CPG_SET", "(Optional) Specify a predefined s
 const Opt O_GPUS = {"gpus", 'G', "GPUS", "(MI355X extension) Number of GPUs to split the run over, by genomic region", "1", false, 'U'};
 // not in the reference either: the .bai files its fixtures ship finally get a reader
 const Opt O_REGION = {"region", 'r', "REGION", "(MI355X extension) Only this region: chr or chr:beg-end (1-based, inclusive); needs the BAM index", nullptr, false, 's'};
+// not in the reference: the two commands `tag`, then the measure, as one
+const Opt O_GENOME = {"genome", 'g', "GENOME", "(MI355X extension) Reference FASTA: derive the methylation calls from it instead of XM:Z tags, as `metheor tag` would; XM:Z tags in the input are ignored", nullptr, false, 's'};
 const Opt O_BAI = {"bai", 'b', "BAI", "(MI355X extension) BAM index for --region [default: <input>.bai]", nullptr, false, 's'};
 
 // lib.rs:24-231
@@ -58,41 +60,41 @@ const std::vector<Cmd> &commands() {
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of PDR calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG stretches to consider", "10", false, 'U'},
           {"min-cpgs", 'p', "MIN_CPGS", "Minimum number of consecutive CpGs in a CpG stretch to consider", "4", false, 'Z'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
         {"pm", "Compute epipolymorphism",
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of PM calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG quartets to consider", "10", false, 'U'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
         {"me", "Compute methylation entropy",
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of PDR calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG quartets to consider", "10", false, 'U'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
         {"fdrp", "Compute fraction of discordant read pairs (FDRP)",
          {{"input", 'i', "INPUT", "Path to input BAM file", nullptr, true, 's'},
           {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of FDRP calculation", nullptr, true, 's'},
           {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum number of reads mapped to a CpG in order to be considered", "10", false, 'Z'},
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
-          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
         {"qfdrp", "Compute quantitative fraction of discordant read pairs (qFDRP)",
          {{"input", 'i', "INPUT", "Path to input BAM file", nullptr, true, 's'},
           {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of FDRP calculation", nullptr, true, 's'},
           {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum number of reads mapped to a CpG in order to be considered", "10", false, 'Z'},
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
-          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
         {"mhl", "Compute methylation haplotype load (MHL)",
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of MHL calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG stretches to consider", "10", false, 'U'},
           {"min-cpgs", 'p', "MIN_CPGS", "Minimum number of consecutive CpGs in a CpG stretch to consider", "4", false, 'Z'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
         {"lpmd", "Compute local pairwise methylation discordance (LPMD)",
          {{"input", 'i', "INPUT", "Path to input BAM file", nullptr, true, 's'},
           {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of LPMD calculation", nullptr, true, 's'},
           {"pairs", 'p', "PAIRS", "(Optional) Concordance information for all CpG pairs", nullptr, false, 's'},
           {"min-distance", 'm', "MIN_DISTANCE", "Minimum distance between CpG pairs to consider", "2", false, 'I'},
           {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
         // not in the reference: any subset of the seven measures from ONE decode of the input (the parameters are shared by every
         // measure that has them, under the single commands' names and defaults; --lpmd-pairs is lpmd's --pairs, whose -p is min-cpgs here)
         {"all", "(MI355X extension) Compute any of the seven measures from one decode of the input",
@@ -112,7 +114,7 @@ const std::vector<Cmd> &commands() {
           {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
           {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'},
-          O_CPG, O_REGION, O_BAI}},
+          O_CPG, O_REGION, O_BAI, O_GENOME}},
         {"tag", "Add bismark XM tag to BAM file",
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
           {"genome", 'g', "GENOME", "", nullptr, true, 's'}}},
@@ -374,6 +376,64 @@ mth_ctx_t *make_ctx() {
     return ctx;
 }
 
+// ---- the reference genome (`tag`, and --genome on the measures) -------------------------------------------------------------------
+// tag.rs:412-431: open the FASTA, fetch every @SQ contig of the input's header up to its LN.  One host copy per process (--gpus N:
+// read once by main(), uploaded by every shard's context).
+struct Genome {
+    std::string path;                      // empty: no --genome
+    bool loaded = false;
+    std::vector<std::vector<uint8_t>> seqs;
+    std::vector<const uint8_t *> ptr;
+    std::vector<int64_t> ln, got;
+};
+Genome g_genome;
+
+// the messages and the status are `tag`'s (tag.rs:414-417, 427); on_fail runs before the process ends (tag flushes its output)
+template <class F>
+mth_fasta_t *genome_open(const std::string &path, F on_fail) {
+    mth_fasta_t *fa = nullptr;
+    char err[1024];
+    if (mth_host_fasta_open(path.c_str(), &fa, err, sizeof err) != 0) { on_fail(); die(std::string("Error opening reference genome file: ") + err); }
+    return fa;
+}
+template <class F>
+void genome_fetch(mth_fasta_t *fa, mth_host_t *h, Genome &g, F on_fail) {
+    const int n_refs = mth_host_n_refs(h);
+    g.seqs.assign((size_t)n_refs, {}); g.ptr.assign((size_t)n_refs, nullptr); g.ln.assign((size_t)n_refs, 0); g.got.assign((size_t)n_refs, 0);
+    for (int t = 0; t < n_refs; ++t) {
+        const uint8_t *p = nullptr;
+        int64_t n = 0;
+        g.ln[(size_t)t] = mth_host_ref_len(h, t);
+        if (mth_host_fasta_fetch(fa, mth_host_ref_name(h, t), g.ln[(size_t)t], &p, &n) != 0) { on_fail(); die("Error fetching reference genome sequence.: " + std::string(mth_host_fasta_last_error(fa))); }
+        g.seqs[(size_t)t].assign(p, p + n);
+        g.ptr[(size_t)t] = g.seqs[(size_t)t].data(); g.got[(size_t)t] = n;
+    }
+    g.loaded = true;
+}
+void genome_upload(mth_ctx_t *ctx, const Genome &g) {
+    check(ctx, mth_tag_set_genome(ctx, (int32_t)g.ln.size(), g.ln.data(), g.ptr.data(), g.got.data()));
+}
+// --genome of a measure: read once, before any output file exists
+template <class F>
+void genome_read_once(mth_host_t *h, F on_fail) {
+    if (g_genome.path.empty() || g_genome.loaded) return;
+    Phase ph("  genome FASTA read");
+    mth_fasta_t *fa = genome_open(g_genome.path, on_fail);
+    genome_fetch(fa, h, g_genome, on_fail);
+    mth_host_fasta_close(fa);
+}
+const char *const kNoHostGenome =
+    "--genome needs the device record decode: the full host decoder (METHEOR_HOST_DECODE=1, or input it has to take: records without a "
+    "contig or an aligned base, contigs not grouped) has no genome form -- run `metheor tag` first and give the measure its output";
+
+// a failed decode call as the reference's panic
+[[noreturn]] void die_decode_format(mth_ctx_t *ctx, const char *what) {
+    const std::string m = mth_last_error(ctx);
+    if (m.rfind("tag:", 0) == 0) die(std::string("metheor (MI355X path): ") + mth_strerror(MTH_ERR_FORMAT) + " -- " + m);      // --genome: determine_xm_tag_string panics
+    if (m.find("XM") != std::string::npos) die("Error reading XM tag in BAM record. Make sure the reads are aligned using Bismark!");   // readutil.rs:46
+    die(std::string("Error reading BAM record. ") + what);
+}
+
 // Device-side record decode (mth_decode_records): the host inflates BGZF and walks the record boundaries, every
 // window goes to the GPU as raw bytes, and the SoA the measures read is built in HBM -- no record / XM parsing and
 // no SoA assembly on host threads (--cpg-set is applied by the decode kernel).  Not used with
@@ -445,11 +505,7 @@ bool load_bgzf_on_device(Input &in) {
         const int rc = mth_bgzf_decode(in.ctx, bz.file + c.base, c.nbytes, rel.data(), bz.csize + c.b0, bz.isize + c.b0, c.b1 - c.b0, first_byte, first ? 0 : 1, &d);
         hdr_left -= first_byte;
         if (rc == MTH_ERR_UNALIGNED) { check(in.ctx, mth_reset(in.ctx)); return false; }
-        if (rc == MTH_ERR_FORMAT) {
-            const std::string m = mth_last_error(in.ctx);
-            if (m.find("XM") != std::string::npos) die("Error reading XM tag in BAM record. Make sure the reads are aligned using Bismark!");   // readutil.rs:46
-            die("Error reading BAM record. corrupt BGZF block or BAM record");
-        }
+        if (rc == MTH_ERR_FORMAT) die_decode_format(in.ctx, "corrupt BGZF block or BAM record");
         check(in.ctx, rc);
         done_u += c.ubytes;
         if (first && ci + 1 < chunks.size() && done_u) {
@@ -473,9 +529,21 @@ bool load_on_device(Input &in, const char *cpg_set, CtxFuture &cf) {
         mth_host_bgzf_t bz;                      // builds (and caches) the block table while the context is being created
         if (!getenv("METHEOR_HOST_INFLATE") && mth_host_bgzf_blocks(in.h, &bz) != 0) { cf.wait(); die(mth_host_last_error(in.h)); }
     }
+    // --genome: the FASTA is read here, while the context is being created; the first record's paired flag is the FILE's
+    // (bamutil.rs:27-37), whatever part of it this shard / region loads
+    int first_flag = -1;
+    if (!g_genome.path.empty()) {
+        genome_read_once(in.h, [&] { cf.wait(); });
+        if (mth_host_first_flag(in.h, &first_flag) != 0) { cf.wait(); die(mth_host_last_error(in.h)); }
+    }
     // (touching the mapped file's pages from 16 threads while the HIP runtime starts was measured: it slows the start-up
     // it competes with and the copies gain nothing, profiles/r02_e2e.md)
     in.ctx = cf.get();
+    if (!g_genome.path.empty()) {
+        Phase ph("  genome -> device");
+        genome_upload(in.ctx, g_genome);
+        check(in.ctx, mth_decode_set_genome(in.ctx, 1, first_flag >= 0 && (first_flag & 1)));
+    }
     if (cpg_set) check(in.ctx, mth_decode_set_cpg_filter(in.ctx, keys, n_keys, 1));
     check(in.ctx, mth_decode_set_xm_min_mapq(in.ctx, (uint32_t)g_shard.xm_min_mapq));
     const bool on_device = !getenv("METHEOR_HOST_INFLATE") && load_bgzf_on_device(in);
@@ -485,11 +553,7 @@ bool load_on_device(Input &in, const char *cpg_set, CtxFuture &cf) {
         st.ctx = in.ctx;
         Phase ph("  inflate + device record decode");
         const int rc = mth_host_decode_stream(in.h, window_to_device, &st);
-        if (st.rc == MTH_ERR_FORMAT) {
-            const std::string m = mth_last_error(in.ctx);
-            if (m.find("XM") != std::string::npos) die("Error reading XM tag in BAM record. Make sure the reads are aligned using Bismark!");   // readutil.rs:46
-            die("Error reading BAM record. corrupt BAM record");
-        }
+        if (st.rc == MTH_ERR_FORMAT) die_decode_format(in.ctx, "corrupt BAM record");
         if (st.rc != MTH_OK) check(in.ctx, st.rc);
         if (rc != 0) die(mth_host_last_error(in.h));
         if (st.first) {   // no record at all: an empty decode
@@ -603,12 +667,14 @@ Input load(const std::string &path, const char *cpg_set, bool host_only = false)
     char err[1024];
     const bool try_device = !getenv("METHEOR_HOST_DECODE") && !host_only;
     if (!try_device && g_shard.planned()) die("--gpus N / --region need the device load path (METHEOR_HOST_DECODE is set)");
+    if (!try_device && !g_genome.path.empty()) die(kNoHostGenome);
     CtxFuture cf;
     if (try_device) cf.start();
     if (mth_host_open(path.c_str(), &in.h, err, sizeof err) != 0) { cf.wait(); die(err); }    // bamutil.rs:7-9
     if (try_device) {
         if (load_on_device(in, cpg_set, cf)) return in;
         if (g_shard.planned()) die("--gpus N / --region need the device load path (coordinate-sorted input, contigs grouped, records inside BGZF blocks)");
+        if (!g_genome.path.empty()) die(kNoHostGenome);
         in.contigs.clear();
     }
     {
@@ -1243,25 +1309,14 @@ int run_tag(const Args &a) {
         while (!text.empty() && text.back() == '\n') text.pop_back();
         if (!text.empty()) { text += '\n'; fwrite(text.data(), 1, text.size(), out); }
     }
-    mth_fasta_t *fa = nullptr;
-    if (mth_host_fasta_open(genome.c_str(), &fa, err, sizeof err) != 0) { cf.wait(); fflush(out); die(std::string("Error opening reference genome file: ") + err); }
+    mth_fasta_t *fa = genome_open(genome, [&] { cf.wait(); fflush(out); });
     printf("Parsing reference genome...\n");
     mth_ctx_t *ctx = cf.get();
     {
         Phase ph("genome -> device");
-        const int n_refs = mth_host_n_refs(h);
-        std::vector<std::vector<uint8_t>> seqs((size_t)n_refs);
-        std::vector<const uint8_t *> ptr((size_t)n_refs);
-        std::vector<int64_t> ln((size_t)n_refs), got((size_t)n_refs);
-        for (int t = 0; t < n_refs; ++t) {
-            const uint8_t *p = nullptr;
-            int64_t n = 0;
-            ln[(size_t)t] = mth_host_ref_len(h, t);
-            if (mth_host_fasta_fetch(fa, mth_host_ref_name(h, t), ln[(size_t)t], &p, &n) != 0) { fflush(out); die("Error fetching reference genome sequence.: " + std::string(mth_host_fasta_last_error(fa))); }
-            seqs[(size_t)t].assign(p, p + n);
-            ptr[(size_t)t] = seqs[(size_t)t].data(); got[(size_t)t] = n;
-        }
-        check(ctx, mth_tag_set_genome(ctx, n_refs, ln.data(), ptr.data(), got.data()));
+        Genome g;
+        genome_fetch(fa, h, g, [&] { fflush(out); });
+        genome_upload(ctx, g);
     }
     printf("Done!\n");
     fflush(stdout);
@@ -1316,6 +1371,7 @@ int main(int argc, char **argv) {
             usage_error(cmd, "the following required arguments were not provided:\n  <--pdr <PDR>|--lpmd <LPMD>|--mhl <MHL>|--me <ME>|--pm <PM>|--fdrp <FDRP>|--qfdrp <QFDRP>>");
         if (a.has("lpmd-pairs") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
     }
+    if (a.has("genome")) g_genome.path = a.s.at("genome");
     // (`all` has no --gpus: one device)
     const int64_t gpus = a.n.count("gpus") ? a.n.at("gpus") : 1;
     int64_t halo = 65536;
@@ -1352,6 +1408,7 @@ int main(int argc, char **argv) {
         mth_host_t *h = nullptr;
         char err[1024];
         if (mth_host_open(a.s.at("input").c_str(), &h, err, sizeof err) != 0) die(err);
+        genome_read_once(h, [] {});          // one host copy of the genome for all the shards
         mth_host_close(h);
     }
     std::vector<Part> parts((size_t)world);

@@ -140,6 +140,21 @@ int mth_host_ref_tid(const mth_host_t *h, const char *name) {
     return it == h->name2tid.end() ? -1 : it->second;
 }
 
+int mth_host_first_flag(mth_host_t *h, int *flag) {
+    if (!h || !flag) return MTH_HOST_ERR_INVALID;
+    *flag = -1;
+    BamReader rd;
+    BamRecord rec;
+    bool eof = false;
+    if (!rd.open(h->path) || !rd.next(rec, eof)) {
+        if (eof) return MTH_HOST_OK;
+        h->last_error = "Error reading BAM record. " + rd.error();
+        return MTH_HOST_ERR_FORMAT;
+    }
+    if (!eof) *flag = rec.flag;
+    return MTH_HOST_OK;
+}
+
 const char *mth_host_path(const mth_host_t *h) { return h ? h->path.c_str() : ""; }
 
 const char *mth_host_header_text(const mth_host_t *h, uint64_t *n_bytes) {

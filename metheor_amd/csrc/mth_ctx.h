@@ -119,6 +119,9 @@ struct mth_ctx {
     // and the host copies mth_tag_records hands out
     mth::DevBuf tag_genome, tag_goff, tag_ncol, tag_coloff, tag_xmlen, tag_cols, tag_xm;
     int32_t tag_n_refs = -1;
+    // mth_decode_set_genome: the decode derives its calls from tag_genome (mth_decode_genome.hip) instead of XM:Z
+    bool dec_genome = false, dec_genome_paired = false;
+    unsigned long long tag_cols_total = 0;   // column scratch of the decode call in progress (count pass -> fill pass)
     std::vector<uint64_t> tag_h_off;
     std::vector<uint32_t> tag_h_len;
     std::vector<uint8_t> tag_h_xm;
@@ -252,6 +255,13 @@ int stage_batch(mth_ctx *ctx, const mth_batch_t &b, mth_batch_t &dev, bool join 
 int scan_u32_to_u64(mth_ctx *ctx, const uint32_t *n, uint32_t count, unsigned long long base, unsigned long long *off,
                     unsigned long long *total_host);
 int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint64_t n_rec, int append, mth_decoded_t *out);
+// mth_tag.hip: the XM strings of n device-resident records into ctx->tag_xm (offsets tag_coloff, lengths tag_xmlen); *total = bytes
+int tag_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint32_t n, int is_paired_end, unsigned long long *total);
+struct DecArgs;
+// mth_decode_genome.hip: the two passes of the decode with the calls derived from the genome (k_decode_genome); `a` as decode_core
+// fills it for k_decode<false>.  count: ncpg / tid / start / end / mapq / fwd; fill: cpg_pos / cpg_rel at a.cpg_off
+int decode_genome_count(mth_ctx *ctx, const DecArgs &a);
+int decode_genome_fill(mth_ctx *ctx, const DecArgs &a);
 // implemented in mth_sites.hip: PDR with exact flush / re-open semantics (spans > 150 bp)
 int launch_pdr_exact(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_pdr_lpmd_params_t &p);
 // site discovery (tile pipeline into the private sink): positions called by >= 1 read with

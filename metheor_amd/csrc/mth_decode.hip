@@ -16,30 +16,9 @@
 #include <algorithm>
 
 #include "mth_ctx.h"
+#include "mth_decode_dev.h"
 
 namespace mth {
-
-struct DecArgs {
-    const uint8_t *raw;
-    const uint64_t *off;          // n_rec + 1 byte offsets of the records (each starts with its block_size)
-    uint32_t n_rec;
-    int32_t *tid, *start, *end;
-    uint8_t *mapq, *fwd;
-    uint32_t *ncpg;               // pass 1 out
-    uint2 *xm_loc;                // pass 1 out / pass 2 in: {offset of the XM string from the record core, its length}
-    const unsigned long long *cpg_off;   // pass 2 in (exclusive scan of ncpg, n_rec + 1; global call indices)
-    uint32_t *cpg_pos;
-    uint16_t *cpg_rel;
-    uint32_t *err;                // DevState.err
-    uint32_t *notes;              // DevState.pad_: non-fatal findings (bit 0: a CIGAR P operation), read back with the error bits
-    const unsigned long long *filt;   // --cpg-set: sorted keys tid << 32 | pos, or nullptr (no filter)
-    uint64_t n_filt;
-    uint32_t xm_min_mapq;         // a record WITHOUT XM:Z is an error only if its mapq >= this (lpmd.rs:176-181 filters on mapq first)
-};
-
-typedef uint32_t u32x4_a1 __attribute__((ext_vector_type(4), aligned(1)));
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
 
 // aux fields until XM:Z (SAM spec 4.2.4); false = malformed or absent
 __device__ __forceinline__ bool dev_find_xm(const uint8_t *aux, uint32_t len, const uint8_t *&xm, uint32_t &xm_len) {
@@ -96,16 +75,6 @@ __device__ __forceinline__ bool dev_find_xm(const uint8_t *aux, uint32_t len, co
     return false;
 }
 
-// filter_isin (readutil.rs:87-95): is (tid, pos) in the sorted key array ?
-__device__ __forceinline__ bool in_cpg_set(const unsigned long long *__restrict__ keys, uint64_t n, unsigned long long key) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo < n && keys[lo] == key;
-}
-
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_decode(const DecArgs a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -130,6 +99,8 @@ __global__ __launch_bounds__(256) void k_decode(const DecArgs a) {
         bool have_xm = false;
         if (o_aux > len) {
             bad = true;
+        } else if (a.xm_base) {                                  // the string k_tag_xm derived from the genome (both passes)
+            xm = a.xm_base + a.xm_off[i]; xm_len = a.xm_lens[i]; have_xm = true;
         } else if (FILL) {                                       // found by the count pass
             const uint2 loc = a.xm_loc[i];
             xm = p + loc.x; xm_len = loc.y; have_xm = loc.x != 0u;
@@ -432,9 +403,22 @@ int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint6
     a.xm_min_mapq = ctx->dec_xm_min_mapq;
     a.filt = ctx->dec_filter_on ? ctx->dec_filter.as<unsigned long long>() : nullptr; a.n_filt = ctx->dec_filter_n;
     if (ctx->dec_filter_on && ctx->dec_filter_n == 0) a.filt = reinterpret_cast<const unsigned long long *>(ctx->d_state);   // empty set: drops every call
+    // mth_decode_set_genome: the calls come from the genome.  Default: k_decode_genome derives them in the decode's own two
+    // passes; METHEOR_GENOME_STAGED=1: k_tag_xm writes every record's XM string to HBM and k_decode reads it from there
+    const bool genome = ctx->dec_genome, staged = genome && getenv("METHEOR_GENOME_STAGED") && atoi(getenv("METHEOR_GENOME_STAGED")) != 0;
+    if (genome && ctx->tag_n_refs < 0) return fail(ctx, MTH_ERR_STATE, "mth_decode_set_genome is on but mth_tag_set_genome has not been called");
     unsigned long long total = 0;
     if (n_rec) {
-        {
+        if (staged) {
+            unsigned long long xm_bytes = 0;
+            const int rc = tag_core(ctx, d_raw, d_off, a.n_rec, ctx->dec_genome_paired ? 1 : 0, &xm_bytes);
+            if (rc) return rc;
+            a.xm_base = ctx->tag_xm.as<uint8_t>(); a.xm_off = ctx->tag_coloff.as<unsigned long long>(); a.xm_lens = ctx->tag_xmlen.as<uint32_t>();
+        }
+        if (genome && !staged) {
+            const int rc = decode_genome_count(ctx, a);
+            if (rc) return rc;
+        } else {
             LaunchTimer lt(ctx, K_DECODE);
             hipLaunchKernelGGL((k_decode<false>), dim3((uint32_t)((nr + 255) / 256)), dim3(256), 0, s, a);
         }
@@ -449,8 +433,13 @@ int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint6
     if (n_rec && total) {
         a.cpg_off = ctx->dec_off.as<unsigned long long>() + R0;
         a.cpg_pos = ctx->dec_pos.as<uint32_t>(); a.cpg_rel = ctx->dec_rel.as<uint16_t>();
-        LaunchTimer lt(ctx, K_DECODE);
-        hipLaunchKernelGGL((k_decode<true>), dim3((uint32_t)((nr + 255) / 256)), dim3(256), 0, s, a);
+        if (genome && !staged) {
+            const int rc = decode_genome_fill(ctx, a);
+            if (rc) return rc;
+        } else {
+            LaunchTimer lt(ctx, K_DECODE);
+            hipLaunchKernelGGL((k_decode<true>), dim3((uint32_t)((nr + 255) / 256)), dim3(256), 0, s, a);
+        }
     }
     MTH_HIP(ctx, hipGetLastError());
     ctx->dec_reads = R1; ctx->dec_cpgs = C1;
@@ -516,6 +505,14 @@ int mth_decode_reserve(mth_ctx_t *ctx, uint64_t n_reads, uint64_t n_cpgs) {
     MTH_HIP(ctx, ctx->dec_off.reserve((R + 1) * 8, s, R0 > 0, R0 ? (R0 + 1) * 8 : 0));
     MTH_HIP(ctx, ctx->dec_pos.reserve(C * 4 + 4, s, C0 > 0, C0 * 4));
     MTH_HIP(ctx, ctx->dec_rel.reserve(C * 2 + 4, s, C0 > 0, C0 * 2));
+    return MTH_OK;
+}
+
+int mth_decode_set_genome(mth_ctx_t *ctx, int enabled, int is_paired_end) {
+    if (!ctx) return MTH_ERR_INVALID;
+    if (enabled && ctx->tag_n_refs < 0) return fail(ctx, MTH_ERR_STATE, "mth_decode_set_genome before mth_tag_set_genome: there is no genome to derive the calls from");
+    ctx->dec_genome = enabled != 0;
+    ctx->dec_genome_paired = enabled && is_paired_end;
     return MTH_OK;
 }
 

@@ -9,7 +9,7 @@ _LIB = None
 
 SYMBOLS = [
     "mth_host_open", "mth_host_close", "mth_host_last_error", "mth_host_notes", "mth_host_n_refs", "mth_host_ref_name",
-    "mth_host_ref_len", "mth_host_ref_tid", "mth_host_set_xm_min_mapq", "mth_host_decode", "mth_host_decode_stream", "mth_host_bgzf_blocks", "mth_host_plan_shard", "mth_host_plan_region", "mth_host_cpg_set_keys", "mth_host_n_reads", "mth_host_n_cpgs",
+    "mth_host_ref_len", "mth_host_ref_tid", "mth_host_first_flag", "mth_host_set_xm_min_mapq", "mth_host_decode", "mth_host_decode_stream", "mth_host_bgzf_blocks", "mth_host_plan_shard", "mth_host_plan_region", "mth_host_cpg_set_keys", "mth_host_n_reads", "mth_host_n_cpgs",
     "mth_host_read_tid", "mth_host_read_start", "mth_host_read_end", "mth_host_read_mapq",
     "mth_host_read_fwd", "mth_host_cpg_off", "mth_host_cpg_pos", "mth_host_cpg_rel", "mth_host_format_f32", "mth_host_write_synthetic_bam",
     "mth_host_write_synthetic_bam_multi", "mth_host_write_synthetic_bam_repeat", "mth_host_header_text", "mth_host_path", "mth_host_sam_format", "mth_host_fasta_open", "mth_host_fasta_close",
@@ -56,6 +56,7 @@ def lib():
         L.mth_host_ref_name.argtypes = [vp, C.c_int]; L.mth_host_ref_name.restype = C.c_char_p
         L.mth_host_ref_len.argtypes = [vp, C.c_int]; L.mth_host_ref_len.restype = C.c_int64
         L.mth_host_ref_tid.argtypes = [vp, C.c_char_p]
+        L.mth_host_first_flag.argtypes = [vp, C.POINTER(C.c_int)]
         L.mth_host_decode.argtypes = [vp, C.c_char_p]
         for f in ("n_reads", "n_cpgs"):
             getattr(L, "mth_host_" + f).argtypes = [vp]; getattr(L, "mth_host_" + f).restype = C.c_int64
@@ -203,6 +204,14 @@ class BamFile:
                     end=arr("read_end", np.int32, n), mapq=arr("read_mapq", np.uint8, n),
                     fwd=arr("read_fwd", np.uint8, n), cpg_off=arr("cpg_off", np.uint64, n + 1),
                     cpg_pos=arr("cpg_pos", np.uint32, nc), cpg_rel=arr("cpg_rel", np.uint16, nc))
+
+    def first_flag(self):
+        """FLAG of the file's first record (bamutil.rs:27-37 looks at its 0x1), -1 for a file without records"""
+        f = C.c_int(-1)
+        rc = self.L.mth_host_first_flag(self.h, C.byref(f))
+        if rc != 0:
+            raise HostError(rc, self.L.mth_host_last_error(self.h).decode())
+        return f.value
 
     def staged_path(self):
         """SAM input: the path of the in-memory BAM the text was converted into (valid while this object lives)"""

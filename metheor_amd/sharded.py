@@ -6,7 +6,8 @@ is exactly `metheor pdr -i in.bam -o out.tsv [flags] --gpus 8`: the executable i
 context per shard (shard r on device r mod the devices in use), every shard plans and loads its own run of BGZF blocks
 (mth_host_plan_shard: no index, no router), owns a (tid, pos) interval, and the parts are concatenated in memory in shard
 order; `lpmd` sums its four global counters with one RCCL all-reduce (mth_allreduce_lpmd).  No temporary files, nothing
-parsed here (cli_main.cpp).
+parsed here (cli_main.cpp): every flag after `--` reaches the executable as it is, `-g / --genome`
+included (the FASTA is then read once and uploaded to every shard's device).
 """
 import argparse
 import os
