@@ -90,7 +90,7 @@ int pipe_join(mth_ctx *ctx) {
 int enter(mth_ctx *ctx) {
     MTH_HIP(ctx, hipSetDevice(ctx->device));
     int rc = pipe_join(ctx);
-    // ME / PM / pairs batches queued without a host sync (mth_quartet.hip, mth_pairs.hip): every entry point but the call that queues
+    // ME / PM / pairs batches queued without a host sync (mth_tile_rows.hip): every entry point but the call that queues
     // the next one settles them first -- the caller may be about to rewrite what a replay would read (mth_decoded_batch rebuilds the
     // offsets array the previous decoded batch points into), and "the next synchronising call" of the header's contract is any of them
     if (!rc && !ctx->tile_queue_hold) {
@@ -98,8 +98,8 @@ int enter(mth_ctx *ctx) {
         // a growth sync behind stage_batch must not make it drop its prepared index and rebuild one: ADVICE r05)
         Prepared *const prep = ctx->cur_prep;
         const uint32_t *const idx = ctx->cur_idx;
-        if (!ctx->q_pending.empty()) rc = quartet_resolve(ctx);
-        if (!rc && !ctx->p_pending.empty()) rc = pairs_resolve(ctx);
+        for (TileRowTable *t : {&ctx->quartets, &ctx->pairs})
+            if (!rc) rc = tile_rows_resolve(ctx, *t);
         ctx->cur_prep = prep; ctx->cur_idx = prep ? idx : nullptr;
     }
     return rc;
@@ -112,8 +112,8 @@ bool has_group_batch(const mth_ctx *ctx, int which) {
         case 0: return any(ctx->batches);
         case 1: return any(ctx->m_batches);
         case 2: return any(ctx->f_batches);
-        case 3: return any(ctx->q_meta);
-        default: return any(ctx->p_meta);
+        case 3: return any(ctx->quartets.meta);
+        default: return any(ctx->pairs.meta);
     }
 }
 
@@ -328,13 +328,15 @@ void mth_ctx_destroy(mth_ctx_t *ctx) {
                       &ctx->dec_mapq, &ctx->dec_fwd, &ctx->dec_n, &ctx->dec_off, &ctx->dec_pos, &ctx->dec_rel, &ctx->dec_blk, &ctx->dec_off32, &ctx->dec_runs, &ctx->dec_xm, &ctx->dec_filter,
                       &ctx->inf_file, &ctx->inf_file2, &ctx->inf_tab, &ctx->inf_raw, &ctx->inf_cnt, &ctx->inf_base, &ctx->inf_recoff, &ctx->crc_mat,
                       &ctx->tag_genome, &ctx->tag_goff, &ctx->tag_ncol, &ctx->tag_coloff, &ctx->tag_xmlen, &ctx->tag_cols, &ctx->tag_xm,
-                      &ctx->batch_cnt, &ctx->out_pos, &ctx->out_pdr, &ctx->out_nc, &ctx->out_nd, &ctx->q_state, &ctx->q_keys,
-                      &ctx->q_hist, &ctx->q_blk, &ctx->q_batch_rows, &ctx->q_tflag, &ctx->q_tile_row0, &ctx->q_tile_rows, &ctx->q_wpos, &ctx->q_wpat, &ctx->q_wk0, &ctx->q_wk1, &ctx->q_snap, &ctx->p_snap, &ctx->q_pos, &ctx->q_cnt, &ctx->q_me, &ctx->q_pm, &ctx->q_depth,
+                      &ctx->batch_cnt, &ctx->out_pos, &ctx->out_pdr, &ctx->out_nc, &ctx->out_nd, &ctx->q_keys,
+                      &ctx->q_hist, &ctx->q_blk, &ctx->q_batch_rows, &ctx->q_wpos, &ctx->q_wpat, &ctx->q_wk0, &ctx->q_wk1, &ctx->q_pos, &ctx->q_cnt, &ctx->q_me, &ctx->q_pm, &ctx->q_depth,
                       &ctx->s_pos, &ctx->s_pdr, &ctx->s_nc, &ctx->s_nd, &ctx->s_batch_cnt, &ctx->w_val, &ctx->w_cov, &ctx->w_aux, &ctx->w_flags,
                       &ctx->w_blk, &ctx->w_huge, &ctx->m_state, &ctx->m_pos, &ctx->m_val, &ctx->m_cov, &ctx->m_batch_rows,
                       &ctx->f_state, &ctx->f_pos, &ctx->f_val, &ctx->f_qval, &ctx->f_n, &ctx->f_batch_rows, &ctx->f_rows, &ctx->f_pairtab, &ctx->fo_sel, &ctx->fo_flag, &ctx->fo_tmp, &ctx->fo_out, &ctx->f_redo, &ctx->f_terms, &ctx->f_soff, &ctx->f_snz, &ctx->f_sdisc, &ctx->f_quot,
-                      &ctx->p_state, &ctx->p_keys, &ctx->p_cnt, &ctx->p_out_key, &ctx->p_out_cnt, &ctx->p_batch_rows, &ctx->p_tflag, &ctx->p_tile_row0, &ctx->p_tile_rows})
+                      &ctx->p_keys, &ctx->p_cnt, &ctx->p_out_key, &ctx->p_out_cnt, &ctx->p_batch_rows})
         b->release();
+    for (TileRowTable *t : {&ctx->quartets, &ctx->pairs})
+        for (DevBuf *b : {&t->state, &t->snap, &t->tflag, &t->tile_row0, &t->tile_rows}) b->release();
     for (auto &g : ctx->groups) g.d_tab.release();
     for (auto &t : ctx->timed) { (void)hipEventDestroy(t.beg); (void)hipEventDestroy(t.end); }
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -468,10 +470,12 @@ int mth_reset(mth_ctx_t *ctx) {
     ctx->batches.clear();
     ctx->out_bound = 0;
     ctx->lpmd_reduced = false;
-    if (ctx->q_state.p) MTH_HIP(ctx, hipMemsetAsync(ctx->q_state.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    ctx->q_meta.clear();
-    ctx->q_pending.clear();                // queued batches' rows are dropped with the rest; their kernels precede the memset in stream order
-    ctx->q_rows = 0;
+    for (TileRowTable *t : {&ctx->quartets, &ctx->pairs}) {
+        if (t->state.p) MTH_HIP(ctx, hipMemsetAsync(t->state.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
+        t->meta.clear();
+        t->pending.clear();                // queued batches' rows are dropped with the rest; their kernels precede the memset in stream order
+        t->rows = 0;
+    }
     ctx->q_epoch += 1;
     if (ctx->m_state.p) MTH_HIP(ctx, hipMemsetAsync(ctx->m_state.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
     ctx->m_batches.clear();
@@ -479,10 +483,6 @@ int mth_reset(mth_ctx_t *ctx) {
     if (ctx->f_state.p) MTH_HIP(ctx, hipMemsetAsync(ctx->f_state.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
     ctx->f_batches.clear();
     ctx->f_rows_bound = 0;
-    if (ctx->p_state.p) MTH_HIP(ctx, hipMemsetAsync(ctx->p_state.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    ctx->p_meta.clear();
-    ctx->p_pending.clear();
-    ctx->p_rows = 0;
     for (uint64_t &k : ctx->multi_stats) k = 0;
     return MTH_OK;
 }

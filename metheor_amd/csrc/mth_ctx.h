@@ -44,9 +44,53 @@ struct PdrLane {
 }  // namespace mth
 
 struct mth_ctx;
-namespace mth { int quartet_resolve(mth_ctx *ctx); int pairs_resolve(mth_ctx *ctx); struct FusedQuartet; }
+namespace mth { struct FusedQuartet; }
 
 namespace mth {
+// ---- the tile-row table of a tile-kernel measure (ME / PM, LPMD pairs; driver: mth_tile_rows.hip) ----
+// a batch: heavy0 = first row of the global path's rows, tile_end = tiles of all batches up to and including it
+struct TileBatch { int32_t tid; uint64_t rows, heavy0, tile_end; };
+union TileParams { mth_quartet_params_t quartet; mth_lpmd_pairs_params_t pairs; };
+// what a measure brings to the driver; everything else of a batch is tile_rows_batch
+struct TileMeasure {
+    int (*tile_shift)(const mth_batch_t &d, const TileParams &p);                 // log2 of the batch's tile width, 13 .. 16
+    hipError_t (*grow_rows)(mth_ctx *ctx, uint64_t cap, uint64_t used);           // the row columns to cap rows, keeping the first `used`
+    // the tile kernel over the batch's ntiles tiles (per-tile arrays from tiles_before on; row_cap: rows it may write)
+    void (*launch_tiles)(mth_ctx *ctx, const mth_batch_t &d, const TileParams &p, int tile_shift, uint32_t ntiles, int32_t idx_base,
+                         uint64_t tiles_before, uint64_t row_cap);
+    // the global path for the tiles flagged in tflag; total: rows in use before it -> after it
+    int (*global_path)(mth_ctx *ctx, const mth_batch_t &d, const TileParams &p, int tile_shift, uint64_t &total);
+};
+const TileMeasure *quartet_measure();     // mth_quartet.hip
+const TileMeasure *pairs_measure();       // mth_pairs.hip
+struct TileRowTable {
+    const char *name, *what, *env;         // "[name] ..." debug line, "what: ..." error text, prefix of the MTH_*_ knobs
+    double rows_per_cpg;                   // output sizing of the next batch
+    const TileMeasure *measure;
+    // eight state words: [0] updates (counting pass of the global path) [1] total rows [2] first row of the global path's rows
+    // [3] its overflow flag [5] tiles left to the global path [6] tiles whose rows did not fit the output ([7]: the measure's own)
+    DevBuf state, snap;                    // snap: the state words as each queued batch's tile kernel left them
+    DevBuf tflag, tile_row0, tile_rows;    // per tile: 1 = left to the global path (latest batch only); first row and length (all batches)
+    std::vector<TileBatch> meta;
+    uint64_t cap = 0, rows = 0;            // row capacity, rows in use (exact as of the last synchronous batch / tile_rows_resolve)
+    uint64_t rows_est = 0;                 // upper bound of the rows in use while batches are queued
+    bool learned = false;                  // a synchronous batch has set rows_per_cpg
+    int queue_off = -1;                    // MTH_*_QUEUE=0 (read once)
+    // batches queued without a host sync: their device-side batch (its arrays stay untouched until the resolve)
+    struct Queued { mth_batch_t d; TileParams params; int32_t tid; uint64_t n_cpgs; };
+    std::vector<Queued> pending;
+    unsigned long long *words() const { return state.as<unsigned long long>(); }
+    uint64_t tiles() const { return meta.empty() ? 0 : meta.back().tile_end; }
+};
+int tile_rows_accumulate(mth_ctx *ctx, TileRowTable &t, const mth_batch_t &batch, const TileParams &params);
+int tile_rows_resolve(mth_ctx *ctx, TileRowTable &t);
+// the pieces the fused pass (mth_multi.hip) drives itself: state words and per-tile arrays for ntiles more tiles, the row columns,
+// the (re)start of a batch at rows_before, and a finished batch into the table
+int tile_rows_open(mth_ctx *ctx, TileRowTable &t, uint64_t ntiles);
+hipError_t tile_rows_grow(mth_ctx *ctx, TileRowTable &t, uint64_t cap, uint64_t used);
+int tile_rows_rewind(mth_ctx *ctx, TileRowTable &t, uint64_t rows_before);
+void tile_rows_commit(TileRowTable &t, TileBatch meta, uint64_t total, uint64_t n_cpgs);
+
 // a prepared batch (include/metheor_hip.h, "prepared batches"): the device-resident batch, the buffers it owns when it was made
 // from a host batch, its fine read index, and a device block with what k_build_index found (error bits, safe_hi)
 struct Prepared {
@@ -137,20 +181,9 @@ struct mth_ctx {
     size_t batch_cnt_cap = 0;
 
     // ME / PM (mth_quartet.hip): hash table of the batch in flight + appended result rows
-    mth::DevBuf q_state, q_keys, q_hist, q_blk, q_batch_rows, q_tflag, q_tile_row0, q_tile_rows, q_wpos, q_wpat, q_wk0, q_wk1;
-    // a batch of the tile-kernel measures (quartets, pairs): heavy0 = first row of the global path's rows, tile_end = tiles of
-    // all batches up to and including it
-    struct TileBatch { int32_t tid; uint64_t rows, heavy0, tile_end; };
-    std::vector<TileBatch> q_meta;
-    double q_rows_per_cpg = 0.15;          // output sizing of the next batch
+    mth::TileRowTable quartets{"quartet", "quartets", "MTH_QUARTET", 0.15, mth::quartet_measure()};
+    mth::DevBuf q_keys, q_hist, q_blk, q_batch_rows, q_wpos, q_wpat, q_wk0, q_wk1;
     mth::DevBuf q_pos, q_cnt, q_me, q_pm, q_depth;
-    uint64_t q_cap = 0, q_rows = 0;        // row capacity, rows in use (exact as of the last synchronous batch / quartet_resolve)
-    // batches queued without a host sync (mth_quartet.hip, quartet_batch): their device-side batch, a snapshot of the state words each
-    struct QueuedBatch { mth_batch_t d; mth_quartet_params_t params; int32_t tid; uint64_t n_cpgs; };
-    std::vector<QueuedBatch> q_pending;
-    mth::DevBuf q_snap;
-    uint64_t q_rows_est = 0;               // upper bound of the rows in use while batches are queued
-    bool q_learned = false;                // a synchronous batch has set q_rows_per_cpg
     bool tile_queue_hold = false;          // set by the accumulate call that is queueing a batch: enter() leaves the queues alone
     // the row order worked out by a count-only mth_quartet_fetch, kept for the fetch that follows it (same min_depth,
     // nothing accumulated in between: q_epoch)
@@ -177,15 +210,8 @@ struct mth_ctx {
     uint64_t fo_rows = 0;
 
     // LPMD per-pair table (mth_pairs.hip)
-    mth::DevBuf p_state, p_keys, p_cnt, p_out_key, p_out_cnt, p_batch_rows, p_tflag, p_tile_row0, p_tile_rows;
-    uint64_t p_cap = 0, p_rows = 0;        // row capacity of p_out_*, rows in use (known exactly: one sync per batch)
-    double p_rows_per_cpg = 0.1;           // output sizing of the next batch
-    std::vector<TileBatch> p_meta;
-    struct QueuedPairs { mth_batch_t d; mth_lpmd_pairs_params_t params; int32_t tid; uint64_t n_cpgs; };   // as q_pending (mth_pairs.hip)
-    std::vector<QueuedPairs> p_pending;
-    mth::DevBuf p_snap;
-    uint64_t p_rows_est = 0;
-    bool p_learned = false;
+    mth::TileRowTable pairs{"pairs", "pairs", "MTH_PAIRS", 0.1, mth::pairs_measure()};
+    mth::DevBuf p_keys, p_cnt, p_out_key, p_out_cnt, p_batch_rows;
 
     // multi-GPU exchange step (mth_rccl.hip): communicator of the one-process-per-GPU form; lpmd_reduced = DevState.lpmd
     // already holds the all-reduced totals (cleared by the next batch that adds to them)
@@ -297,5 +323,29 @@ int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_mhl_pa
 int launch_fdrp_wtile(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_fdrp_params_t &p, const uint16_t *pair_tab, uint32_t *redo_list, uint32_t *redo_cnt);
 int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_pdr_lpmd_params_t &p,
                     const TileSink *sink = nullptr, bool pipelined = false);
+
+// How a fetch opens: the rows of a table live in [0, rows) with gaps (the unused tails of the tile kernels' chunks).  Per batch,
+// row(meta, device row, from the global path) sees its tiles' rows in tile order -- sorted, each tile sorts in LDS -- and then the
+// rows [heavy0, batch end) of the global path, in table order; batch_end(batch number) follows.
+template <class Row, class End>
+int tile_rows_walk(mth_ctx *ctx, const TileRowTable &t, Row &&row, End &&batch_end) {
+    const uint64_t n_tiles = t.tiles();
+    std::vector<unsigned long long> trow0(n_tiles);
+    std::vector<uint32_t> trows(n_tiles);
+    if (n_tiles) {
+        MTH_HIP(ctx, hipMemcpy(trow0.data(), t.tile_row0.p, n_tiles * 8, hipMemcpyDeviceToHost));
+        MTH_HIP(ctx, hipMemcpy(trows.data(), t.tile_rows.p, n_tiles * 4, hipMemcpyDeviceToHost));
+    }
+    uint64_t rows_end = 0, tile = 0;
+    for (size_t b = 0; b < t.meta.size(); ++b) {
+        const TileBatch &mb = t.meta[b];
+        rows_end += mb.rows;
+        for (; tile < mb.tile_end; ++tile)
+            for (uint32_t j = 0; j < trows[tile]; ++j) row(mb, (uint64_t)trow0[tile] + j, false);
+        for (uint64_t i = mb.heavy0; i < rows_end; ++i) row(mb, i, true);
+        batch_end(b);
+    }
+    return MTH_OK;
+}
 
 }  // namespace mth

@@ -33,40 +33,26 @@ namespace mth {
 // everywhere: force).  *fused: the pass ran (else the quartet side went through mth_quartet_accumulate as in the split form).
 static int fused_batch(mth_ctx *ctx, const mth_batch_t &pb, const mth_multi_params_t &mp, bool force, bool *fused) {
     *fused = false;
-    MTH_ENTER(ctx);                                         // queued ME / PM batches settled: ctx->q_rows is exact
+    MTH_ENTER(ctx);                                         // queued ME / PM batches settled: the table's row count is exact
     hipStream_t s = ctx->stream;
-    if (!ctx->q_state.p) {
-        MTH_HIP(ctx, ctx->q_state.reserve(8 * sizeof(unsigned long long), s));
-        MTH_HIP(ctx, hipMemsetAsync(ctx->q_state.p, 0, 8 * sizeof(unsigned long long), s));
-    }
-    unsigned long long *qs = ctx->q_state.as<unsigned long long>();
-    const uint64_t rows_before = ctx->q_rows;
-    const uint64_t tiles_before = ctx->q_meta.empty() ? 0 : ctx->q_meta.back().tile_end;
+    TileRowTable &t = ctx->quartets;
+    const uint64_t rows_before = t.rows, tiles_before = t.tiles();
     const int64_t region_len = (int64_t)pb.region_end - pb.region_beg;
     // a wide-form tile is at least 8192 positions (half a 16384-bp slice); at most one quartet row per CpG call of the batch
     const uint32_t max_tiles = (uint32_t)std::max<int64_t>(region_len, 0) / 8192u + 2u;
-    const uint64_t cap = rows_before + pb.n_cpgs + 1024;
-    if (cap > ctx->q_cap) {
-        MTH_HIP(ctx, ctx->q_pos.reserve(cap * 16, s, true, rows_before * 16));
-        MTH_HIP(ctx, ctx->q_cnt.reserve(cap * 64, s, true, rows_before * 64));
-        MTH_HIP(ctx, ctx->q_me.reserve(cap * 4, s, true, rows_before * 4));
-        MTH_HIP(ctx, ctx->q_pm.reserve(cap * 4, s, true, rows_before * 4));
-        MTH_HIP(ctx, ctx->q_depth.reserve(cap * 4, s, true, rows_before * 4));
-        ctx->q_cap = cap;
-    }
-    MTH_HIP(ctx, ctx->q_tflag.reserve((size_t)max_tiles * 4, s));
-    MTH_HIP(ctx, ctx->q_tile_row0.reserve((tiles_before + max_tiles) * 8, s, true, tiles_before * 8));
-    MTH_HIP(ctx, ctx->q_tile_rows.reserve((tiles_before + max_tiles) * 4, s, true, tiles_before * 4));
-    hipLaunchKernelGGL(k_quartet_rewind, dim3(1), dim3(1), 0, s, qs, (unsigned long long)rows_before);
-    MTH_HIP(ctx, hipGetLastError());
+    int rc = tile_rows_open(ctx, t, max_tiles);
+    if (rc) return rc;
+    if (rows_before + pb.n_cpgs + 1024 > t.cap) MTH_HIP(ctx, tile_rows_grow(ctx, t, rows_before + pb.n_cpgs + 1024, rows_before));
+    if ((rc = tile_rows_rewind(ctx, t, rows_before))) return rc;
+    unsigned long long *qs = t.words();
     FusedQuartet fq;
     fq.force = force ? 1 : 0;
     fq.force_heavy = getenv("MTH_MULTI_FORCE_HANDBACK") ? 1 : 0;       // tests: every tile handed back
     fq.min_qual = mp.quartet.min_qual;
-    fq.qs = qs; fq.row_cap = ctx->q_cap; fq.max_tiles = max_tiles;
-    fq.tile_flag = ctx->q_tflag.as<uint32_t>();
-    fq.tile_row0 = ctx->q_tile_row0.as<unsigned long long>() + tiles_before;
-    fq.tile_rows = ctx->q_tile_rows.as<uint32_t>() + tiles_before;
+    fq.qs = qs; fq.row_cap = t.cap; fq.max_tiles = max_tiles;
+    fq.tile_flag = t.tflag.as<uint32_t>();
+    fq.tile_row0 = t.tile_row0.as<unsigned long long>() + tiles_before;
+    fq.tile_rows = t.tile_rows.as<uint32_t>() + tiles_before;
     fq.out_pos = ctx->q_pos.as<int32_t>(); fq.out_cnt = ctx->q_cnt.as<uint32_t>(); fq.out_me = ctx->q_me.as<float>();
     fq.out_pm = ctx->q_pm.as<float>(); fq.out_depth = ctx->q_depth.as<uint32_t>();
     fq.taken = false; fq.ntiles = 0;
@@ -74,7 +60,7 @@ static int fused_batch(mth_ctx *ctx, const mth_batch_t &pb, const mth_multi_para
     p.want_pdr = (mp.want & MTH_MULTI_PDR) ? 1 : 0;
     p.want_lpmd = (mp.want & MTH_MULTI_LPMD) ? 1 : 0;
     ctx->fuse_q = &fq;
-    int rc = mth_pdr_lpmd_accumulate(ctx, &pb, &p);
+    rc = mth_pdr_lpmd_accumulate(ctx, &pb, &p);
     ctx->fuse_q = nullptr;
     if (rc) return rc;
     if (!fq.taken) return mth_quartet_accumulate(ctx, &pb, &mp.quartet);     // (the dense form ran, or a PDR-only exact pass)
@@ -88,11 +74,8 @@ static int fused_batch(mth_ctx *ctx, const mth_batch_t &pb, const mth_multi_para
         ctx->multi_stats[3] += st[6] ? fq.ntiles : st[5];
         return mth_quartet_accumulate(ctx, &pb, &mp.quartet);
     }
-    const uint64_t total = st[1];
-    ctx->q_meta.push_back(mth_ctx::TileBatch{pb.tid, total - rows_before, total, tiles_before + fq.ntiles});
-    ctx->q_rows = total;
+    tile_rows_commit(t, TileBatch{pb.tid, 0, st[1], tiles_before + fq.ntiles}, st[1], pb.n_cpgs);
     ctx->q_epoch += 1;
-    if (pb.n_cpgs) { ctx->q_rows_per_cpg = std::max(ctx->q_rows_per_cpg * 0.5, (double)(total - rows_before) / (double)pb.n_cpgs); ctx->q_learned = true; }
     return MTH_OK;
 }
 

@@ -57,8 +57,6 @@ struct PairArgs {
 constexpr int PT_OCC = 6;
 constexpr int PT_S = 2048, PT_B = 256, PT_U = 2, PT_CHUNK = 1024, PT_GRID = 8192;   // tile kernel: LDS slots, threads, reads per thread and round (the tile
                                                    // width is a template parameter: 8192 / 16384 / 32768, chosen per batch)
-constexpr int P_STATE_WORDS = 8;
-constexpr int P_QUEUE_MAX = 4096;       // queued batches between two resolves
 constexpr int PT_NC = 8;                                 // calls of a read parked in LDS for the pair loops
 
 // COUNT: only count the updates (table sizing); otherwise insert them
@@ -420,236 +418,142 @@ __global__ __launch_bounds__(PT_B, PT_OCC) void k_pairs_tile(const PTileArgs a) 
     }
 }
 
-// restart of a batch whose rows did not fit: back to the row count before it
-__global__ void k_pairs_rewind(unsigned long long *ps, unsigned long long rows_before) { ps[1] = rows_before; ps[5] = 0; ps[6] = 0; }
+// ---- what the pairs table brings to the tile-row driver (mth_tile_rows.hip) ----------------------------------------
+// Tile width (see mth_quartet.hip): distinct pairs per tile ~ sites per tile x sites per pair window
+static int pairs_tile_shift(const mth_batch_t &d, const TileParams &p) {
+    const int64_t region_len = (int64_t)d.region_end - d.region_beg;
+    int tile_shift = 13;
+    if (d.n_reads && region_len > 0) {
+        const double sites_per_bp = (double)d.n_cpgs / (double)d.n_reads / (double)std::max(d.max_span, 1);
+        const double reads_per_bp = (double)d.n_reads / (double)region_len;
+        const double window = std::max(1.0, (double)std::min<int64_t>((int64_t)p.pairs.max_distance - std::max(p.pairs.min_distance, 0) + 1, d.max_span));
+        while (tile_shift < 16 && sites_per_bp * (double)(2 << tile_shift) * std::max(1.0, sites_per_bp * window) <= 0.3 * PT_S &&
+               reads_per_bp * (double)((2 << tile_shift) + d.max_span + 2 * IDX_Q) <= 30000.0)
+            ++tile_shift;
+    }
+    if (const char *e = getenv("MTH_PAIRS_TILE_SHIFT")) tile_shift = std::min(16, std::max(13, atoi(e)));   // tests / tuning
+    return tile_shift;
+}
 
-// a queued batch's state words as its tile kernel left them (mth_quartet.hip: k_quartet_snap)
-__global__ void k_pairs_snap(const unsigned long long *__restrict__ ps, unsigned long long *__restrict__ snap) {
-    if (threadIdx.x < P_STATE_WORDS) snap[threadIdx.x] = ps[threadIdx.x];
+static hipError_t pairs_grow_rows(mth_ctx *ctx, uint64_t cap, uint64_t used) {
+    const hipError_t e = ctx->p_out_key.reserve(cap * 8, ctx->stream, true, used * 8);
+    return e != hipSuccess ? e : ctx->p_out_cnt.reserve(cap * 8, ctx->stream, true, used * 8);
+}
+
+static void pairs_launch_tiles(mth_ctx *ctx, const mth_batch_t &d, const TileParams &p, int tile_shift, uint32_t ntiles, int32_t idx_base,
+                               uint64_t tiles_before, uint64_t row_cap) {
+    const TileRowTable &t = ctx->pairs;
+    const mth_lpmd_pairs_params_t *params = &p.pairs;
+    hipStream_t s = ctx->stream;
+    unsigned long long *ps = t.words();
+    const bool r8 = d.cpg_rel != nullptr;
+    PTileArgs a;
+    a.read_start = d.read_start; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
+    a.idx = idx_ptr(ctx); a.cpg_rel = r8 ? (const void *)d.cpg_rel : (const void *)d.cpg_rel16;
+    a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span;
+    a.min_dist = params->min_distance; a.max_dist = params->max_distance; a.n_reads = d.n_reads; a.ntiles = ntiles; a.n_cpgs = (uint32_t)d.n_cpgs;
+    a.min_qual = params->min_qual; a.force_heavy = getenv("MTH_PAIRS_FORCE_GLOBAL") ? 1 : 0;
+    a.row_total = ps + 1; a.row_cap = row_cap; a.unfit = ps + 6; a.n_heavy = ps + 5;
+    a.tile_flag = t.tflag.as<uint32_t>();
+    a.tile_row0 = t.tile_row0.as<unsigned long long>() + tiles_before;
+    a.tile_rows = t.tile_rows.as<uint32_t>() + tiles_before;
+    a.out_key = ctx->p_out_key.as<unsigned long long>(); a.out_cnt = ctx->p_out_cnt.as<uint32_t>(); a.st = ctx->d_state;
+    LaunchTimer lt(ctx, K_PAIRSTILE);
+    if (tile_shift == 13) {
+        if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 13>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+        else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 13>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+    } else if (tile_shift == 14) {
+        if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 14>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+        else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 14>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+    } else if (tile_shift == 15) {
+        if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 15>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+        else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 15>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+    } else {
+        if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 16>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+        else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 16>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
+    }
+}
+
+// The tiles the LDS table could not hold: the global table, for their pairs only.
+static int pairs_global_path(mth_ctx *ctx, const mth_batch_t &d, const TileParams &p, int tile_shift, uint64_t &total) {
+    TileRowTable &t = ctx->pairs;
+    const mth_lpmd_pairs_params_t *params = &p.pairs;
+    hipStream_t s = ctx->stream;
+    unsigned long long *ps = t.words();
+    const bool r8 = d.cpg_rel != nullptr;
+    PairArgs g;
+    g.read_mapq = d.read_mapq; g.cpg_off = d.cpg_off; g.cpg_pos = d.cpg_pos;
+    g.cpg_rel = r8 ? (const void *)d.cpg_rel : (const void *)d.cpg_rel16;
+    g.keys = nullptr; g.cnt = nullptr; g.n_updates = ps; g.mask = 0; g.overflow = ps + 3;
+    g.region_beg = d.region_beg; g.region_end = d.region_end; g.min_dist = params->min_distance; g.max_dist = params->max_distance;
+    g.n_reads = d.n_reads; g.min_qual = params->min_qual; g.tile_flag = t.tflag.as<uint32_t>(); g.tile_shift = tile_shift;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)d.n_reads + 255) / 256 + 1, 8192);
+    MTH_HIP(ctx, hipMemsetAsync(ps, 0, sizeof(unsigned long long), s));
+    {
+        LaunchTimer lt(ctx, K_PAIRS);
+        if (r8) hipLaunchKernelGGL((k_pairs<uint8_t, true>), dim3(grid), dim3(256), 0, s, g);
+        else hipLaunchKernelGGL((k_pairs<uint16_t, true>), dim3(grid), dim3(256), 0, s, g);
+    }
+    unsigned long long bound = 0;
+    MTH_HIP(ctx, hipMemcpyAsync(&bound, ps, sizeof bound, hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipStreamSynchronize(s));
+    // `bound` counts pair UPDATES; at depth D there are ~D per distinct pair, and the table is cleared and scanned once per
+    // batch: start at bound / 2 slots and redo 4x larger if an insert ran out of probes (cannot happen at 2 x bound)
+    unsigned long long n_slots = 1024;
+    while (n_slots < bound / 2) n_slots <<= 1;
+    if (const char *e = getenv("MTH_PAIRS_SLOTS_MIN")) { const unsigned long long k = strtoull(e, nullptr, 10); if (k >= 16) { n_slots = 16; while (n_slots < k) n_slots <<= 1; } }   // tests: force the retry
+    for (;;) {
+        MTH_HIP(ctx, ctx->p_keys.reserve(n_slots * 8, s));
+        MTH_HIP(ctx, ctx->p_cnt.reserve(n_slots * 8, s));
+        MTH_HIP(ctx, hipMemsetAsync(ctx->p_keys.p, 0xFF, n_slots * 8, s));
+        MTH_HIP(ctx, hipMemsetAsync(ctx->p_cnt.p, 0, n_slots * 8, s));
+        MTH_HIP(ctx, hipMemsetAsync(ps + 3, 0, sizeof(unsigned long long), s));
+        g.keys = ctx->p_keys.as<unsigned long long>(); g.cnt = ctx->p_cnt.as<uint32_t>(); g.mask = n_slots - 1;
+        {
+            LaunchTimer lt(ctx, K_PAIRS);
+            if (r8) hipLaunchKernelGGL((k_pairs<uint8_t, false>), dim3(grid), dim3(256), 0, s, g);
+            else hipLaunchKernelGGL((k_pairs<uint16_t, false>), dim3(grid), dim3(256), 0, s, g);
+        }
+        unsigned long long ovf = 0;
+        MTH_HIP(ctx, hipMemcpyAsync(&ovf, ps + 3, sizeof ovf, hipMemcpyDeviceToHost, s));
+        MTH_HIP(ctx, hipStreamSynchronize(s));
+        if (!ovf) break;
+        n_slots <<= 2;
+    }
+    if (total + bound > t.cap) MTH_HIP(ctx, tile_rows_grow(ctx, t, total + bound, total));     // distinct pairs <= updates
+    const uint32_t nblk = (uint32_t)((n_slots + 256 * SCAN_PER - 1) / (256 * SCAN_PER));
+    MTH_HIP(ctx, ctx->w_blk.reserve((size_t)nblk * 4, s));
+    MTH_HIP(ctx, ctx->p_batch_rows.reserve(4, s));
+    hipLaunchKernelGGL(k_pairs_blockcount, dim3(nblk), dim3(256), 0, s, ctx->p_keys.as<unsigned long long>(), n_slots,
+                       ctx->w_blk.as<uint32_t>());
+    hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, ctx->w_blk.as<uint32_t>(), nblk, ps + 1, ps + 2,
+                       ctx->p_batch_rows.as<uint32_t>(), 0u);
+    hipLaunchKernelGGL(k_pairs_emit, dim3(nblk), dim3(256), 0, s, ctx->p_keys.as<unsigned long long>(), ctx->p_cnt.as<uint32_t>(),
+                       n_slots, ctx->w_blk.as<uint32_t>(), ps + 2, ctx->p_out_key.as<unsigned long long>(),
+                       ctx->p_out_cnt.as<uint32_t>());
+    unsigned long long t2 = 0;
+    MTH_HIP(ctx, hipMemcpyAsync(&t2, ps + 1, sizeof t2, hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipStreamSynchronize(s));
+    total = t2;
+    return MTH_OK;
+}
+
+const TileMeasure *pairs_measure() {
+    static const TileMeasure m = {pairs_tile_shift, pairs_grow_rows, pairs_launch_tiles, pairs_global_path};
+    return &m;
 }
 
 }  // namespace mth
 
 using namespace mth;
 
-// One batch, synchronous or queued: the scheme of mth_quartet.hip's quartet_batch / quartet_resolve.
-static int pairs_batch(mth_ctx *ctx, const mth_batch_t &d, const mth_lpmd_pairs_params_t *params, int32_t batch_tid, bool queued) {
-    int rc = MTH_OK;
-    hipStream_t s = ctx->stream;
-    if (!ctx->p_state.p) {
-        MTH_HIP(ctx, ctx->p_state.reserve(P_STATE_WORDS * sizeof(unsigned long long), s));
-        MTH_HIP(ctx, hipMemsetAsync(ctx->p_state.p, 0, P_STATE_WORDS * sizeof(unsigned long long), s));
-    }
-    // [0] updates (counting pass of the global path) [1] total rows [2] first row of the global path's rows
-    // [3] its overflow flag [5] tiles left to the global path [6] tiles whose rows did not fit the output
-    unsigned long long *ps = ctx->p_state.as<unsigned long long>();
-    const int64_t region_len = (int64_t)d.region_end - d.region_beg;
-    // Tile width (see mth_quartet.hip): distinct pairs per tile ~ sites per tile x sites per pair window
-    int tile_shift = 13;
-    if (d.n_reads && region_len > 0) {
-        const double sites_per_bp = (double)d.n_cpgs / (double)d.n_reads / (double)std::max(d.max_span, 1);
-        const double reads_per_bp = (double)d.n_reads / (double)region_len;
-        const double window = std::max(1.0, (double)std::min<int64_t>((int64_t)params->max_distance - std::max(params->min_distance, 0) + 1, d.max_span));
-        while (tile_shift < 16 && sites_per_bp * (double)(2 << tile_shift) * std::max(1.0, sites_per_bp * window) <= 0.3 * PT_S &&
-               reads_per_bp * (double)((2 << tile_shift) + d.max_span + 2 * IDX_Q) <= 30000.0)
-            ++tile_shift;
-    }
-    if (const char *e = getenv("MTH_PAIRS_TILE_SHIFT")) tile_shift = std::min(16, std::max(13, atoi(e)));   // tests / tuning
-    const int PT_W = 1 << tile_shift;
-    const uint32_t ntiles = (d.n_reads && region_len > 0) ? (uint32_t)((region_len + PT_W - 1) / PT_W) : 0u;
-    const uint64_t tiles_before = ctx->p_meta.empty() ? 0 : ctx->p_meta.back().tile_end;
-    const uint64_t rows_before = queued && !ctx->p_pending.empty() ? ctx->p_rows_est : ctx->p_rows;
-    mth_ctx::TileBatch meta{batch_tid, 0, rows_before, tiles_before + ntiles};
-    if (!ntiles && queued && !ctx->p_pending.empty()) queued = false, rc = pairs_resolve(ctx);
-    if (rc) return rc;
-    if (!ntiles) { meta.heavy0 = ctx->p_rows; ctx->p_meta.push_back(meta); return MTH_OK; }
-    const bool r8 = d.cpg_rel != nullptr;
-    int32_t idx_base = 0;
-    uint32_t nt = 0;
-    rc = build_read_index(ctx, d, PT_W, idx_base, nt);
-    if (rc) return rc;
-    MTH_HIP(ctx, ctx->p_tflag.reserve((size_t)ntiles * 4, s));
-    MTH_HIP(ctx, ctx->p_tile_row0.reserve((tiles_before + ntiles) * 8, s, true, tiles_before * 8));
-    MTH_HIP(ctx, ctx->p_tile_rows.reserve((tiles_before + ntiles) * 4, s, true, tiles_before * 4));
-    // output size: rows per CpG call of the batches so far (first batch: a guess); the kernel reports the exact need
-    uint64_t want = rows_before + (uint64_t)((double)d.n_cpgs * ctx->p_rows_per_cpg * 1.25) + 4096;
-    if (const char *e = getenv("MTH_PAIRS_ROWS_MIN")) want = rows_before + strtoull(e, nullptr, 10);   // tests: force the redo
-    unsigned long long *st = ctx->h_words;     // pinned: the read-back does not go through a staging copy
-    for (int attempt = 0;; ++attempt) {
-        if (want > ctx->p_cap) {
-            const uint64_t cap = want + (queued ? want / 4 : 0), used = std::min<uint64_t>(rows_before, ctx->p_cap);
-            MTH_HIP(ctx, ctx->p_out_key.reserve(cap * 8, s, true, used * 8));
-            MTH_HIP(ctx, ctx->p_out_cnt.reserve(cap * 8, s, true, used * 8));
-            ctx->p_cap = cap;
-        }
-        if (!queued || ctx->p_pending.empty()) hipLaunchKernelGGL(k_pairs_rewind, dim3(1), dim3(1), 0, s, ps, (unsigned long long)rows_before);
-        PTileArgs a;
-        a.read_start = d.read_start; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
-        a.idx = idx_ptr(ctx); a.cpg_rel = r8 ? (const void *)d.cpg_rel : (const void *)d.cpg_rel16;
-        a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span;
-        a.min_dist = params->min_distance; a.max_dist = params->max_distance; a.n_reads = d.n_reads; a.ntiles = ntiles; a.n_cpgs = (uint32_t)d.n_cpgs;
-        a.min_qual = params->min_qual; a.force_heavy = getenv("MTH_PAIRS_FORCE_GLOBAL") ? 1 : 0;
-        // (a queued batch must stay within its estimate: see quartet_batch)
-        a.row_total = ps + 1; a.row_cap = queued ? std::min<uint64_t>(ctx->p_cap, want) : ctx->p_cap; a.unfit = ps + 6; a.n_heavy = ps + 5;
-        a.tile_flag = ctx->p_tflag.as<uint32_t>();
-        a.tile_row0 = ctx->p_tile_row0.as<unsigned long long>() + tiles_before;
-        a.tile_rows = ctx->p_tile_rows.as<uint32_t>() + tiles_before;
-        a.out_key = ctx->p_out_key.as<unsigned long long>(); a.out_cnt = ctx->p_out_cnt.as<uint32_t>(); a.st = ctx->d_state;
-        {
-            LaunchTimer lt(ctx, K_PAIRSTILE);
-            if (tile_shift == 13) {
-                if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 13>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-                else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 13>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-            } else if (tile_shift == 14) {
-                if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 14>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-                else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 14>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-            } else if (tile_shift == 15) {
-                if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 15>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-                else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 15>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-            } else {
-                if (r8) hipLaunchKernelGGL((k_pairs_tile<uint8_t, 16>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-                else hipLaunchKernelGGL((k_pairs_tile<uint16_t, 16>), dim3(std::min<uint32_t>(ntiles, PT_GRID)), dim3(PT_B), 0, s, a);
-            }
-        }
-        if (queued) {
-            const size_t k = ctx->p_pending.size();
-            MTH_HIP(ctx, ctx->p_snap.reserve((size_t)P_QUEUE_MAX * P_STATE_WORDS * sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(k_pairs_snap, dim3(1), dim3(64), 0, s, (const unsigned long long *)ps, ctx->p_snap.as<unsigned long long>() + k * P_STATE_WORDS);
-            MTH_HIP(ctx, hipGetLastError());
-            ctx->p_pending.push_back(mth_ctx::QueuedPairs{d, *params, batch_tid, d.n_cpgs});
-            ctx->p_rows_est = want;
-            ctx->p_meta.push_back(meta);                   // rows / heavy0: pairs_resolve
-            return MTH_OK;
-        }
-        MTH_HIP(ctx, hipMemcpyAsync(st, ps, P_STATE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        MTH_HIP(ctx, hipStreamSynchronize(s));            // one sync per batch: rows, flagged tiles, fit
-        if (!st[6]) break;
-        if (attempt) return fail(ctx, MTH_ERR_STATE, "pairs: rows did not fit an exactly sized output");
-        want = st[1];                                     // every tile claimed its range: this is the exact size
-    }
-    uint64_t total = st[1];
-    meta.heavy0 = total;
-    if (st[5]) {
-        // The tiles the LDS table could not hold: the global table, for their pairs only.
-        PairArgs g;
-        g.read_mapq = d.read_mapq; g.cpg_off = d.cpg_off; g.cpg_pos = d.cpg_pos;
-        g.cpg_rel = r8 ? (const void *)d.cpg_rel : (const void *)d.cpg_rel16;
-        g.keys = nullptr; g.cnt = nullptr; g.n_updates = ps; g.mask = 0; g.overflow = ps + 3;
-        g.region_beg = d.region_beg; g.region_end = d.region_end; g.min_dist = params->min_distance; g.max_dist = params->max_distance;
-        g.n_reads = d.n_reads; g.min_qual = params->min_qual; g.tile_flag = ctx->p_tflag.as<uint32_t>(); g.tile_shift = tile_shift;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)d.n_reads + 255) / 256 + 1, 8192);
-        MTH_HIP(ctx, hipMemsetAsync(ps, 0, sizeof(unsigned long long), s));
-        {
-            LaunchTimer lt(ctx, K_PAIRS);
-            if (r8) hipLaunchKernelGGL((k_pairs<uint8_t, true>), dim3(grid), dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((k_pairs<uint16_t, true>), dim3(grid), dim3(256), 0, s, g);
-        }
-        unsigned long long bound = 0;
-        MTH_HIP(ctx, hipMemcpyAsync(&bound, ps, sizeof bound, hipMemcpyDeviceToHost, s));
-        MTH_HIP(ctx, hipStreamSynchronize(s));
-        // `bound` counts pair UPDATES; at depth D there are ~D per distinct pair, and the table is cleared and scanned once per
-        // batch: start at bound / 2 slots and redo 4x larger if an insert ran out of probes (cannot happen at 2 x bound)
-        unsigned long long n_slots = 1024;
-        while (n_slots < bound / 2) n_slots <<= 1;
-        if (const char *e = getenv("MTH_PAIRS_SLOTS_MIN")) { const unsigned long long k = strtoull(e, nullptr, 10); if (k >= 16) { n_slots = 16; while (n_slots < k) n_slots <<= 1; } }   // tests: force the retry
-        for (;;) {
-            MTH_HIP(ctx, ctx->p_keys.reserve(n_slots * 8, s));
-            MTH_HIP(ctx, ctx->p_cnt.reserve(n_slots * 8, s));
-            MTH_HIP(ctx, hipMemsetAsync(ctx->p_keys.p, 0xFF, n_slots * 8, s));
-            MTH_HIP(ctx, hipMemsetAsync(ctx->p_cnt.p, 0, n_slots * 8, s));
-            MTH_HIP(ctx, hipMemsetAsync(ps + 3, 0, sizeof(unsigned long long), s));
-            g.keys = ctx->p_keys.as<unsigned long long>(); g.cnt = ctx->p_cnt.as<uint32_t>(); g.mask = n_slots - 1;
-            {
-                LaunchTimer lt(ctx, K_PAIRS);
-                if (r8) hipLaunchKernelGGL((k_pairs<uint8_t, false>), dim3(grid), dim3(256), 0, s, g);
-                else hipLaunchKernelGGL((k_pairs<uint16_t, false>), dim3(grid), dim3(256), 0, s, g);
-            }
-            unsigned long long ovf = 0;
-            MTH_HIP(ctx, hipMemcpyAsync(&ovf, ps + 3, sizeof ovf, hipMemcpyDeviceToHost, s));
-            MTH_HIP(ctx, hipStreamSynchronize(s));
-            if (!ovf) break;
-            n_slots <<= 2;
-        }
-        const uint64_t need = total + bound;              // distinct pairs <= updates
-        if (need > ctx->p_cap) {
-            MTH_HIP(ctx, ctx->p_out_key.reserve(need * 8, s, true, total * 8));
-            MTH_HIP(ctx, ctx->p_out_cnt.reserve(need * 8, s, true, total * 8));
-            ctx->p_cap = need;
-        }
-        const uint32_t nblk = (uint32_t)((n_slots + 256 * SCAN_PER - 1) / (256 * SCAN_PER));
-        MTH_HIP(ctx, ctx->w_blk.reserve((size_t)nblk * 4, s));
-        MTH_HIP(ctx, ctx->p_batch_rows.reserve(4, s));
-        hipLaunchKernelGGL(k_pairs_blockcount, dim3(nblk), dim3(256), 0, s, ctx->p_keys.as<unsigned long long>(), n_slots,
-                           ctx->w_blk.as<uint32_t>());
-        hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, ctx->w_blk.as<uint32_t>(), nblk, ps + 1, ps + 2,
-                           ctx->p_batch_rows.as<uint32_t>(), 0u);
-        hipLaunchKernelGGL(k_pairs_emit, dim3(nblk), dim3(256), 0, s, ctx->p_keys.as<unsigned long long>(), ctx->p_cnt.as<uint32_t>(),
-                           n_slots, ctx->w_blk.as<uint32_t>(), ps + 2, ctx->p_out_key.as<unsigned long long>(),
-                           ctx->p_out_cnt.as<uint32_t>());
-        unsigned long long t2 = 0;
-        MTH_HIP(ctx, hipMemcpyAsync(&t2, ps + 1, sizeof t2, hipMemcpyDeviceToHost, s));
-        MTH_HIP(ctx, hipStreamSynchronize(s));
-        total = t2;
-    }
-    MTH_HIP(ctx, hipGetLastError());
-    meta.rows = total - rows_before;
-    ctx->p_rows = total;
-    if (d.n_cpgs) { ctx->p_rows_per_cpg = std::max(ctx->p_rows_per_cpg * 0.5, (double)meta.rows / (double)d.n_cpgs); ctx->p_learned = true; }
-    ctx->p_meta.push_back(meta);
-    return MTH_OK;
-}
-
-namespace mth {
-
-int pairs_resolve(mth_ctx *ctx) {
-    if (ctx->p_pending.empty()) return MTH_OK;
-    // (a replay below rebuilds its batch's read index in the context's own buffer: whatever prepared batch the latest entry point
-    // worked on is not this one's)
-    ctx->cur_prep = nullptr; ctx->cur_idx = nullptr;
-    MTH_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<mth_ctx::QueuedPairs> pend;
-    pend.swap(ctx->p_pending);
-    const size_t n = pend.size(), base = ctx->p_meta.size() - n;
-    std::vector<unsigned long long> snap(n * P_STATE_WORDS);
-    MTH_HIP(ctx, hipMemcpyAsync(snap.data(), ctx->p_snap.p, snap.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    MTH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    size_t good = 0;
-    uint64_t rows = 0, cpgs = 0;
-    for (; good < n; ++good) {
-        const unsigned long long *w = snap.data() + good * P_STATE_WORDS;
-        if (w[5] || w[6]) break;
-        mth_ctx::TileBatch &m = ctx->p_meta[base + good];
-        m.rows = w[1] - ctx->p_rows;
-        m.heavy0 = w[1];
-        rows += m.rows; cpgs += pend[good].n_cpgs;
-        ctx->p_rows = w[1];
-    }
-    if (cpgs) ctx->p_rows_per_cpg = std::max(ctx->p_rows_per_cpg * 0.5, (double)rows / (double)cpgs);
-    if (getenv("MTH_PAIRS_DEBUG")) fprintf(stderr, "[pairs] queued batches %zu, replayed %zu\n", n, n - good);     // tests
-    if (good == n) return MTH_OK;
-    ctx->p_meta.resize(base + good);
-    for (size_t k = good; k < n; ++k) {
-        const int rc = pairs_batch(ctx, pend[k].d, &pend[k].params, pend[k].tid, false);
-        if (rc) return rc;
-    }
-    return MTH_OK;
-}
-
-}  // namespace mth
-
 extern "C" {
 
 int mth_lpmd_pairs_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_lpmd_pairs_params_t *params) {
     if (!ctx || !batch || !params) return MTH_ERR_INVALID;
-    static const bool queue_off = getenv("MTH_PAIRS_QUEUE") && atoi(getenv("MTH_PAIRS_QUEUE")) == 0;      // A/B: one sync per batch
-    const bool queued = (batch->mem == MTH_MEM_DEVICE || batch->mem == MTH_MEM_PREPARED) && ctx->p_learned && !ctx->timing && !queue_off && ctx->p_pending.size() < (size_t)P_QUEUE_MAX;
-    mth_batch_t d;
-    ctx->tile_queue_hold = queued;
-    int rc = stage_batch(ctx, *batch, d);
-    ctx->tile_queue_hold = false;
-    if (rc) return rc;
-    if (!queued && (rc = pairs_resolve(ctx))) return rc;
-    return pairs_batch(ctx, d, params, batch->tid, queued);
+    TileParams p{};
+    p.pairs = *params;
+    return tile_rows_accumulate(ctx, ctx->pairs, *batch, p);
 }
 
 // rows sorted by ((tid,pos1),(tid,pos2)) given batches were submitted in (tid, region) order
@@ -658,40 +562,22 @@ int mth_lpmd_pairs_fetch(mth_ctx_t *ctx, uint64_t *n_rows, int32_t *tid, int32_t
     if (!ctx) return MTH_ERR_INVALID;
     int rc = sync_and_check(ctx);
     if (rc) return rc;
-    // Rows live in [0, p_rows) with gaps (the unused tails of the tile kernel's chunks); the per-tile ranges say where.
-    const uint64_t extent = ctx->p_rows;
-    const uint64_t n_tiles = ctx->p_meta.empty() ? 0 : ctx->p_meta.back().tile_end;
-    std::vector<unsigned long long> trow0(n_tiles);
-    std::vector<uint32_t> trows(n_tiles);
-    if (n_tiles) {
-        MTH_HIP(ctx, hipMemcpy(trow0.data(), ctx->p_tile_row0.p, n_tiles * 8, hipMemcpyDeviceToHost));
-        MTH_HIP(ctx, hipMemcpy(trows.data(), ctx->p_tile_rows.p, n_tiles * 4, hipMemcpyDeviceToHost));
-    }
-    // lpmd.rs:94 (pairs.sort()): the tiles in position order give sorted rows; only a run of batches of one contig that
-    // holds rows of the global path is sorted here (batches arrive tid-ordered)
+    const TileRowTable &t = ctx->pairs;
+    const uint64_t extent = t.rows;
+    // lpmd.rs:94 (pairs.sort()): the tiles in position order give sorted rows (tile_rows_walk); only a run of batches of one
+    // contig that holds rows of the global path is sorted here (batches arrive tid-ordered)
     std::vector<uint64_t> order;
     std::vector<std::pair<size_t, size_t>> unsorted_runs;
     std::vector<std::pair<size_t, int32_t>> run_tid;       // (first output row of the run, tid)
-    {
-        uint64_t batch_end = 0;
-        const size_t nb = ctx->p_meta.size();
-        for (size_t b = 0; b < nb;) {
-            size_t e = b;
-            const size_t run0 = order.size();
-            bool unsorted = false;
-            while (e < nb && ctx->p_meta[e].tid == ctx->p_meta[b].tid) {
-                const auto &mb = ctx->p_meta[e];
-                batch_end += mb.rows;
-                for (uint64_t t = e ? ctx->p_meta[e - 1].tile_end : 0; t < mb.tile_end; ++t)
-                    for (uint32_t j = 0; j < trows[t]; ++j) order.push_back(trow0[t] + j);
-                for (uint64_t i = mb.heavy0; i < batch_end; ++i) { order.push_back(i); unsorted = true; }
-                ++e;
-            }
-            if (unsorted) unsorted_runs.emplace_back(run0, order.size());
-            run_tid.emplace_back(run0, ctx->p_meta[b].tid);
-            b = e;
-        }
-    }
+    size_t run0 = 0;
+    bool unsorted = false;
+    rc = tile_rows_walk(ctx, t, [&](const TileBatch &, uint64_t i, bool heavy) { order.push_back(i); unsorted |= heavy; }, [&](size_t b) {
+        if (b + 1 < t.meta.size() && t.meta[b + 1].tid == t.meta[b].tid) return;       // the contig's run goes on
+        if (unsorted) unsorted_runs.emplace_back(run0, order.size());
+        run_tid.emplace_back(run0, t.meta[b].tid);
+        run0 = order.size(); unsorted = false;
+    });
+    if (rc) return rc;
     const uint64_t n = order.size();
     if (n_rows) *n_rows = n;
     if (n == 0 || (!tid && !pos1 && !pos2 && !lpmd && !n_concordant && !n_discordant)) return MTH_OK;

@@ -35,8 +35,6 @@ constexpr int QT_NC = 8;   // calls of a read held in registers
 constexpr int QT_QCAP = 2048;   // candidate reads per fill of the contributor queue
 constexpr int QT_OCC = 6;  // waves per SIMD (LDS: 23 KiB per workgroup = 6 per CU)
 constexpr int QT_S = 512, QT_B = 256, QT_U = 2, QT_CHUNK = 512, QT_GRID = 8192;   // (the tile width is a template parameter: 8192 / 16384 / 32768, chosen per batch)
-constexpr int Q_STATE_WORDS = 8;
-constexpr int Q_QUEUE_MAX = 4096;       // queued batches between two resolves (their snapshots: 256 KB)
 
 __device__ __forceinline__ unsigned long long qhash(unsigned long long x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
@@ -392,39 +390,12 @@ __global__ __launch_bounds__(QT_B, QT_OCC) void k_quartet_tile(const QTileArgs a
     }
 }
 
-// (re)start of a batch: back to the row count before it (also the start of a fused batch, mth_multi.hip)
-__global__ void k_quartet_rewind(unsigned long long *qs, unsigned long long rows_before) { qs[1] = rows_before; qs[5] = 0; qs[6] = 0; }
-
-// a queued batch's state words as its tile kernel left them ([1] rows so far, [5] tiles for the global path and [6] tiles that did not
-// fit, both since the run of queued batches began): read back by quartet_resolve, not by the call that queued the batch
-__global__ void k_quartet_snap(const unsigned long long *__restrict__ qs, unsigned long long *__restrict__ snap) {
-    if (threadIdx.x < Q_STATE_WORDS) snap[threadIdx.x] = qs[threadIdx.x];
-}
-
-}  // namespace mth
-
-using namespace mth;
-
-// One batch.  queued = false: the call ends knowing the batch's rows (one host sync; redone with the exact size if the rows did not fit,
-// the global path for tiles the LDS table could not hold).  queued = true (device-resident batches after the first of a job): tile
-// kernel and a snapshot of the state words only -- whether everything fitted is looked at by quartet_resolve, at the next call that
-// needs the rows, and anything else than "all fitted, no tile for the global path" replays the batches from the first such one on
-// through the synchronous form (their arrays are still there: include/metheor_hip.h, device-resident batches stay untouched until
-// the next synchronising call).
-static int quartet_batch(mth_ctx *ctx, const mth_batch_t &d, const mth_quartet_params_t *params, int32_t batch_tid, bool queued) {
-    int rc = MTH_OK;
-    hipStream_t s = ctx->stream;
-    if (!ctx->q_state.p) {
-        MTH_HIP(ctx, ctx->q_state.reserve(Q_STATE_WORDS * sizeof(unsigned long long), s));
-        MTH_HIP(ctx, hipMemsetAsync(ctx->q_state.p, 0, Q_STATE_WORDS * sizeof(unsigned long long), s));
-    }
-    // [0] updates (counting pass of the global path) [1] total rows [2] first row of the global path's rows
-    // [3] its overflow flag [5] tiles left to the global path [6] tiles whose rows did not fit the output
-    unsigned long long *qs = ctx->q_state.as<unsigned long long>();
+// ---- what ME / PM brings to the tile-row driver (mth_tile_rows.hip) -----------------------------------------------
+// Tile width: wide tiles pay the per-tile costs (index look-up, LDS clear, barriers, halo reads) less often, but the
+// table holds QT_S quartets and a 16-bit bin 65535 candidate reads.  About one quartet starts per CpG site; sites per
+// bp ~ calls per read / read length (max_span stands in for the length).  Tiles that overflow anyway take the global path.
+static int quartet_tile_shift(const mth_batch_t &d, const TileParams &) {
     const int64_t region_len = (int64_t)d.region_end - d.region_beg;
-    // Tile width: wide tiles pay the per-tile costs (index look-up, LDS clear, barriers, halo reads) less often, but the
-    // table holds QT_S quartets and a 16-bit bin 65535 candidate reads.  About one quartet starts per CpG site; sites per
-    // bp ~ calls per read / read length (max_span stands in for the length).  Tiles that overflow anyway take the global path.
     int tile_shift = 13;
     if (d.n_reads && region_len > 0) {
         const double sites_per_bp = (double)d.n_cpgs / (double)d.n_reads / (double)std::max(d.max_span, 1);
@@ -439,246 +410,165 @@ static int quartet_batch(mth_ctx *ctx, const mth_batch_t &d, const mth_quartet_p
             ++tile_shift;
     }
     if (const char *e = getenv("MTH_QUARTET_TILE_SHIFT")) tile_shift = std::min(16, std::max(13, atoi(e)));   // tests / tuning
-    const int QT_W = 1 << tile_shift;
-    const uint32_t ntiles = (d.n_reads && region_len > 0) ? (uint32_t)((region_len + QT_W - 1) / QT_W) : 0u;
-    const uint64_t tiles_before = ctx->q_meta.empty() ? 0 : ctx->q_meta.back().tile_end;
-    // queued: the exact count is on the device only; q_rows_est bounds it from above (every queued batch so far within its estimate --
-    // if one was not, the resolve replays from there and none of this batch's rows survive anyway)
-    const uint64_t rows_before = queued && !ctx->q_pending.empty() ? ctx->q_rows_est : ctx->q_rows;
-    mth_ctx::TileBatch meta{batch_tid, 0, rows_before, tiles_before + ntiles};
-    if (!ntiles && queued && !ctx->q_pending.empty()) queued = false, rc = quartet_resolve(ctx);       // (rare: an empty batch inside a run)
-    if (rc) return rc;
-    if (!ntiles) { meta.heavy0 = ctx->q_rows; ctx->q_meta.push_back(meta); return MTH_OK; }
-    auto grow_rows = [&](uint64_t cap, uint64_t used) -> hipError_t {      // keeps the rows of earlier batches
-        hipError_t e;
-        if ((e = ctx->q_pos.reserve(cap * 16, s, true, used * 16)) != hipSuccess) return e;
-        if ((e = ctx->q_cnt.reserve(cap * 64, s, true, used * 64)) != hipSuccess) return e;
-        if ((e = ctx->q_me.reserve(cap * 4, s, true, used * 4)) != hipSuccess) return e;
-        if ((e = ctx->q_pm.reserve(cap * 4, s, true, used * 4)) != hipSuccess) return e;
-        if ((e = ctx->q_depth.reserve(cap * 4, s, true, used * 4)) != hipSuccess) return e;
-        ctx->q_cap = cap;
-        return hipSuccess;
-    };
-    int32_t idx_base = 0;
-    uint32_t nt = 0;
-    rc = build_read_index(ctx, d, QT_W, idx_base, nt);
-    if (rc) return rc;
-    MTH_HIP(ctx, ctx->q_tflag.reserve((size_t)ntiles * 4, s));
-    MTH_HIP(ctx, ctx->q_tile_row0.reserve((tiles_before + ntiles) * 8, s, true, tiles_before * 8));
-    MTH_HIP(ctx, ctx->q_tile_rows.reserve((tiles_before + ntiles) * 4, s, true, tiles_before * 4));
-    // output size: rows per CpG call of the batches so far (first batch: a guess); the kernel reports the exact need --
-    // there is no counting pre-pass
-    uint64_t want = rows_before + (uint64_t)((double)d.n_cpgs * ctx->q_rows_per_cpg * 1.25) + 4096;
-    if (const char *e = getenv("MTH_QUARTET_ROWS_MIN")) want = rows_before + strtoull(e, nullptr, 10);   // tests: force the redo
-    unsigned long long *st = ctx->h_words;     // pinned: the read-back does not go through a staging copy
-    for (int attempt = 0;; ++attempt) {
-        if (want > ctx->q_cap) MTH_HIP(ctx, grow_rows(want + (queued ? want / 4 : 0), std::min<uint64_t>(rows_before, ctx->q_cap)));
-        // a run of queued batches continues from the device's own row count; its first batch (and every synchronous one) starts from
-        // the host's, which is exact then
-        if (!queued || ctx->q_pending.empty()) hipLaunchKernelGGL(k_quartet_rewind, dim3(1), dim3(1), 0, s, qs, (unsigned long long)rows_before);
-        QTileArgs a;
-        a.read_start = d.read_start; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
-        a.idx = idx_ptr(ctx);
-        a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span;
-        a.n_reads = d.n_reads; a.ntiles = ntiles; a.n_cpgs = (uint32_t)d.n_cpgs; a.min_qual = params->min_qual;
-        a.force_heavy = getenv("MTH_QUARTET_FORCE_GLOBAL") ? 1 : 0;
-        // a queued batch must stay within its ESTIMATE, not just within the buffer: the next queued batch takes the estimate as the
-        // rows in use and keeps only that many when it grows the buffer (rows between the estimate and the device's count
-        // were lost without a flag); beyond the estimate the batch is unfit and quartet_resolve replays it
-        a.row_total = qs + 1; a.row_cap = queued ? std::min<uint64_t>(ctx->q_cap, want) : ctx->q_cap; a.unfit = qs + 6; a.n_heavy = qs + 5;
-        a.tile_flag = ctx->q_tflag.as<uint32_t>();
-        a.tile_row0 = ctx->q_tile_row0.as<unsigned long long>() + tiles_before;
-        a.tile_rows = ctx->q_tile_rows.as<uint32_t>() + tiles_before;
-        a.out_pos = ctx->q_pos.as<int32_t>(); a.out_cnt = ctx->q_cnt.as<uint32_t>(); a.out_me = ctx->q_me.as<float>();
-        a.out_pm = ctx->q_pm.as<float>(); a.out_depth = ctx->q_depth.as<uint32_t>(); a.st = ctx->d_state;
-        {
-            LaunchTimer lt(ctx, K_QTILE);
-            if (tile_shift == 13) hipLaunchKernelGGL(k_quartet_tile<8192>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
-            else if (tile_shift == 14) hipLaunchKernelGGL(k_quartet_tile<16384>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
-            else if (tile_shift == 15) hipLaunchKernelGGL(k_quartet_tile<32768>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
-            else hipLaunchKernelGGL(k_quartet_tile<65536>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
-        }
-        if (queued) {
-            const size_t k = ctx->q_pending.size();
-            MTH_HIP(ctx, ctx->q_snap.reserve((size_t)Q_QUEUE_MAX * Q_STATE_WORDS * sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(k_quartet_snap, dim3(1), dim3(64), 0, s, (const unsigned long long *)qs, ctx->q_snap.as<unsigned long long>() + k * Q_STATE_WORDS);
-            MTH_HIP(ctx, hipGetLastError());
-            ctx->q_pending.push_back(mth_ctx::QueuedBatch{d, *params, batch_tid, d.n_cpgs});
-            ctx->q_rows_est = want;
-            ctx->q_meta.push_back(meta);                   // rows / heavy0: quartet_resolve
-            return MTH_OK;
-        }
-        MTH_HIP(ctx, hipMemcpyAsync(st, qs, Q_STATE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        MTH_HIP(ctx, hipStreamSynchronize(s));            // one sync per batch: rows, flagged tiles, fit
-        if (!st[6]) break;
-        if (attempt) return fail(ctx, MTH_ERR_STATE, "quartets: rows did not fit an exactly sized output");
-        want = st[1];                                     // every tile claimed its range: this is the exact size
+    return tile_shift;
+}
+
+static hipError_t quartet_grow_rows(mth_ctx *ctx, uint64_t cap, uint64_t used) {
+    hipStream_t s = ctx->stream;
+    hipError_t e;
+    if ((e = ctx->q_pos.reserve(cap * 16, s, true, used * 16)) != hipSuccess) return e;
+    if ((e = ctx->q_cnt.reserve(cap * 64, s, true, used * 64)) != hipSuccess) return e;
+    if ((e = ctx->q_me.reserve(cap * 4, s, true, used * 4)) != hipSuccess) return e;
+    if ((e = ctx->q_pm.reserve(cap * 4, s, true, used * 4)) != hipSuccess) return e;
+    return ctx->q_depth.reserve(cap * 4, s, true, used * 4);
+}
+
+static void quartet_launch_tiles(mth_ctx *ctx, const mth_batch_t &d, const TileParams &p, int tile_shift, uint32_t ntiles, int32_t idx_base,
+                                 uint64_t tiles_before, uint64_t row_cap) {
+    const TileRowTable &t = ctx->quartets;
+    hipStream_t s = ctx->stream;
+    unsigned long long *qs = t.words();
+    QTileArgs a;
+    a.read_start = d.read_start; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
+    a.idx = idx_ptr(ctx);
+    a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span;
+    a.n_reads = d.n_reads; a.ntiles = ntiles; a.n_cpgs = (uint32_t)d.n_cpgs; a.min_qual = p.quartet.min_qual;
+    a.force_heavy = getenv("MTH_QUARTET_FORCE_GLOBAL") ? 1 : 0;
+    a.row_total = qs + 1; a.row_cap = row_cap; a.unfit = qs + 6; a.n_heavy = qs + 5;
+    a.tile_flag = t.tflag.as<uint32_t>();
+    a.tile_row0 = t.tile_row0.as<unsigned long long>() + tiles_before;
+    a.tile_rows = t.tile_rows.as<uint32_t>() + tiles_before;
+    a.out_pos = ctx->q_pos.as<int32_t>(); a.out_cnt = ctx->q_cnt.as<uint32_t>(); a.out_me = ctx->q_me.as<float>();
+    a.out_pm = ctx->q_pm.as<float>(); a.out_depth = ctx->q_depth.as<uint32_t>(); a.st = ctx->d_state;
+    LaunchTimer lt(ctx, K_QTILE);
+    if (tile_shift == 13) hipLaunchKernelGGL(k_quartet_tile<8192>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
+    else if (tile_shift == 14) hipLaunchKernelGGL(k_quartet_tile<16384>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
+    else if (tile_shift == 15) hipLaunchKernelGGL(k_quartet_tile<32768>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
+    else hipLaunchKernelGGL(k_quartet_tile<65536>, dim3(std::min<uint32_t>(ntiles, QT_GRID)), dim3(QT_B), 0, s, a);
+}
+
+// The tiles the LDS table could not hold: the global table, for their quartets only.  Its size: `bound` counts
+// quartet INSTANCES of the whole batch; bound / 2 slots to start with, redone 4x larger if an insert ran out of
+// probes -- at 2 x bound slots that cannot happen.
+static int quartet_global_path(mth_ctx *ctx, const mth_batch_t &d, const TileParams &p, int tile_shift, uint64_t &total) {
+    TileRowTable &t = ctx->quartets;
+    const mth_quartet_params_t *params = &p.quartet;
+    hipStream_t s = ctx->stream;
+    unsigned long long *qs = t.words();
+    MTH_HIP(ctx, hipMemsetAsync(qs, 0, sizeof(unsigned long long), s));
+    {
+        LaunchTimer lt(ctx, K_QBOUND);
+        hipLaunchKernelGGL(k_quartet_bound, dim3(1024), dim3(256), 0, s, d.cpg_off, d.read_mapq, d.n_reads,
+                           params->min_qual, qs);
     }
-    uint64_t total = st[1];
-    meta.heavy0 = total;
-    if (st[5]) {
-        // The tiles the LDS table could not hold: the global table, for their quartets only.  Its size: `bound` counts
-        // quartet INSTANCES of the whole batch; bound / 2 slots to start with, redone 4x larger if an insert ran out of
-        // probes -- at 2 x bound slots that cannot happen.
-        MTH_HIP(ctx, hipMemsetAsync(qs, 0, sizeof(unsigned long long), s));
+    unsigned long long bound = 0;
+    MTH_HIP(ctx, hipMemcpyAsync(&bound, qs, sizeof bound, hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipStreamSynchronize(s));
+    unsigned long long n_slots = 1024;
+    while (n_slots < bound / 2) n_slots <<= 1;
+    unsigned long long wide_cap = std::max<unsigned long long>(ctx->q_wpat.cap / 4, 65536), wide_n = 0;
+    if (const char *e = getenv("MTH_QUARTET_SLOTS_MIN")) { const unsigned long long k = strtoull(e, nullptr, 10); if (k >= 16) { n_slots = 16; while (n_slots < k) n_slots <<= 1; } }   // tests: force the retry
+    for (;;) {
+        MTH_HIP(ctx, ctx->q_keys.reserve(n_slots * 8, s));
+        MTH_HIP(ctx, ctx->q_hist.reserve(n_slots * 64, s));
+        MTH_HIP(ctx, hipMemsetAsync(ctx->q_keys.p, 0xFF, n_slots * 8, s));
+        MTH_HIP(ctx, hipMemsetAsync(ctx->q_hist.p, 0, n_slots * 64, s));
+        MTH_HIP(ctx, hipMemsetAsync(qs + 3, 0, sizeof(unsigned long long), s));
+        MTH_HIP(ctx, hipMemsetAsync(qs + 7, 0, sizeof(unsigned long long), s));
+        MTH_HIP(ctx, ctx->q_wpos.reserve(wide_cap * 16, s));
+        MTH_HIP(ctx, ctx->q_wpat.reserve(wide_cap * 4, s));
         {
-            LaunchTimer lt(ctx, K_QBOUND);
-            hipLaunchKernelGGL(k_quartet_bound, dim3(1024), dim3(256), 0, s, d.cpg_off, d.read_mapq, d.n_reads,
-                               params->min_qual, qs);
+            LaunchTimer lt(ctx, K_QINSERT);
+            hipLaunchKernelGGL(k_quartet_insert, dim3((d.n_reads + 255) / 256), dim3(256), 0, s, d.cpg_off, d.cpg_pos,
+                               d.read_mapq, d.n_reads, params->min_qual, d.region_beg, d.region_end,
+                               ctx->q_keys.as<unsigned long long>(), ctx->q_hist.as<uint32_t>(), n_slots - 1, qs + 3,
+                               ctx->d_state, (const uint32_t *)t.tflag.as<uint32_t>(), tile_shift,
+                               ctx->q_wpos.as<uint4>(), ctx->q_wpat.as<uint32_t>(), wide_cap, qs + 7);
         }
-        unsigned long long bound = 0;
-        MTH_HIP(ctx, hipMemcpyAsync(&bound, qs, sizeof bound, hipMemcpyDeviceToHost, s));
+        unsigned long long ovf = 0;
+        MTH_HIP(ctx, hipMemcpyAsync(&ovf, qs + 3, sizeof ovf, hipMemcpyDeviceToHost, s));
+        MTH_HIP(ctx, hipMemcpyAsync(&wide_n, qs + 7, sizeof wide_n, hipMemcpyDeviceToHost, s));
         MTH_HIP(ctx, hipStreamSynchronize(s));
-        unsigned long long n_slots = 1024;
-        while (n_slots < bound / 2) n_slots <<= 1;
-        unsigned long long wide_cap = std::max<unsigned long long>(ctx->q_wpat.cap / 4, 65536), wide_n = 0;
-        if (const char *e = getenv("MTH_QUARTET_SLOTS_MIN")) { const unsigned long long k = strtoull(e, nullptr, 10); if (k >= 16) { n_slots = 16; while (n_slots < k) n_slots <<= 1; } }   // tests: force the retry
+        if (wide_n > wide_cap) { wide_cap = wide_n; continue; }        // the wide list was too short: same table, again
+        if (!ovf) break;
+        n_slots <<= 2;
+    }
+    if (total + bound > t.cap) MTH_HIP(ctx, tile_rows_grow(ctx, t, total + bound, total));     // distinct quartets <= instances
+    const uint32_t nblk = (uint32_t)((n_slots + 256 * QE_PER - 1) / (256 * QE_PER));
+    MTH_HIP(ctx, ctx->q_blk.reserve((size_t)nblk * 4, s));
+    MTH_HIP(ctx, ctx->q_batch_rows.reserve(4, s));
+    {
+        LaunchTimer lt(ctx, K_QEMIT);
+        hipLaunchKernelGGL(k_quartet_blockcount, dim3(nblk), dim3(256), 0, s, ctx->q_keys.as<unsigned long long>(),
+                           n_slots, ctx->q_blk.as<uint32_t>());
+        hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, ctx->q_blk.as<uint32_t>(), nblk, qs + 1, qs + 2,
+                           ctx->q_batch_rows.as<uint32_t>(), 0u);
+        hipLaunchKernelGGL(k_quartet_emit, dim3(nblk), dim3(256), 0, s, ctx->q_keys.as<unsigned long long>(),
+                           (const unsigned long long *)nullptr,
+                           ctx->q_hist.as<uint32_t>(), n_slots, ctx->q_blk.as<uint32_t>(), qs + 2,
+                           ctx->q_pos.as<int32_t>(), ctx->q_cnt.as<uint32_t>(), ctx->q_me.as<float>(),
+                           ctx->q_pm.as<float>(), ctx->q_depth.as<uint32_t>());
+    }
+    unsigned long long t2 = 0;
+    MTH_HIP(ctx, hipMemcpyAsync(&t2, qs + 1, sizeof t2, hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipStreamSynchronize(s));
+    total = t2;
+    if (wide_n) {
+        // the wide instances under their 128-bit keys: same emit, rows appended after the packed-key rows of the batch
+        unsigned long long w_slots = 1024;
+        while (w_slots < 2 * wide_n) w_slots <<= 1;
         for (;;) {
-            MTH_HIP(ctx, ctx->q_keys.reserve(n_slots * 8, s));
-            MTH_HIP(ctx, ctx->q_hist.reserve(n_slots * 64, s));
-            MTH_HIP(ctx, hipMemsetAsync(ctx->q_keys.p, 0xFF, n_slots * 8, s));
-            MTH_HIP(ctx, hipMemsetAsync(ctx->q_hist.p, 0, n_slots * 64, s));
+            MTH_HIP(ctx, ctx->q_wk0.reserve(w_slots * 8, s));
+            MTH_HIP(ctx, ctx->q_wk1.reserve(w_slots * 8, s));
+            MTH_HIP(ctx, ctx->q_hist.reserve(w_slots * 64, s));
+            MTH_HIP(ctx, hipMemsetAsync(ctx->q_wk0.p, 0xFF, w_slots * 8, s));
+            MTH_HIP(ctx, hipMemsetAsync(ctx->q_wk1.p, 0xFF, w_slots * 8, s));
+            MTH_HIP(ctx, hipMemsetAsync(ctx->q_hist.p, 0, w_slots * 64, s));
             MTH_HIP(ctx, hipMemsetAsync(qs + 3, 0, sizeof(unsigned long long), s));
-            MTH_HIP(ctx, hipMemsetAsync(qs + 7, 0, sizeof(unsigned long long), s));
-            MTH_HIP(ctx, ctx->q_wpos.reserve(wide_cap * 16, s));
-            MTH_HIP(ctx, ctx->q_wpat.reserve(wide_cap * 4, s));
-            {
-                LaunchTimer lt(ctx, K_QINSERT);
-                hipLaunchKernelGGL(k_quartet_insert, dim3((d.n_reads + 255) / 256), dim3(256), 0, s, d.cpg_off, d.cpg_pos,
-                                   d.read_mapq, d.n_reads, params->min_qual, d.region_beg, d.region_end,
-                                   ctx->q_keys.as<unsigned long long>(), ctx->q_hist.as<uint32_t>(), n_slots - 1, qs + 3,
-                                   ctx->d_state, (const uint32_t *)ctx->q_tflag.as<uint32_t>(), tile_shift,
-                                   ctx->q_wpos.as<uint4>(), ctx->q_wpat.as<uint32_t>(), wide_cap, qs + 7);
-            }
+            hipLaunchKernelGGL(k_quartet_wide_insert, dim3((uint32_t)((wide_n + 255) / 256)), dim3(256), 0, s, ctx->q_wpos.as<uint4>(),
+                               ctx->q_wpat.as<uint32_t>(), wide_n, ctx->q_wk0.as<unsigned long long>(), ctx->q_wk1.as<unsigned long long>(),
+                               ctx->q_hist.as<uint32_t>(), w_slots - 1, qs + 3);
             unsigned long long ovf = 0;
             MTH_HIP(ctx, hipMemcpyAsync(&ovf, qs + 3, sizeof ovf, hipMemcpyDeviceToHost, s));
-            MTH_HIP(ctx, hipMemcpyAsync(&wide_n, qs + 7, sizeof wide_n, hipMemcpyDeviceToHost, s));
             MTH_HIP(ctx, hipStreamSynchronize(s));
-            if (wide_n > wide_cap) { wide_cap = wide_n; continue; }        // the wide list was too short: same table, again
             if (!ovf) break;
-            n_slots <<= 2;
+            w_slots <<= 2;
         }
-        if (total + bound > ctx->q_cap) MTH_HIP(ctx, grow_rows(total + bound, total));     // distinct quartets <= instances
-        const uint32_t nblk = (uint32_t)((n_slots + 256 * QE_PER - 1) / (256 * QE_PER));
-        MTH_HIP(ctx, ctx->q_blk.reserve((size_t)nblk * 4, s));
-        MTH_HIP(ctx, ctx->q_batch_rows.reserve(4, s));
-        {
-            LaunchTimer lt(ctx, K_QEMIT);
-            hipLaunchKernelGGL(k_quartet_blockcount, dim3(nblk), dim3(256), 0, s, ctx->q_keys.as<unsigned long long>(),
-                               n_slots, ctx->q_blk.as<uint32_t>());
-            hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, ctx->q_blk.as<uint32_t>(), nblk, qs + 1, qs + 2,
-                               ctx->q_batch_rows.as<uint32_t>(), 0u);
-            hipLaunchKernelGGL(k_quartet_emit, dim3(nblk), dim3(256), 0, s, ctx->q_keys.as<unsigned long long>(),
-                               (const unsigned long long *)nullptr,
-                               ctx->q_hist.as<uint32_t>(), n_slots, ctx->q_blk.as<uint32_t>(), qs + 2,
-                               ctx->q_pos.as<int32_t>(), ctx->q_cnt.as<uint32_t>(), ctx->q_me.as<float>(),
-                               ctx->q_pm.as<float>(), ctx->q_depth.as<uint32_t>());
-        }
-        unsigned long long t2 = 0;
+        if (total + wide_n > t.cap) MTH_HIP(ctx, tile_rows_grow(ctx, t, total + wide_n, total));
+        const uint32_t wblk = (uint32_t)((w_slots + 256 * QE_PER - 1) / (256 * QE_PER));
+        MTH_HIP(ctx, ctx->q_blk.reserve((size_t)wblk * 4, s));
+        hipLaunchKernelGGL(k_quartet_blockcount, dim3(wblk), dim3(256), 0, s, ctx->q_wk0.as<unsigned long long>(), w_slots, ctx->q_blk.as<uint32_t>());
+        hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, ctx->q_blk.as<uint32_t>(), wblk, qs + 1, qs + 2,
+                           ctx->q_batch_rows.as<uint32_t>(), 0u);
+        hipLaunchKernelGGL(k_quartet_emit, dim3(wblk), dim3(256), 0, s, ctx->q_wk0.as<unsigned long long>(),
+                           (const unsigned long long *)ctx->q_wk1.as<unsigned long long>(),
+                           ctx->q_hist.as<uint32_t>(), w_slots, ctx->q_blk.as<uint32_t>(), qs + 2,
+                           ctx->q_pos.as<int32_t>(), ctx->q_cnt.as<uint32_t>(), ctx->q_me.as<float>(),
+                           ctx->q_pm.as<float>(), ctx->q_depth.as<uint32_t>());
         MTH_HIP(ctx, hipMemcpyAsync(&t2, qs + 1, sizeof t2, hipMemcpyDeviceToHost, s));
         MTH_HIP(ctx, hipStreamSynchronize(s));
         total = t2;
-        if (wide_n) {
-            // the wide instances under their 128-bit keys: same emit, rows appended after the packed-key rows of the batch
-            unsigned long long w_slots = 1024;
-            while (w_slots < 2 * wide_n) w_slots <<= 1;
-            for (;;) {
-                MTH_HIP(ctx, ctx->q_wk0.reserve(w_slots * 8, s));
-                MTH_HIP(ctx, ctx->q_wk1.reserve(w_slots * 8, s));
-                MTH_HIP(ctx, ctx->q_hist.reserve(w_slots * 64, s));
-                MTH_HIP(ctx, hipMemsetAsync(ctx->q_wk0.p, 0xFF, w_slots * 8, s));
-                MTH_HIP(ctx, hipMemsetAsync(ctx->q_wk1.p, 0xFF, w_slots * 8, s));
-                MTH_HIP(ctx, hipMemsetAsync(ctx->q_hist.p, 0, w_slots * 64, s));
-                MTH_HIP(ctx, hipMemsetAsync(qs + 3, 0, sizeof(unsigned long long), s));
-                hipLaunchKernelGGL(k_quartet_wide_insert, dim3((uint32_t)((wide_n + 255) / 256)), dim3(256), 0, s, ctx->q_wpos.as<uint4>(),
-                                   ctx->q_wpat.as<uint32_t>(), wide_n, ctx->q_wk0.as<unsigned long long>(), ctx->q_wk1.as<unsigned long long>(),
-                                   ctx->q_hist.as<uint32_t>(), w_slots - 1, qs + 3);
-                unsigned long long ovf = 0;
-                MTH_HIP(ctx, hipMemcpyAsync(&ovf, qs + 3, sizeof ovf, hipMemcpyDeviceToHost, s));
-                MTH_HIP(ctx, hipStreamSynchronize(s));
-                if (!ovf) break;
-                w_slots <<= 2;
-            }
-            if (total + wide_n > ctx->q_cap) MTH_HIP(ctx, grow_rows(total + wide_n, total));
-            const uint32_t wblk = (uint32_t)((w_slots + 256 * QE_PER - 1) / (256 * QE_PER));
-            MTH_HIP(ctx, ctx->q_blk.reserve((size_t)wblk * 4, s));
-            hipLaunchKernelGGL(k_quartet_blockcount, dim3(wblk), dim3(256), 0, s, ctx->q_wk0.as<unsigned long long>(), w_slots, ctx->q_blk.as<uint32_t>());
-            hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, ctx->q_blk.as<uint32_t>(), wblk, qs + 1, qs + 2,
-                               ctx->q_batch_rows.as<uint32_t>(), 0u);
-            hipLaunchKernelGGL(k_quartet_emit, dim3(wblk), dim3(256), 0, s, ctx->q_wk0.as<unsigned long long>(),
-                               (const unsigned long long *)ctx->q_wk1.as<unsigned long long>(),
-                               ctx->q_hist.as<uint32_t>(), w_slots, ctx->q_blk.as<uint32_t>(), qs + 2,
-                               ctx->q_pos.as<int32_t>(), ctx->q_cnt.as<uint32_t>(), ctx->q_me.as<float>(),
-                               ctx->q_pm.as<float>(), ctx->q_depth.as<uint32_t>());
-            MTH_HIP(ctx, hipMemcpyAsync(&t2, qs + 1, sizeof t2, hipMemcpyDeviceToHost, s));
-            MTH_HIP(ctx, hipStreamSynchronize(s));
-            total = t2;
-        }
     }
-    MTH_HIP(ctx, hipGetLastError());
-    meta.rows = total - rows_before;
-    ctx->q_rows = total;
-    if (d.n_cpgs) { ctx->q_rows_per_cpg = std::max(ctx->q_rows_per_cpg * 0.5, (double)meta.rows / (double)d.n_cpgs); ctx->q_learned = true; }
-    ctx->q_meta.push_back(meta);
     return MTH_OK;
 }
 
-namespace mth {
-
-// The queued batches' rows: one read-back of their snapshots.  All fitted and no tile was left to the global path: the metas get
-// their row counts.  Otherwise the batches from the first one that says so are replayed synchronously, in order.
-int quartet_resolve(mth_ctx *ctx) {
-    if (ctx->q_pending.empty()) return MTH_OK;
-    // (a replay below rebuilds its batch's read index in the context's own buffer: whatever prepared batch the latest entry point
-    // worked on is not this one's)
-    ctx->cur_prep = nullptr; ctx->cur_idx = nullptr;
-    MTH_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<mth_ctx::QueuedBatch> pend;
-    pend.swap(ctx->q_pending);
-    const size_t n = pend.size(), base = ctx->q_meta.size() - n;
-    std::vector<unsigned long long> snap(n * Q_STATE_WORDS);
-    MTH_HIP(ctx, hipMemcpyAsync(snap.data(), ctx->q_snap.p, snap.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    MTH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    size_t good = 0;
-    uint64_t rows = 0, cpgs = 0;
-    for (; good < n; ++good) {
-        const unsigned long long *w = snap.data() + good * Q_STATE_WORDS;
-        if (w[5] || w[6]) break;
-        mth_ctx::TileBatch &m = ctx->q_meta[base + good];
-        m.rows = w[1] - ctx->q_rows;
-        m.heavy0 = w[1];
-        rows += m.rows; cpgs += pend[good].n_cpgs;
-        ctx->q_rows = w[1];
-    }
-    if (cpgs) ctx->q_rows_per_cpg = std::max(ctx->q_rows_per_cpg * 0.5, (double)rows / (double)cpgs);
-    if (getenv("MTH_QUARTET_DEBUG")) fprintf(stderr, "[quartet] queued batches %zu, replayed %zu\n", n, n - good);     // tests
-    if (good == n) return MTH_OK;
-    ctx->q_meta.resize(base + good);
-    for (size_t k = good; k < n; ++k) {
-        const int rc = quartet_batch(ctx, pend[k].d, &pend[k].params, pend[k].tid, false);
-        if (rc) return rc;
-    }
-    return MTH_OK;
+const TileMeasure *quartet_measure() {
+    static const TileMeasure m = {quartet_tile_shift, quartet_grow_rows, quartet_launch_tiles, quartet_global_path};
+    return &m;
 }
 
 }  // namespace mth
+
+using namespace mth;
 
 extern "C" {
 
 int mth_quartet_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_quartet_params_t *params) {
     if (!ctx || !batch || !params) return MTH_ERR_INVALID;
     ctx->q_epoch += 1;
-    // Queued (no host sync in the call): a device-resident batch once a batch of this context has taught the output sizing, unless the
-    // launches are being timed.  MTH_QUARTET_QUEUE=0 switches it off (A/B).  Every other entry point settles the queue (mth::enter).
-    static const bool queue_off = getenv("MTH_QUARTET_QUEUE") && atoi(getenv("MTH_QUARTET_QUEUE")) == 0;
-    const bool queued = (batch->mem == MTH_MEM_DEVICE || batch->mem == MTH_MEM_PREPARED) && ctx->q_learned && !ctx->timing && !queue_off && ctx->q_pending.size() < (size_t)Q_QUEUE_MAX;
-    mth_batch_t d;
-    ctx->tile_queue_hold = queued;
-    int rc = stage_batch(ctx, *batch, d);
-    ctx->tile_queue_hold = false;
-    if (rc) return rc;
-    if (!queued && (rc = quartet_resolve(ctx))) return rc;
-    return quartet_batch(ctx, d, params, batch->tid, queued);
+    TileParams p{};
+    p.quartet = *params;
+    return tile_rows_accumulate(ctx, ctx->quartets, *batch, p);
 }
 
 // rows of all batches with depth >= min_depth (me.rs:82 / pm.rs:77); any pointer may be NULL.
@@ -688,10 +578,10 @@ int mth_quartet_fetch(mth_ctx_t *ctx, uint32_t min_depth, uint64_t *n_rows, int3
     if (!ctx) return MTH_ERR_INVALID;
     int rc = sync_and_check(ctx);          // resolves the queued batches first
     if (rc) return rc;
-    // Rows live in [0, q_rows) with gaps (the unused tails of the tile kernel's chunks).  Row order: per batch, sorted by
-    // (p1..p4): the tiles in position order give that for free (each tile's rows are sorted in LDS); a batch with rows from
-    // the global path is sorted here.  The reference's order is HashMap-random.
-    const uint64_t total = ctx->q_rows;
+    // Row order: per batch, sorted by (p1..p4): the tiles in position order give that for free (tile_rows_walk); a batch with
+    // rows from the global path is sorted here.  The reference's order is HashMap-random.
+    const TileRowTable &t = ctx->quartets;
+    const uint64_t total = t.rows;
     std::vector<int32_t> hp;                // pos1..pos4 of every device row
     std::vector<uint64_t> &order = ctx->q_order;            // device row of every output row that passes the depth filter
     std::vector<int32_t> &order_tid = ctx->q_order_tid;
@@ -699,41 +589,29 @@ int mth_quartet_fetch(mth_ctx_t *ctx, uint32_t min_depth, uint64_t *n_rows, int3
     if (!cached) {
         std::vector<uint32_t> depth(total);
         if (total) MTH_HIP(ctx, hipMemcpy(depth.data(), ctx->q_depth.p, total * 4, hipMemcpyDeviceToHost));
-        const uint64_t n_tiles = ctx->q_meta.empty() ? 0 : ctx->q_meta.back().tile_end;
-        std::vector<unsigned long long> trow0(n_tiles);
-        std::vector<uint32_t> trows(n_tiles);
-        if (n_tiles) {
-            MTH_HIP(ctx, hipMemcpy(trow0.data(), ctx->q_tile_row0.p, n_tiles * 8, hipMemcpyDeviceToHost));
-            MTH_HIP(ctx, hipMemcpy(trows.data(), ctx->q_tile_rows.p, n_tiles * 4, hipMemcpyDeviceToHost));
-        }
         order.clear(); order_tid.clear();
         bool any_heavy = false;
         {
             uint64_t batch_end = 0;
-            for (const auto &mb : ctx->q_meta) { batch_end += mb.rows; any_heavy |= mb.heavy0 < batch_end; }
+            for (const auto &mb : t.meta) { batch_end += mb.rows; any_heavy |= mb.heavy0 < batch_end; }
         }
         if (total && (pos4 || any_heavy)) {
             hp.resize(total * 4);
             MTH_HIP(ctx, hipMemcpy(hp.data(), ctx->q_pos.p, total * 16, hipMemcpyDeviceToHost));
         }
-        {
-            uint64_t batch_end = 0;
-            for (size_t b = 0; b < ctx->q_meta.size(); ++b) {
-                const auto &mb = ctx->q_meta[b];
-                batch_end += mb.rows;
-                const size_t first = order.size();
-                auto put = [&](uint64_t i) { if (depth[i] >= min_depth) { order.push_back(i); order_tid.push_back(mb.tid); } };
-                for (uint64_t t = b ? ctx->q_meta[b - 1].tile_end : 0; t < mb.tile_end; ++t)
-                    for (uint32_t j = 0; j < trows[t]; ++j) put(trow0[t] + j);
-                const size_t sorted_end = order.size();
-                for (uint64_t i = mb.heavy0; i < batch_end; ++i) put(i);
-                if (order.size() > sorted_end)      // rows of the global path came in table order: put the batch in (pos1..pos4) order
-                    std::sort(order.begin() + (ptrdiff_t)first, order.end(), [&](uint64_t x, uint64_t y) {
-                        return std::lexicographical_compare(hp.begin() + (ptrdiff_t)(x * 4), hp.begin() + (ptrdiff_t)(x * 4 + 4),
-                                                            hp.begin() + (ptrdiff_t)(y * 4), hp.begin() + (ptrdiff_t)(y * 4 + 4));
-                    });
-            }
-        }
+        size_t first = 0;                       // the batch's first output row
+        bool unsorted = false;
+        rc = tile_rows_walk(ctx, t, [&](const TileBatch &mb, uint64_t i, bool heavy) {
+            if (depth[i] >= min_depth) { order.push_back(i); order_tid.push_back(mb.tid); unsorted |= heavy; }
+        }, [&](size_t) {
+            if (unsorted)                       // rows of the global path came in table order: put the batch in (pos1..pos4) order
+                std::sort(order.begin() + (ptrdiff_t)first, order.end(), [&](uint64_t x, uint64_t y) {
+                    return std::lexicographical_compare(hp.begin() + (ptrdiff_t)(x * 4), hp.begin() + (ptrdiff_t)(x * 4 + 4),
+                                                        hp.begin() + (ptrdiff_t)(y * 4), hp.begin() + (ptrdiff_t)(y * 4 + 4));
+                });
+            first = order.size(); unsorted = false;
+        });
+        if (rc) return rc;
         ctx->q_order_epoch = ctx->q_epoch; ctx->q_order_min_depth = min_depth;
     }
     const uint64_t n = order.size();

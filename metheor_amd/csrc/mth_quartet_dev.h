@@ -9,10 +9,6 @@
 
 namespace mth {
 
-// (re)start of a batch's quartet state words: back to the row count before it, no tile handed back, nothing beyond the output
-// (mth_quartet.hip)
-__global__ void k_quartet_rewind(unsigned long long *qs, unsigned long long rows_before);
-
 constexpr unsigned long long QKEY_EMPTY = ~0ull;
 
 // slot of a key in an LDS table of mask + 1 slots: two 32-bit multiplies (a 64-bit mixer costs ~30 VALU)

@@ -169,7 +169,7 @@ def test_every_tile_width(eng, monkeypatch, shift):
     assert check(d, reads, kw) > 8000
 
 
-# ---- batches queued without a host sync (device-resident batches after a context's first; pairs_batch / pairs_resolve) ----
+# ---- batches queued without a host sync (device-resident batches after a context's first; tile_rows_batch / tile_rows_resolve) ----
 @pytest.mark.parametrize("force", ["", "global", "unfit"])
 def test_queued_batches(monkeypatch, capfd, force):
     """global: every tile of the queued batches refuses its LDS table -> replayed through the global path; unfit: the context learns
@@ -215,7 +215,7 @@ def test_queued_batches(monkeypatch, capfd, force):
 def test_queued_batch_beyond_its_estimate_is_replayed_not_truncated(monkeypatch, capfd):
     """ADVICE r04 (high), the pairs table's half: a queued batch that produces more rows than its estimate but still fits the buffer
     (grown to 1.25 x the estimate) used to lose the rows beyond the estimate when the next queued batch grew the buffer.  It is unfit
-    now and the resolve replays it (mth_pairs.hip, pairs_batch)."""
+    now and the resolve replays it (mth_tile_rows.hip, tile_rows_batch)."""
     import metheor_amd
     from metheor_amd import synth
     rng = np.random.default_rng(2025)

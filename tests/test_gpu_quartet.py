@@ -305,7 +305,7 @@ def test_every_tile_width(eng, monkeypatch, shift):
     assert len(d["tid"]) > 7000
 
 
-# ---- batches queued without a host sync (device-resident batches after the first of a context; quartet_batch / quartet_resolve) ----
+# ---- batches queued without a host sync (device-resident batches after the first of a context; tile_rows_batch / tile_rows_resolve) ----
 def _queued_case(seed=31, n_contigs=5, length=60_000, reads=6_000):
     from metheor_amd import synth
     rng = np.random.default_rng(seed)
