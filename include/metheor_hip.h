@@ -52,7 +52,8 @@ enum {
     MTH_ERR_CAPACITY = -8,  /* an on-chip capacity was exceeded */
     MTH_ERR_STATE = -9,     /* call order violated */
     MTH_ERR_FORMAT = -10,   /* device decode: corrupt BGZF block, malformed BAM record, or a record without XM:Z */
-    MTH_ERR_UNALIGNED = -11,/* mth_bgzf_decode: a record straddles two BGZF blocks (decode via the host walk instead) */
+    MTH_ERR_UNALIGNED = -11,/* mth_bgzf_decode: a record straddles two BGZF blocks (mth_bgzf_decode_straddle takes such a file; it returns this when
+                               its rounds do not settle or the carry is too large: decode via the host walk instead) */
     MTH_ERR_RCCL = -12      /* librccl could not be loaded, or an RCCL call failed (mth_last_error has the text) */
 };
 
@@ -367,6 +368,38 @@ int  mth_bgzf_inflate(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const 
  * MTH_ERR_FORMAT. */
 int  mth_bgzf_decode(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
                      const uint32_t *isize, uint64_t n_blocks, uint64_t first_byte, int append, mth_decoded_t *out);
+/* The same step for a BAM whose records STRADDLE BGZF blocks (htsjdk / Picard / GATK, sambamba, biobambam and most writers
+ * that are not htslib cut blocks at a byte count): mth_bgzf_decode refuses such a file, this entry point decodes it.  The
+ * record offsets come from speculation and exact verification: every block guesses its first record start (the first offset whose
+ * 36 header bytes look like a record and whose block_size leads to another such offset or exactly to the end of the call's
+ * stream -- one whose block_size leads PAST the stream is not taken, so the record a call ends inside is nobody's guess; the
+ * block that holds first_byte starts there) and is walked from its guess; the result stands when block 0 enters at first_byte and every block enters where its
+ * predecessor's walk left (a block whose entry lies at or past its own end passes it on).  A block that disagrees takes its
+ * predecessor's exit and is walked again when every block before it is final, or when the predecessor itself agrees with ITS
+ * predecessor -- one round per launch, at most MTH_STRADDLE_MAX_ROUNDS rounds (a record that covers k blocks costs about k),
+ * MTH_ERR_UNALIGNED beyond (the caller takes the host walk, as after mth_bgzf_decode; nothing is appended).  The offsets are
+ * those of the serial chain whatever the guesses were.
+ * The arguments are mth_bgzf_decode's; flags: MTH_STRADDLE_APPEND = its `append`.  The stream of a call may end inside a record:
+ *   neither _LAST nor _DROP_TAIL  the bytes from the start of the first unfinished record on are kept on the device (the carry) and
+ *                                 come first in the stream of the next _APPEND call, which passes first_byte = 0; a carry above
+ *                                 MTH_STRADDLE_MAX_CARRY bytes is MTH_ERR_UNALIGNED
+ *   MTH_STRADDLE_LAST             the stream ends with this call: an unfinished record is MTH_ERR_FORMAT
+ *   MTH_STRADDLE_DROP_TAIL        the stream ends with this call and an unfinished last record is dropped (a --region load: the
+ *                                 last block the index names may end inside a record that starts past the region)
+ * A call without _APPEND, and mth_reset, drop the carry.  info (may be NULL): rounds = repair rounds run, repaired_blocks = blocks
+ * walked again in them, carry_bytes = the carry this call leaves.  mth_timing_get: k_straddle_guess / _walk / _repair. */
+#define MTH_STRADDLE_APPEND     1u
+#define MTH_STRADDLE_LAST       2u
+#define MTH_STRADDLE_DROP_TAIL  4u
+#define MTH_STRADDLE_MAX_ROUNDS 64
+#define MTH_STRADDLE_MAX_CARRY  (256ull << 20)
+typedef struct {
+    uint32_t rounds, repaired_blocks;
+    uint64_t carry_bytes;
+} mth_straddle_info_t;
+int  mth_bgzf_decode_straddle(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
+                              const uint32_t *isize, uint64_t n_blocks, uint64_t first_byte, unsigned flags, mth_decoded_t *out,
+                              mth_straddle_info_t *info);
 /* Overlap of the NEXT chunk's host-to-device copy with the current chunk's kernels: announces file[0, n_bytes) (host memory
  * that stays valid) as the chunk after the one the next mth_bgzf_decode / mth_bgzf_inflate call is given.  That call starts a
  * helper thread which copies the announced bytes into a second staging buffer on a side stream while its own kernels run;

@@ -121,6 +121,12 @@ int  mth_host_plan_shard(mth_host_t *h, int rank, int world, int64_t halo_bp, mt
  * <bam without .bam>.bai.  MTH_HOST_ERR_OPEN without an index, MTH_HOST_ERR_FORMAT for one that is not this file's. */
 int  mth_host_plan_region(mth_host_t *h, const char *bai_path, int32_t tid, int32_t beg, int32_t end, int64_t halo_bp,
                           mth_host_shard_t *out);
+/* The same plan for a file whose BGZF blocks do not start at records (mth_bgzf_decode_straddle in metheor_hip.h): when the plan
+ * does not start at the top of the file, first_byte is the in-block part of the index's first virtual offset -- an exact record
+ * start, where mth_host_plan_region says 0 and lets the load begin with the block.  The last block named may end inside a record
+ * that starts behind the index's end offset (MTH_STRADDLE_DROP_TAIL). */
+int  mth_host_plan_region_at_record(mth_host_t *h, const char *bai_path, int32_t tid, int32_t beg, int32_t end, int64_t halo_bp,
+                                    mth_host_shard_t *out);
 int64_t mth_host_n_reads(const mth_host_t *h);
 int64_t mth_host_n_cpgs(const mth_host_t *h);
 const int32_t  *mth_host_read_tid(const mth_host_t *h);

@@ -16,7 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_decode_set_genome",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_decode_set_genome",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -82,6 +82,14 @@ MULTI_FORMS = dict(auto=MTH_MULTI_AUTO, fused=MTH_MULTI_FUSED, split=MTH_MULTI_S
 class mth_multi_params_t(C.Structure):
     _fields_ = [("want", C.c_uint32), ("pdr_lpmd", mth_pdr_lpmd_params_t), ("quartet", mth_quartet_params_t),
                 ("mhl", mth_mhl_params_t), ("fdrp", mth_fdrp_params_t), ("pairs", mth_lpmd_pairs_params_t), ("form", C.c_int32)]
+
+
+class mth_straddle_info_t(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("repaired_blocks", C.c_uint32), ("carry_bytes", C.c_uint64)]
+
+
+MTH_STRADDLE_APPEND, MTH_STRADDLE_LAST, MTH_STRADDLE_DROP_TAIL = 1, 2, 4
+MTH_STRADDLE_MAX_ROUNDS = 64
 
 
 class mth_tag_out_t(C.Structure):
@@ -152,6 +160,8 @@ def lib():
         L.mth_decode_set_xm_min_mapq.argtypes = [vp, C.c_uint32]
         L.mth_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.mth_bgzf_decode.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(mth_decoded_t)]
+        L.mth_bgzf_decode_straddle.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint, C.POINTER(mth_decoded_t),
+                                               C.POINTER(mth_straddle_info_t)]
         L.mth_bgzf_stage.argtypes = [vp, vp, C.c_uint64]
         L.mth_decode_reserve.argtypes = [vp, C.c_uint64, C.c_uint64]
         L.mth_tag_set_genome.argtypes = [vp, C.c_int32, vp, vp, vp]
@@ -501,6 +511,23 @@ class Engine:
                                            len(coff), int(first_byte), int(bool(append)), C.byref(d)))
         self._decoded = d
         return int(d.n_reads), int(d.n_cpgs)
+
+    def bgzf_decode_straddle(self, file_bytes, coff, csize, isize, first_byte, append=False, last=False, drop_tail=False):
+        """bgzf_decode for a file whose records straddle BGZF blocks (mth_bgzf_decode_straddle).  A call whose stream ends inside a
+        record keeps that record's bytes on the device for the next append=True call; last=True: the stream ends here (an unfinished
+        record is an error); drop_tail=True: it ends here and an unfinished last record is dropped.
+        -> (n_reads, n_cpgs, dict(rounds, repaired_blocks, carry_bytes)); the dict is also self.straddle_info, set before an error is
+        raised"""
+        fb = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(file_bytes, np.uint8)
+        coff = np.ascontiguousarray(coff, np.uint64); csize = np.ascontiguousarray(csize, np.uint32); isize = np.ascontiguousarray(isize, np.uint32)
+        flags = (MTH_STRADDLE_APPEND if append else 0) | (MTH_STRADDLE_LAST if last else 0) | (MTH_STRADDLE_DROP_TAIL if drop_tail else 0)
+        d, info = mth_decoded_t(), mth_straddle_info_t()
+        rc = self.L.mth_bgzf_decode_straddle(self.h, fb.ctypes.data, fb.size, coff.ctypes.data, csize.ctypes.data, isize.ctypes.data,
+                                             len(coff), int(first_byte), flags, C.byref(d), C.byref(info))
+        self.straddle_info = dict(rounds=int(info.rounds), repaired_blocks=int(info.repaired_blocks), carry_bytes=int(info.carry_bytes))
+        self._check(rc)
+        self._decoded = d
+        return int(d.n_reads), int(d.n_cpgs), self.straddle_info
 
     def tag_set_genome(self, contigs):
         """contigs: [(header LN, bases as bytes)] in tid order (mth_tag_set_genome; tag.rs:419-431)"""

@@ -450,24 +450,17 @@ int window_to_device(void *user, const uint8_t *buf, const uint64_t *rec_off, ui
 
 // Whole load path on the device (mth_bgzf_decode): the file's bytes go to the GPU as they are, BGZF inflate, record
 // boundaries and record decode all happen there.  Needs every BGZF block to hold whole records (what htslib-family
-// writers produce); returns false -- with the context reset -- for a file where that does not hold.
+// writers produce).  For a file where that does not hold (htsjdk / Picard, sambamba, ...: blocks cut at a byte count) the
+// chunks go through mth_bgzf_decode_straddle instead -- under --region always (nothing else can load a part of such a file),
+// for a whole file when METHEOR_DEVICE_STRADDLE=1 (which route is the faster one there: profiles/straddle_walk.md) -- with a
+// phase line of its own.  Returns false, with the context reset, when the file is left to the host walk.
+// --gpus N keeps needing whole records per block: a shard's first block has no verified entry without its neighbour's chain.
+const char *const kStraddlePhase = "  device inflate + straddle walk + decode";
 
-bool load_bgzf_on_device(Input &in) {
-    mth_host_bgzf_t bz;
-    if (mth_host_bgzf_blocks(in.h, &bz) != 0) die(mth_host_last_error(in.h));
-    uint64_t blk_beg = 0;
-    if (g_shard.planned()) {      // this shard's run of blocks (+ halo blocks), or the blocks the .bai names for --region, instead of the whole file
-        if (g_shard.region) {
-            const int tid = mth_host_ref_tid(in.h, g_shard.region_name.c_str());
-            if (tid < 0) die("--region: the BAM header has no reference named '" + g_shard.region_name + "'");
-            if (mth_host_plan_region(in.h, g_shard.bai.empty() ? nullptr : g_shard.bai.c_str(), tid, g_shard.r_beg, g_shard.r_end, g_shard.halo, &g_shard.plan) != 0)
-                die(mth_host_last_error(in.h));
-        } else if (mth_host_plan_shard(in.h, g_shard.rank, g_shard.world, g_shard.halo, &g_shard.plan) != 0) die(mth_host_last_error(in.h));
-        blk_beg = g_shard.plan.block_beg;
-        bz.n_blocks = g_shard.plan.block_end;
-        bz.header_bytes = g_shard.plan.first_byte;
-    }
-    Phase ph("  device inflate + walk + decode");
+// the chunk loop over blocks [blk_beg, bz.n_blocks) (bz.header_bytes: inflated bytes of the first block before the first record);
+// straddle: records may cross blocks and chunks (the library carries the unfinished record from call to call), region_tail: the
+// last block may end inside a record that is not wanted.  -> MTH_OK or MTH_ERR_UNALIGNED
+int load_chunks(Input &in, const mth_host_bgzf_t &bz, uint64_t blk_beg, bool straddle, bool region_tail) {
     // Chunks of whole blocks.  The first is small (<= 512 MiB of file bytes) so that the GPU starts early; every later chunk
     // (<= 2 GiB; METHEOR_CHUNK_GROWTH makes the sizes grow geometrically instead -- measured slower, profiles/r02_e2e.md) is copied to the device by a helper thread on a side stream (mth_bgzf_stage) while the chunk before it is
     // being inflated and decoded -- only the first copy is exposed.  METHEOR_DEVICE_CHUNK_MB sets both sizes,
@@ -502,9 +495,20 @@ bool load_bgzf_on_device(Input &in) {
         std::vector<uint64_t> rel((size_t)(c.b1 - c.b0));
         for (uint64_t k = c.b0; k < c.b1; ++k) rel[(size_t)(k - c.b0)] = bz.coff[k] - c.base;
         mth_decoded_t d;
-        const int rc = mth_bgzf_decode(in.ctx, bz.file + c.base, c.nbytes, rel.data(), bz.csize + c.b0, bz.isize + c.b0, c.b1 - c.b0, first_byte, first ? 0 : 1, &d);
+        int rc;
+        if (straddle) {
+            // the next chunk is staged from its planned file offset all the same: the record a chunk ends in travels in the carry
+            const unsigned flags = (first ? 0u : MTH_STRADDLE_APPEND) | (ci + 1 < chunks.size() ? 0u : (region_tail ? MTH_STRADDLE_DROP_TAIL : MTH_STRADDLE_LAST));
+            mth_straddle_info_t info;
+            rc = mth_bgzf_decode_straddle(in.ctx, bz.file + c.base, c.nbytes, rel.data(), bz.csize + c.b0, bz.isize + c.b0, c.b1 - c.b0, first_byte, flags, &d, &info);
+            if (getenv("METHEOR_TIMING"))       // one line per library call: what the walk needed, and what travels into the next chunk
+                fprintf(stderr, "[metheor straddle] chunk %zu of %zu: %llu blocks, %u rounds, %u blocks repaired, %llu bytes carried\n", ci + 1, chunks.size(),
+                        (unsigned long long)(c.b1 - c.b0), info.rounds, info.repaired_blocks, (unsigned long long)info.carry_bytes);
+        } else {
+            rc = mth_bgzf_decode(in.ctx, bz.file + c.base, c.nbytes, rel.data(), bz.csize + c.b0, bz.isize + c.b0, c.b1 - c.b0, first_byte, first ? 0 : 1, &d);
+        }
         hdr_left -= first_byte;
-        if (rc == MTH_ERR_UNALIGNED) { check(in.ctx, mth_reset(in.ctx)); return false; }
+        if (rc == MTH_ERR_UNALIGNED) { check(in.ctx, mth_reset(in.ctx)); return rc; }
         if (rc == MTH_ERR_FORMAT) die_decode_format(in.ctx, "corrupt BGZF block or BAM record");
         check(in.ctx, rc);
         done_u += c.ubytes;
@@ -515,7 +519,39 @@ bool load_bgzf_on_device(Input &in) {
         }
         first = false;
     }
-    return true;
+    return MTH_OK;
+}
+
+bool load_bgzf_on_device(Input &in) {
+    mth_host_bgzf_t bz;
+    if (mth_host_bgzf_blocks(in.h, &bz) != 0) die(mth_host_last_error(in.h));
+    const uint64_t all_blocks = bz.n_blocks, file_header = bz.header_bytes;
+    uint64_t blk_beg = 0;
+    // this shard's run of blocks (+ halo blocks), or the blocks the .bai names for --region, instead of the whole file.  at_record: the
+    // region plan that starts at the index's exact record offset inside its first block (blocks that do not start at records)
+    auto plan = [&](bool at_record) {
+        if (g_shard.region) {
+            const int tid = mth_host_ref_tid(in.h, g_shard.region_name.c_str());
+            if (tid < 0) die("--region: the BAM header has no reference named '" + g_shard.region_name + "'");
+            const char *bai = g_shard.bai.empty() ? nullptr : g_shard.bai.c_str();
+            if ((at_record ? mth_host_plan_region_at_record : mth_host_plan_region)(in.h, bai, tid, g_shard.r_beg, g_shard.r_end, g_shard.halo, &g_shard.plan) != 0)
+                die(mth_host_last_error(in.h));
+        } else if (mth_host_plan_shard(in.h, g_shard.rank, g_shard.world, g_shard.halo, &g_shard.plan) != 0) die(mth_host_last_error(in.h));
+        blk_beg = g_shard.plan.block_beg;
+        bz.n_blocks = g_shard.plan.block_end;
+        bz.header_bytes = g_shard.plan.first_byte;
+    };
+    if (g_shard.planned()) plan(false);
+    {
+        Phase ph("  device inflate + walk + decode");
+        if (load_chunks(in, bz, blk_beg, false, false) == MTH_OK) return true;
+    }
+    const char *e = getenv("METHEOR_DEVICE_STRADDLE");
+    if (g_shard.world > 1 || !(g_shard.region || (e && atoi(e) != 0))) return false;
+    bz.n_blocks = all_blocks; bz.header_bytes = file_header;
+    if (g_shard.region) plan(true);
+    Phase ph(kStraddlePhase);
+    return load_chunks(in, bz, blk_beg, true, g_shard.region) == MTH_OK;
 }
 
 bool batch_decoded(Input &in, const std::vector<int32_t> &tids, const std::vector<uint64_t> &rb, const std::vector<uint64_t> &re,

@@ -336,7 +336,8 @@ int mth_host_plan_shard(mth_host_t *h, int rank, int world, int64_t halo_bp, mth
     return MTH_HOST_OK;
 }
 
-int mth_host_plan_region(mth_host_t *h, const char *bai_path, int32_t tid, int32_t beg, int32_t end, int64_t halo_bp, mth_host_shard_t *out) {
+// at_record: first_byte = the in-block part of the index's first virtual offset (an exact record start) instead of 0
+static int plan_region(mth_host_t *h, const char *bai_path, int32_t tid, int32_t beg, int32_t end, int64_t halo_bp, mth_host_shard_t *out, bool at_record) {
     if (!h || !out || tid < 0 || tid >= (int32_t)h->reader.refs().size() || beg < 0 || end < beg || halo_bp < 0) return MTH_HOST_ERR_INVALID;
     mth_host_bgzf_t bz;
     const int rc = mth_host_bgzf_blocks(h, &bz);
@@ -365,9 +366,17 @@ int mth_host_plan_region(mth_host_t *h, const char *bai_path, int32_t tid, int32
     // the block that holds the first record also holds the tail of the header: load from the top of the file then
     uint64_t D = 0, cum = 0;
     while (D < bz.n_blocks && cum + m.isize[D] <= h->header_bytes) cum += m.isize[D++];
-    if (L <= D) { out->block_beg = 0; out->first_byte = h->header_bytes; } else { out->block_beg = L; out->first_byte = 0; }
+    if (L <= D) { out->block_beg = 0; out->first_byte = h->header_bytes; } else { out->block_beg = L; out->first_byte = at_record ? (vlo & 0xffffu) : 0; }
     out->block_end = R;
     return MTH_HOST_OK;
+}
+
+int mth_host_plan_region(mth_host_t *h, const char *bai_path, int32_t tid, int32_t beg, int32_t end, int64_t halo_bp, mth_host_shard_t *out) {
+    return plan_region(h, bai_path, tid, beg, end, halo_bp, out, false);
+}
+
+int mth_host_plan_region_at_record(mth_host_t *h, const char *bai_path, int32_t tid, int32_t beg, int32_t end, int64_t halo_bp, mth_host_shard_t *out) {
+    return plan_region(h, bai_path, tid, beg, end, halo_bp, out, true);
 }
 
 int mth_host_decode_stream(mth_host_t *h, mth_host_window_cb cb, void *user) {

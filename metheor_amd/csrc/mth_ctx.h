@@ -159,6 +159,10 @@ struct mth_ctx {
     uint64_t next_bytes = 0;
     std::thread stage_thread;
     int stage_rc = 0;
+    // mth_bgzf_decode_straddle: per-block entry / exit / count of the record chain (two generations, a round reads one and writes
+    // the other), and the bytes of the record the previous call's stream ended in (they come first in the next call's stream)
+    mth::DevBuf inf_links, inf_carry;
+    uint64_t carry_bytes = 0;
     // `tag` (mth_tag.hip): the genome (contigs back to back), per-contig offsets + header lengths, per-record work arrays,
     // and the host copies mth_tag_records hands out
     mth::DevBuf tag_genome, tag_goff, tag_ncol, tag_coloff, tag_xmlen, tag_cols, tag_xm;

@@ -13,7 +13,23 @@
 // k_block_walk: BAM writers built on htslib flush the BGZF block before a record that would not fit, so records
 // never straddle blocks and every block starts at a record boundary: one thread per block follows the block_size
 // chain, counting / writing record offsets, and VERIFIES that the chain ends exactly at the block's end.  A file for
-// which that does not hold sets ERRB_UNALIGNED and the caller takes the host walk instead.
+// which that does not hold sets ERRB_UNALIGNED and the caller takes the host walk instead -- or mth_bgzf_decode_straddle:
+//
+// Records that STRADDLE blocks (htsjdk / Picard / GATK, sambamba, biobambam cut blocks at a byte count).  The inflated stream of a
+// call is contiguous in inf_raw; only the record offsets are missing, and the entry offset of block b is the exit offset of block
+// b - 1: a serial chain over the file.  It is built by speculation and exact verification.  k_straddle_guess: a wave per block finds
+// the block's first offset that looks like a record start (the block that holds first_byte starts there).  k_straddle_walk: a thread
+// per block follows block_size from its entry while a record STARTS inside the block (it may end in a later one) and leaves a count
+// and an exit offset, absolute in the stream; a speculative walk sets no error bit, an unreadable or bogus block_size just ends it
+// with an exit past everything.  The state is final when block 0 enters at first_byte and every block enters where its predecessor
+// left (a block whose entry lies at or past its own end passes it on): by induction those are the offsets of the serial chain, and
+// nothing of the guess rule enters the result.  Until then k_straddle_check / k_straddle_repair run in rounds -- separate launches,
+// the host reads one mismatch counter per round, no grid barrier, no workgroup waits for another -- at most
+// MTH_STRADDLE_MAX_ROUNDS of them; past that the call is MTH_ERR_UNALIGNED like mth_bgzf_decode's and the caller takes the host
+// walk.  A record that covers k whole blocks costs about k rounds.  Then count -> scan_u32_to_u64 -> fill (the only pass that raises
+// ERRB_FORMAT: block_size < 32, or a finished stream that ends inside a record) and decode_core as ever.  A call whose stream ends
+// inside a record keeps the bytes from that record's start on the device (ctx->inf_carry); they come first in the next call's
+// stream, whose block 0 then begins at offset 0.
 #include "mth_ctx.h"
 
 namespace mth {
@@ -475,6 +491,138 @@ __global__ __launch_bounds__(256) void k_block_walk(const WalkBArgs a) {
     if (FILL && blk == a.n_blocks - 1) a.rec_off[a.base[blk] + n] = a.total_bytes;
 }
 
+// ---- record walk for records that straddle blocks: speculation, then exact verification ------------------------------
+// (mth_bgzf_decode_straddle; the formulation is described at the top of the file)
+constexpr uint64_t STR_NONE = ~0ull;          // entry of a block without a guess: equal to no exit
+constexpr uint64_t STR_PAST = 1ull << 62;     // exit of a walk that cannot go on (no readable, sane block_size): past every block
+
+// mismatch / first_bad: blocks that do not enter where their predecessor left, and the first of them (k_straddle_check);
+// tail: where the unfinished (or bogus) record starts, else the stream's end
+struct StrState { uint32_t mismatch, first_bad, repaired, pad_; unsigned long long tail; };
+struct StrArgs {
+    const uint8_t *raw;            // the call's stream: the carry, then the inflated blocks
+    const uint64_t *uoff;          // per block: offset of its bytes in raw (block 0 also owns the carry in front of it)
+    const uint32_t *isize;
+    uint32_t n_blocks;
+    uint64_t first_byte, total;    // records start at first_byte; raw holds total bytes
+    const uint64_t *entry_in, *exit_in;      // the generation a launch reads ...
+    const uint32_t *cnt_in;
+    uint64_t *entry_out, *exit_out;          // ... and the one it writes
+    uint32_t *cnt_out;
+    StrState *st;
+    const unsigned long long *base;          // fill: exclusive scan of the final counts
+    uint64_t *rec_off;                       // fill: record offsets + the closing offset
+    int last;                                // fill: the stream ends here and may not end inside a record (MTH_STRADDLE_LAST)
+    uint32_t *err;
+};
+__device__ __forceinline__ uint32_t str_ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+// do the 36 bytes at p look like the fixed part of a BAM record (SAM spec 4.2)?  next = where its block_size leads.
+// Bounded by the stream length before anything is loaded: p is any offset at all.
+__device__ __forceinline__ bool str_plausible(const uint8_t *raw, uint64_t p, uint64_t total, uint64_t &next) {
+    if (p + 36 > total) return false;
+    const int32_t bs = (int32_t)str_ld32(raw + p), ref = (int32_t)str_ld32(raw + p + 4), pos = (int32_t)str_ld32(raw + p + 8);
+    const int64_t l_name = str_ld32(raw + p + 12) & 0xffu, n_cigar = str_ld32(raw + p + 16) & 0xffffu;
+    const int32_t l_seq = (int32_t)str_ld32(raw + p + 20), next_ref = (int32_t)str_ld32(raw + p + 24), next_pos = (int32_t)str_ld32(raw + p + 28);
+    next = p + 4 + (uint64_t)(uint32_t)bs;
+    return bs >= 32 && ref >= -1 && next_ref >= -1 && pos >= -1 && next_pos >= -1 && l_name >= 1 && l_seq >= 0 &&
+           32 + l_name + 4 * n_cigar + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq <= (int64_t)bs;
+}
+// one wave per block: the lanes test 64 consecutive offsets at a time; the first that passes, and whose record leads to another
+// offset that passes or exactly to the stream's end, is the block's guess.  (A block_size that leads PAST the stream is not
+// taken: among sequence and quality bytes one offset in a few dozen passes the field tests with a block_size of hundreds of
+// megabytes.  The record a call's stream ends inside therefore is nobody's guess; the block it starts in is repaired if it
+// holds no earlier start.)
+__global__ __launch_bounds__(256) void k_straddle_guess(const StrArgs a) {
+    const uint32_t blk = uni(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    if (blk == 0 && lane == 0) a.st->tail = a.total;
+    if (blk >= a.n_blocks) return;
+    const uint64_t b0 = blk ? uni64(a.uoff[blk]) : 0ull, b1 = uni64(a.uoff[blk]) + uni(a.isize[blk]);
+    uint64_t g = STR_NONE;
+    if (b0 <= a.first_byte) {
+        g = a.first_byte;                        // the records start in (or after) this block: no guess needed
+    } else {
+        for (uint64_t q = b0; q < b1; q += 64) {
+            const uint64_t p = q + lane;
+            uint64_t nx = 0, nx2;
+            bool ok = p < b1 && str_plausible(a.raw, p, a.total, nx);
+            if (ok && nx != a.total) ok = nx < a.total && str_plausible(a.raw, nx, a.total, nx2);
+            const unsigned long long m = __ballot(ok);
+            if (m) { g = q + (uint64_t)(__ffsll((long long)m) - 1); break; }
+        }
+    }
+    if (lane == 0) a.entry_out[blk] = g;
+}
+// the records that START in [entry, b1), following block_size; a record may end in a later block.  Returns where the chain
+// leaves the block: the next block's entry.  FILL (the final pass) writes the offsets and is the only one to raise an error.
+template <bool FILL>
+__device__ __forceinline__ uint64_t str_walk(const StrArgs &a, uint32_t blk, uint64_t entry, uint64_t b1, uint32_t &n) {
+    n = 0;
+    if (entry == STR_NONE) return STR_PAST;
+    uint64_t p = entry;
+    unsigned long long w = FILL ? a.base[blk] : 0ull;
+    while (p < b1) {
+        bool cut = p + 4 > a.total, bogus = false;         // cut: the stream ends inside this record
+        uint32_t bs = 0;
+        if (!cut) {
+            bs = str_ld32(a.raw + p);
+            bogus = (int32_t)bs < 32;
+            cut = !bogus && p + 4 + (uint64_t)bs > a.total;
+        }
+        if (cut || bogus) {
+            if (FILL) {
+                if (bogus || a.last) atomicOr(a.err, (uint32_t)ERRB_FORMAT);
+                a.st->tail = p;                              // (one block at most gets here: no record starts behind this one)
+                a.rec_off[w] = p;                            // the closing offset: the end of the last whole record
+            }
+            return STR_PAST;
+        }
+        if (FILL) a.rec_off[w++] = p;
+        ++n;
+        p += 4 + (uint64_t)bs;
+    }
+    return p;
+}
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_straddle_walk(const StrArgs a) {
+    const uint32_t blk = blockIdx.x * 256 + threadIdx.x;
+    if (blk >= a.n_blocks) return;
+    const uint64_t b1 = a.uoff[blk] + a.isize[blk];
+    uint32_t n;
+    const uint64_t x = str_walk<FILL>(a, blk, a.entry_in[blk], b1, n);
+    if (!FILL) { a.exit_out[blk] = x; a.cnt_out[blk] = n; }
+    if (FILL && blk == a.n_blocks - 1 && x == a.total) a.rec_off[a.base[blk] + n] = a.total;    // the chain ends with the stream: the closing offset
+}
+// A round.  k_straddle_check counts the blocks that do not enter where their predecessor left (none: the offsets are final) and
+// finds the first of them: every block before it is final, so its own new entry is certain.  k_straddle_repair then walks again
+// that block, and every other such block whose predecessor agrees with ITS predecessor -- from a predecessor that is itself about
+// to change, a wrong entry would only move on, one block per round, with the correction chasing it.  A predecessor can agree and
+// still be wrong (two guesses on one chain of decoys); walking from a wrong offset nearly always ends on an unreadable block_size,
+// so an exit that says "cannot go on" is believed only of the block whose predecessors are final.
+__device__ __forceinline__ uint64_t str_want(const StrArgs &a, uint32_t blk) { return blk ? a.exit_in[blk - 1] : a.first_byte; }
+__global__ __launch_bounds__(256) void k_straddle_check(const StrArgs a) {
+    const uint32_t blk = blockIdx.x * 256 + threadIdx.x;
+    if (blk >= a.n_blocks || a.entry_in[blk] == str_want(a, blk)) return;
+    atomicAdd(&a.st->mismatch, 1u);
+    atomicMin(&a.st->first_bad, blk);
+}
+__global__ __launch_bounds__(256) void k_straddle_repair(const StrArgs a) {
+    const uint32_t blk = blockIdx.x * 256 + threadIdx.x;
+    if (blk >= a.n_blocks) return;
+    uint64_t entry = a.entry_in[blk], x = a.exit_in[blk];
+    uint32_t n = a.cnt_in[blk];
+    const uint64_t want = str_want(a, blk);
+    if (entry != want) {
+        const bool pred_agrees = blk == 0 || a.entry_in[blk - 1] == str_want(a, blk - 1);
+        if (blk == a.st->first_bad || (pred_agrees && want < STR_PAST)) {
+            entry = want;
+            x = str_walk<false>(a, blk, entry, a.uoff[blk] + a.isize[blk], n);
+            atomicAdd(&a.st->repaired, 1u);
+        }
+    }
+    a.entry_out[blk] = entry; a.exit_out[blk] = x; a.cnt_out[blk] = n;
+}
+
 }  // namespace mth
 
 using namespace mth;
@@ -494,14 +642,16 @@ static void crc_zero_operators(uint32_t (*mat)[32]) {
 // (Splitting a pageable host-to-device copy over 4 / 8 host threads that enqueue slices into the same stream was measured:
 // no gain at 4, slower at 8 -- profiles/r02_e2e.md.)
 // stage the file bytes + block table and launch the inflate; on return d_uoff / d_isize point at the device table
+// (the blocks' output starts at stream_base in inf_raw; total includes it)
 static int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
-                          const uint32_t *isize, uint64_t n_blocks, uint64_t &total, uint64_t *&d_uoff, uint32_t *&d_isize) {
+                          const uint32_t *isize, uint64_t n_blocks, uint64_t &total, uint64_t *&d_uoff, uint32_t *&d_isize, uint64_t stream_base = 0) {
     if (n_blocks >= (1ull << 31)) return fail(ctx, MTH_ERR_CAPACITY, "too many BGZF blocks in one call: split the file");
     MTH_ENTER(ctx);
     hipStream_t s = ctx->stream;
     const size_t nb = (size_t)n_blocks;
     // output offsets of the blocks + validation of the table against the byte range given
     std::vector<uint64_t> uoff(nb + 1, 0);
+    uoff[0] = stream_base;                    // (mth_bgzf_decode_straddle: the carry comes first in the stream)
     for (size_t i = 0; i < nb; ++i) {
         if (coff[i] + (uint64_t)csize[i] > n_bytes || isize[i] > 65536u) return fail(ctx, MTH_ERR_INVALID, "BGZF block table does not fit the file bytes");
         uoff[i + 1] = uoff[i] + isize[i];
@@ -685,6 +835,105 @@ int mth_bgzf_decode(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const ui
         MTH_HIP(ctx, ctx->inf_recoff.reserve((size_t)(n_rec + 1) * 8 + 16, s));
         wa.base = ctx->inf_base.as<unsigned long long>(); wa.rec_off = ctx->inf_recoff.as<uint64_t>();
         hipLaunchKernelGGL((k_block_walk<true>), dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, wa);
+    }
+    return decode_core(ctx, ctx->inf_raw.as<uint8_t>(), ctx->inf_recoff.as<uint64_t>(), n_rec, append, out);
+}
+
+int mth_bgzf_decode_straddle(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
+                             const uint32_t *isize, uint64_t n_blocks, uint64_t first_byte, unsigned flags, mth_decoded_t *out,
+                             mth_straddle_info_t *info) {
+    if (!ctx || !out || (n_blocks && (!file || !coff || !csize || !isize))) return MTH_ERR_INVALID;
+    const unsigned ends = flags & (MTH_STRADDLE_LAST | MTH_STRADDLE_DROP_TAIL);
+    if ((flags & ~(MTH_STRADDLE_APPEND | MTH_STRADDLE_LAST | MTH_STRADDLE_DROP_TAIL)) || ends == (MTH_STRADDLE_LAST | MTH_STRADDLE_DROP_TAIL))
+        return fail(ctx, MTH_ERR_INVALID, "mth_bgzf_decode_straddle: flags");
+    if (info) *info = mth_straddle_info_t{0, 0, 0};
+    const int append = (flags & MTH_STRADDLE_APPEND) ? 1 : 0;
+    if (!append) ctx->carry_bytes = 0;
+    const uint64_t carry = ctx->carry_bytes;
+    if (carry && first_byte) return fail(ctx, MTH_ERR_INVALID, "first_byte must be 0 while a record of the previous call is carried");
+    ctx->carry_bytes = 0;                     // consumed by this call, whatever becomes of it
+    uint64_t total = 0, *d_uoff = nullptr;
+    uint32_t *d_isize = nullptr;
+    int rc = inflate_blocks(ctx, file, n_bytes, coff, csize, isize, n_blocks, total, d_uoff, d_isize, carry);
+    if (rc) return rc;
+    if (first_byte > total) return fail(ctx, MTH_ERR_INVALID, "first_byte beyond the inflated stream");
+    hipStream_t s = ctx->stream;
+    // the carry was copied aside at the end of the previous call: inf_raw may have been reallocated since
+    if (carry) MTH_HIP(ctx, hipMemcpyAsync(ctx->inf_raw.p, ctx->inf_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, s));
+    const size_t nb = (size_t)n_blocks;
+    uint64_t n_rec = 0, tail = total;
+    if (nb == 0) {
+        tail = 0;                             // nothing but the carry: still unfinished
+        if (carry && (flags & MTH_STRADDLE_LAST)) return fail(ctx, MTH_ERR_FORMAT, "the BAM stream ends inside a record");
+    } else {
+        // per block, two generations of (entry, exit, count): a round reads one and writes the other
+        const size_t gen = nb * 8;
+        MTH_HIP(ctx, ctx->inf_links.reserve(64 + 4 * gen + 2 * nb * 4 + 16, s));
+        MTH_HIP(ctx, ctx->inf_base.reserve((nb + 1) * 8 + 16, s));
+        uint8_t *const lk = static_cast<uint8_t *>(ctx->inf_links.p);
+        StrState *const st = reinterpret_cast<StrState *>(lk);
+        uint64_t *const entry[2] = {reinterpret_cast<uint64_t *>(lk + 64), reinterpret_cast<uint64_t *>(lk + 64 + gen)};
+        uint64_t *const exit_[2] = {reinterpret_cast<uint64_t *>(lk + 64 + 2 * gen), reinterpret_cast<uint64_t *>(lk + 64 + 3 * gen)};
+        uint32_t *const cnt[2] = {reinterpret_cast<uint32_t *>(lk + 64 + 4 * gen), reinterpret_cast<uint32_t *>(lk + 64 + 4 * gen + nb * 4)};
+        MTH_HIP(ctx, hipMemsetAsync(st, 0, sizeof(StrState), s));
+        StrArgs a{};
+        a.raw = ctx->inf_raw.as<uint8_t>(); a.uoff = d_uoff; a.isize = d_isize; a.n_blocks = (uint32_t)nb;
+        a.first_byte = first_byte; a.total = total; a.st = st; a.err = &ctx->d_state->err;
+        const dim3 per_thread((uint32_t)((nb + 255) / 256));
+        a.entry_out = entry[0];
+        { LaunchTimer lt(ctx, K_STR_GUESS); hipLaunchKernelGGL(k_straddle_guess, dim3((uint32_t)((nb + 3) / 4)), dim3(256), 0, s, a); }
+        a.entry_in = entry[0]; a.exit_out = exit_[0]; a.cnt_out = cnt[0];
+        { LaunchTimer lt(ctx, K_STR_WALK); hipLaunchKernelGGL((k_straddle_walk<false>), per_thread, dim3(256), 0, s, a); }
+        // rounds: separate launches, the host reads one mismatch counter per round; generation `cur` is final when nothing mismatches
+        int cur = 0;
+        uint32_t rounds = 0;
+        bool settled = false;
+        for (;;) {
+            const uint32_t none[2] = {0u, 0xffffffffu};                  // mismatch, first_bad
+            MTH_HIP(ctx, hipMemcpyAsync(st, none, sizeof none, hipMemcpyHostToDevice, s));
+            a.entry_in = entry[cur]; a.exit_in = exit_[cur]; a.cnt_in = cnt[cur];
+            a.entry_out = entry[cur ^ 1]; a.exit_out = exit_[cur ^ 1]; a.cnt_out = cnt[cur ^ 1];
+            { LaunchTimer lt(ctx, K_STR_REPAIR); hipLaunchKernelGGL(k_straddle_check, per_thread, dim3(256), 0, s, a); }
+            uint32_t mismatch = 0;
+            MTH_HIP(ctx, hipMemcpyAsync(&mismatch, &st->mismatch, 4, hipMemcpyDeviceToHost, s));
+            MTH_HIP(ctx, hipStreamSynchronize(s));
+            if (mismatch == 0) { settled = true; break; }
+            if (rounds == MTH_STRADDLE_MAX_ROUNDS) break;
+            { LaunchTimer lt(ctx, K_STR_REPAIR); hipLaunchKernelGGL(k_straddle_repair, per_thread, dim3(256), 0, s, a); }
+            cur ^= 1;
+            ++rounds;
+        }
+        StrState hs{};
+        if (!settled) {
+            if ((rc = sync_and_check(ctx))) return rc;      // a corrupt block explains it better
+            MTH_HIP(ctx, hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
+            if (info) { info->rounds = MTH_STRADDLE_MAX_ROUNDS; info->repaired_blocks = hs.repaired; }
+            return fail(ctx, MTH_ERR_UNALIGNED, "the record offsets did not settle within the round bound (records far longer than a BGZF block, or data that looks like record headers): use the host walk");
+        }
+        unsigned long long tot_rec = 0;
+        rc = scan_u32_to_u64(ctx, cnt[cur], (uint32_t)nb, 0ull, ctx->inf_base.as<unsigned long long>(), &tot_rec);
+        if (rc) return rc;                       // (synchronises: inflate errors surface here)
+        n_rec = tot_rec;
+        if (n_rec >= (1ull << 32) - 16) return fail(ctx, MTH_ERR_CAPACITY, "more than 2^32 records in one decode call: split the stream");
+        MTH_HIP(ctx, ctx->inf_recoff.reserve((size_t)(n_rec + 1) * 8 + 16, s));
+        a.entry_in = entry[cur]; a.base = ctx->inf_base.as<unsigned long long>(); a.rec_off = ctx->inf_recoff.as<uint64_t>();
+        a.last = (flags & MTH_STRADDLE_LAST) ? 1 : 0;
+        { LaunchTimer lt(ctx, K_STR_WALK); hipLaunchKernelGGL((k_straddle_walk<true>), per_thread, dim3(256), 0, s, a); }
+        if ((rc = sync_and_check(ctx))) return rc;          // block_size < 32, or a finished stream that ends inside a record
+        MTH_HIP(ctx, hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
+        tail = hs.tail;
+        if (info) { info->rounds = rounds; info->repaired_blocks = hs.repaired; }
+    }
+    if (!ends && tail < total) {
+        // the unfinished record comes first in the next call's stream: copied aside now, inf_raw is that call's to reuse
+        const uint64_t keep = total - tail;
+        if (keep > MTH_STRADDLE_MAX_CARRY) return fail(ctx, MTH_ERR_UNALIGNED, "a record left unfinished by this call is larger than the carry buffer: use the host walk");
+        if (nb) {                                 // (nb == 0: the carry is where it was)
+            MTH_HIP(ctx, ctx->inf_carry.reserve((size_t)keep, s));
+            MTH_HIP(ctx, hipMemcpyAsync(ctx->inf_carry.p, ctx->inf_raw.as<uint8_t>() + tail, (size_t)keep, hipMemcpyDeviceToDevice, s));
+        }
+        ctx->carry_bytes = keep;
+        if (info) info->carry_bytes = keep;
     }
     return decode_core(ctx, ctx->inf_raw.as<uint8_t>(), ctx->inf_recoff.as<uint64_t>(), n_rec, append, out);
 }
