@@ -5,8 +5,11 @@
 // concordant / discordant CpG-pair counts inside a query-distance window.
 //
 // How (MI355X-first, nothing like the reference's hash maps):
-//   k_build_index   one thread per read: a linear index "first read starting at or after q*32 bp"
-//                   (reads are coordinate sorted) + sortedness validation.
+//   k_build_index   sortedness validation (reads are coordinate sorted) + a linear index over the reads.  <2>, the dense tile
+//                   kernel's own: "first read starting at or after the boundary" for the two boundaries of every 4096-bp
+//                   tile, decided per wave of 256 consecutive reads on the scalar unit from the element before the wave and
+//                   the wave's last read (ballots + popcounts where a boundary is crossed; nothing per read but the
+//                   compares).  <1>, for every other kernel: "first read starting at or after q*32 bp", four reads a thread.
 //   k_pdr_lpmd_tile one 256-thread workgroup per 4096-bp tile of the contig.  The tile's site
 //                   accumulators are DENSE in LDS (one 32-bit word per reference position holding both
 //                   16-bit counts, 16 KiB; tiles with > 65535 candidate reads run two half-tile passes with
@@ -39,12 +42,26 @@ namespace mth {
 // whose group contains index n_reads also plays the sentinel that closes the index.
 constexpr int IDX_GROUPS = 1;   // groups of 4 reads per thread; 4 (all loads hoisted) measured slower: 0.0177 against 0.0157 ms on config 2.  Under the batch
                                 // pipeline 2 looked 1.4 % better in one interleaved A/B (tools/ab_lib.sh) -- and three copies of ONE build differed by up to 3 % in the next: not adopted
-// NIDX = 1: the fine index (QSHIFT = IDX_QSHIFT, 32-bp quanta) every tile / site kernel can look any position up in.
-// NIDX = 2 (the dense PDR + LPMD tile kernel's own, round 4): that kernel asks two questions per 4096-bp tile only -- the first
-// read starting at or after T0 - max_span + 1 and the first one starting after T0 + W -- so two indices with ONE entry per tile
-// (quantum = tile width, origins region_beg - max_span + 1 and region_beg + 1) answer them exactly: 2 x 14 312 entries instead of
-// 1.83 M on config 2, no store loop for four reads in five, and the tile's candidate range loses the up to 2 x 31 bp of reads the
-// 32-bp rounding handed it.
+// NIDX = 1 (this body): the fine index (QSHIFT = IDX_QSHIFT, 32-bp quanta) every tile / site kernel can look any position up in.
+// NIDX = 2 (the specialisation below): the dense PDR + LPMD tile kernel's own index, two families with one entry per tile.
+// safe_hi: the largest read index r with cpg_off[r] + 8 <= n_cpgs, searched among the batch's last 256 indices by the
+// first wave of the index kernel (0 if it is not there: every tile then takes the clamped loads).  The tile kernel used to load
+// cpg_off[hi] for this decision: a dependent round trip before its first useful load.
+__device__ __forceinline__ void index_safe_hi(const uint32_t *__restrict__ cpg_off, const uint32_t n_reads, const uint32_t n_cpgs,
+                                              const uint32_t gtid, DevState *__restrict__ st) {
+    uint32_t best = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t back = gtid * 4u + k;
+        if (back <= n_reads) {
+            const uint32_t r = n_reads - back;
+            if ((uint64_t)cpg_off[r] + 8u <= (uint64_t)n_cpgs) best = max(best, r);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
+    if (gtid == 0) st->safe_hi = best;
+}
 template <int NIDX>
 __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict__ read_start,
                                                        uint32_t n_reads, int32_t idx_base, int32_t idx_base2, int qshift,
@@ -53,28 +70,13 @@ __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict
                                                        DevState *__restrict__ st, DevState *__restrict__ cst,
                                                        unsigned long long *__restrict__ bucket_sums, uint32_t n_bucket_words,
                                                        const uint32_t *__restrict__ cpg_off, uint32_t n_cpgs) {
+    static_assert(NIDX == 1, "the tile-granular families are the specialisation's");
     // first kernel of a batch: its rows go after everything emitted so far, and the bucket sums start at zero
     // (nothing else runs between the previous batch's last kernel and this one on the stream)
     const uint32_t gtid = blockIdx.x * BLOCK + threadIdx.x;
     if (gtid == 0 && cst) cst->cur_base = cst->n_sites;      // (pipelined batches: the base travels along the chain of gathers instead)
     for (uint32_t w = gtid; w < n_bucket_words; w += gridDim.x * BLOCK) bucket_sums[w] = 0ull;
-    // safe_hi: the largest read index r with cpg_off[r] + 8 <= n_cpgs, searched among the batch's last 256 indices by the
-    // first wave (0 if it is not there: every tile then takes the clamped loads).  The tile kernel used to load
-    // cpg_off[hi] for this decision: a dependent round trip before its first useful load.
-    if (cpg_off && gtid < 64) {
-        uint32_t best = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) {
-            const uint32_t back = gtid * 4u + k;
-            if (back <= n_reads) {
-                const uint32_t r = n_reads - back;
-                if ((uint64_t)cpg_off[r] + 8u <= (uint64_t)n_cpgs) best = max(best, r);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
-        if (gtid == 0) st->safe_hi = best;
-    }
+    if (cpg_off && gtid < 64) index_safe_hi(cpg_off, n_reads, n_cpgs, gtid, st);
     auto bucket = [&](int32_t s, int32_t base) -> int32_t {  // min(floor((s-base)/Q), nq), -1 below the base
         const int64_t d = (int64_t)s - base;
         return d < 0 ? -1 : (int32_t)min(d >> qshift, (int64_t)nq);
@@ -106,10 +108,10 @@ __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict
     // ---- the fine index (NIDX = 1), usual case: every thread's four reads open at most FAST_SPAN entries between them.  Entry q of
     // (g_prev, g_last] is the first of the four reads whose quantum reaches q: i0 + the number of reads whose quantum lies below q --
     // one loop over the thread's entries, three compares each, 32-bit quantum arithmetic (the values of a valid batch are >= idx_base;
-    // anything below it counts as quantum -1, as in the general form).  A wave where some thread spans more (assembly gaps), and
-    // NIDX = 2, take the general form below.  (Round 5: the general form alone was 85 % vector-unit bound at WGBS depth -- 0.31 ms
+    // anything below it counts as quantum -1, as in the general form).  A wave where some thread spans more (assembly gaps)
+    // takes the general form below.  (Round 5: the general form alone was 85 % vector-unit bound at WGBS depth -- 0.31 ms
     // per pass on config 3, paid by every measure's pass.)
-    if (NIDX == 1 && IDX_GROUPS == 1) {
+    if (IDX_GROUPS == 1) {
         constexpr int FAST_SPAN = 16;
         const uint32_t i0 = gi[0];
         const bool gact = i0 <= n_reads;
@@ -147,32 +149,12 @@ __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict
     for (int u = 0; u < IDX_GROUPS; ++u) {
         const uint32_t i0 = gi[u];
         const bool gact = i0 <= n_reads;
-        if (NIDX == 2) {
-            // sortedness once, on the values alone (the per-family loops below only run where a boundary is crossed)
-            int32_t sprev = sp[u];
-            bool hp = gact && i0 > 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (gact && i0 + k < n_reads) { if (hp && sv[u][k] < sprev) err |= ERRB_UNSORTED; sprev = sv[u][k]; hp = true; }
-            }
-        }
-#pragma unroll
-        for (int w = 0; w < NIDX; ++w) {
-            uint32_t *__restrict__ out = w ? idx2 : idx;
-            const int32_t base = w ? idx_base2 : idx_base;
+        {
+            uint32_t *__restrict__ out = idx;
+            const int32_t base = idx_base;
             int32_t g_prev = -1, s_prev = 0;
             bool have_prev = false;
             if (gact && i0 > 0) { s_prev = sp[u]; g_prev = bucket(s_prev, base); have_prev = true; }
-            if (NIDX == 2) {
-                // tile-granular families: the reads of a wave (256 consecutive ones) cross a boundary of the family in about one
-                // wave out of three on config 2 -- the others are done after two bucket computations per lane
-                int32_t g_last = g_prev;
-                if (gact) {
-                    const uint32_t last = min(i0 + 3u, n_reads);            // the group's last index (n_reads: the sentinel)
-                    g_last = last == n_reads ? (int32_t)nq : bucket(sv[u][last - i0], base);
-                }
-                if (!__any(g_last > g_prev)) continue;
-            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t i = i0 + k;
@@ -182,7 +164,7 @@ __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict
                     if (i < n_reads) {
                         const int32_t s = sv[u][k];
                         g_cur = bucket(s, base);
-                        if (NIDX == 1 && have_prev && s < s_prev) err |= ERRB_UNSORTED;
+                        if (have_prev && s < s_prev) err |= ERRB_UNSORTED;
                         s_prev = s; have_prev = true;
                     } else {
                         g_cur = (int32_t)nq;   // sentinel closes the index
@@ -203,6 +185,95 @@ __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict
         }
     }
     if (err) atomicOr(&st->err, err);
+}
+
+// ---------------------------------------------------------------------------------------------
+// NIDX = 2, the dense PDR + LPMD tile kernel's own index (round 4).  That kernel asks two questions per 4096-bp tile only -- the first
+// read starting at or after T0 - max_span + 1 and the first one starting after T0 + W -- so two families with ONE entry per tile
+// (quantum = tile width, origins region_beg - max_span + 1 and region_beg + 1) answer them exactly: 2 x 14 312 entries instead of
+// 1.83 M on config 2, and the tile's candidate range loses the up to 2 x 31 bp of reads the 32-bp rounding handed it.
+//     idx[q] = the number of reads with read_start < base + q * Q   (q = 0..nq; starts below the base: quantum -1, beyond the end: nq)
+// The reads are sorted, so which entries a wave's IDX2_WAVE_READS consecutive reads open is decided by two values, the element before
+// the wave's first read and the wave's last one: their quanta are computed on the scalar unit, and about two waves in three on config 2
+// are done with that.  A wave that does cross a boundary takes the four quanta of each lane once and then, per entry q it owns,
+//     idx[q] = the wave's first index + sum over the four components of popcount(ballot(quantum < q))
+// on the scalar unit again; the read that entry points at says how many further entries hold the same value (gaps, assembly holes:
+// filled 64 per step by the whole wave).  Per read the kernel issues the sortedness compares and nothing else.  The index that is
+// n_reads (the sentinel) and what lies behind it in its wave count as quantum nq and close both families.
+constexpr int IDX2_WAVE_READS = 256;      // 64 lanes x one 16-byte load.  (Four such chunks per wave, all loads requested first, in a grid a quarter
+                                          // the size: slower beside a tile kernel, 0.0811-0.0846 against 0.0798-0.0811 ms a step; profiles/tile_bounds_and_tabs.md)
+template <>
+__global__ __launch_bounds__(BLOCK) void k_build_index<2>(const int32_t *__restrict__ read_start,
+                                                          uint32_t n_reads, int32_t idx_base, int32_t idx_base2, int qshift,
+                                                          uint32_t nq, int aligned16,
+                                                          uint32_t *__restrict__ idx, uint32_t *__restrict__ idx2,
+                                                          DevState *__restrict__ st, DevState *__restrict__ cst,
+                                                          unsigned long long *__restrict__ bucket_sums, uint32_t n_bucket_words,
+                                                          const uint32_t *__restrict__ cpg_off, uint32_t n_cpgs) {
+    static_assert(IDX2_WAVE_READS == 64 * 4, "one wave, four reads per lane");
+    const uint32_t gtid = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave0 = __builtin_amdgcn_readfirstlane(gtid & ~63u);       // the wave's first thread: wave-uniform decisions below
+    // first kernel of a batch (as in the fine form): the row base, the bucket sums, safe_hi
+    if (wave0 == 0) {
+        if (lane == 0 && cst) cst->cur_base = cst->n_sites;
+        if (cpg_off) index_safe_hi(cpg_off, n_reads, n_cpgs, gtid, st);
+    }
+    if (wave0 < n_bucket_words)
+        for (uint32_t w = gtid; w < n_bucket_words; w += gridDim.x * BLOCK) bucket_sums[w] = 0ull;
+
+    const uint32_t w0 = wave0 * 4u, i0 = w0 + lane * 4u;             // the wave's first read, the lane's
+    if (w0 > n_reads) return;                                        // the sentinel's wave is the last one with work
+    const bool full = w0 + IDX2_WAVE_READS <= n_reads;               // 256 reads
+    // Beyond the batch a component reads as INT32_MAX and the element before index 0 as INT32_MIN: neither ever looks unsorted, and
+    // no validity test is left on the usual path
+    int32_t sv[4] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX}, sp = INT32_MIN;
+    if (full) {
+        if (aligned16) {
+            const int4 x = *reinterpret_cast<const int4 *>(read_start + i0);
+            sv[0] = x.x; sv[1] = x.y; sv[2] = x.z; sv[3] = x.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sv[k] = read_start[i0 + k];
+        }
+        // (the element before the group: the load hits the line the neighbouring lane fetches)
+        if (i0 > 0) sp = read_start[i0 - 1];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (i0 + k < n_reads) sv[k] = read_start[i0 + k];
+        if (i0 > 0 && i0 <= n_reads) sp = read_start[i0 - 1];
+    }
+    const bool unsorted = (sv[0] < sp) | (sv[1] < sv[0]) | (sv[2] < sv[1]) | (sv[3] < sv[2]);
+    const int32_t s_before = __builtin_amdgcn_readfirstlane(sp), s_last = __builtin_amdgcn_readlane(sv[3], 63);
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+        uint32_t *__restrict__ out = f ? idx2 : idx;
+        const int32_t base = f ? idx_base2 : idx_base;
+        // min(floor((s - base) / Q), nq), -1 below the base (s - base fits 32 bits unsigned where s >= base)
+        auto quantum = [&](const int32_t s) -> int32_t { return s < base ? -1 : (int32_t)min(((uint32_t)s - (uint32_t)base) >> qshift, nq); };
+        const int32_t q_before = w0 == 0 ? -1 : quantum(s_before);
+        const int32_t q_last = full ? quantum(s_last) : (int32_t)nq;
+        if (q_last <= q_before) continue;
+        // this wave owns the entries (q_before, q_last]
+        int32_t g[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = (full || i0 + k < n_reads) ? quantum(sv[k]) : (int32_t)nq;
+        for (int32_t q = q_before + 1; q <= q_last;) {
+            const uint32_t below = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__popcll(__ballot(g[0] < q)) + __popcll(__ballot(g[1] < q)) +
+                                                                                   __popcll(__ballot(g[2] < q)) + __popcll(__ballot(g[3] < q))));
+            // the read entry q points at is the wave's first with a quantum >= q; the entries up to that quantum point at it too.
+            // (An unsorted batch is an error: the clamps keep its stores inside (q_before, q_last] and the walk moving.)
+            const uint32_t at = min(below, (uint32_t)IDX2_WAVE_READS - 1u);
+            const int l = (int)(at >> 2);
+            const int32_t m0 = __builtin_amdgcn_readlane(g[0], l), m1 = __builtin_amdgcn_readlane(g[1], l);
+            const int32_t m2 = __builtin_amdgcn_readlane(g[2], l), m3 = __builtin_amdgcn_readlane(g[3], l);
+            const int32_t m = min(max((at & 2u) ? ((at & 1u) ? m3 : m2) : ((at & 1u) ? m1 : m0), q), q_last);
+            const uint32_t entry = w0 + below;
+            for (int32_t x = q + (int32_t)lane; x <= m; x += 64) out[x] = entry;
+            q = m + 1;
+        }
+    }
+    if (unsorted) atomicOr(&st->err, ERRB_UNSORTED);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1618,7 +1689,8 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
 
     // The dense tile kernel's own index: one entry per tile in each of two families (k_build_index<2>).  Site discovery for the walk
     // measures (sink) leaves the fine index behind for them; the wide form looks up arbitrary stretch bounds.  MTH_COARSE_INDEX=0: A/B.
-    static const bool coarse_off = getenv("MTH_COARSE_INDEX") && atoi(getenv("MTH_COARSE_INDEX")) == 0;
+    const char *coarse_env = getenv("MTH_COARSE_INDEX");     // (read per call: the tests run both indices in one process)
+    const bool coarse_off = coarse_env && atoi(coarse_env) == 0;
     // a prepared batch brings its fine index: no index kernel in this call (k_batch_begin does what else that kernel did)
     Prepared *prep = ctx->cur_prep;
     if (prep && !(prep->idx_base == idx_base && nq <= prep->nq)) prep = nullptr;
