@@ -48,7 +48,7 @@ enum {
     MTH_ERR_UNSORTED = -4,  /* reads of a batch are not sorted by start */
     MTH_ERR_SPAN = -5,      /* a read spans more than batch.max_span */
     MTH_ERR_REOPEN = -6,    /* reserved (was: flush re-open semantics not implemented; they are now) */
-    MTH_ERR_RANGE = -7,     /* a CpG of an owned site lies outside what the batch declared */
+    MTH_ERR_RANGE = -7,     /* a CpG of an owned site lies outside what the batch declared: a batch carries the word of position -1 */
     MTH_ERR_CAPACITY = -8,  /* an on-chip capacity was exceeded */
     MTH_ERR_STATE = -9,     /* call order violated */
     MTH_ERR_FORMAT = -10,   /* device decode: corrupt BGZF block, malformed BAM record, or a record without XM:Z */
@@ -56,6 +56,9 @@ enum {
                                its rounds do not settle or the carry is too large: decode via the host walk instead) */
     MTH_ERR_RCCL = -12      /* librccl could not be loaded, or an RCCL call failed (mth_last_error has the text) */
 };
+/* Several data errors pending at one synchronising call: one is reported, in the order UNSORTED, RANGE, SPAN, CAPACITY, FORMAT, UNALIGNED.
+ * RANGE comes before SPAN: the word of position -1 in a batch also reads as a call 2^31 positions past its read to some tile kernels.  A
+ * file-order run over a stream that holds both a contig-less record with calls and a span violation therefore reports RANGE. */
 
 enum { MTH_MEM_HOST = 0, MTH_MEM_DEVICE = 1, MTH_MEM_PREPARED = 2 /* only in batches made by mth_batch_prepare */ };
 
@@ -73,6 +76,15 @@ enum { MTH_MEM_HOST = 0, MTH_MEM_DEVICE = 1, MTH_MEM_PREPARED = 2 /* only in bat
  *   cpg_off[n_reads+1]   CSR offsets into the per-call arrays
  * Per CpG call (readutil.rs:247-251), in query order:
  *   cpg_pos              abspos (31 bits) | methylated << 31
+ *                        Position -1 -- a record at position 0 whose flag is outside {0,99,147} calling on its first aligned base reports
+ *                        abspos - 1 (readutil.rs:338), and the reference keeps -1 as an ordinary i32 key, first of its contig -- has no
+ *                        word of its own in 31 bits.  The decoders write it as 0x7fffffff (no contig has a position 2^31 - 1).  A BATCH
+ *                        must not carry that word: such a contig goes in as a contig group (below), shifted by a voff >= 1, where the
+ *                        call lies at voff - 1 and every fetch returns it as position -1, first row of its contig.  mth_decoded_group /
+ *                        _each do that for a decoded stream.  A batch that does carry the word is refused with MTH_ERR_RANGE (found by
+ *                        the read index build -- by a small launch of its own in the run form MTH_TILE_RUNS=1, which builds no index --, on a
+ *                        read that starts at 0, as its first call; a host batch before anything is copied).  mth_fileorder_run takes the word as it
+ *                        is and orders it before position 0.
  *   cpg_rel              relpos = query offset of the call (u8; use cpg_rel16 when reads > 255 bp)
  */
 typedef struct {
@@ -218,7 +230,8 @@ int  mth_lpmd_pairs_fetch(mth_ctx_t *ctx, uint64_t *n_rows, int32_t *tid, int32_
  * the group is accumulated as ONE batch whose `tid` is the group's handle (<= -2).  No measure looks at a tid: the reference's
  * per-contig behaviour -- a record on a later contig flushes every earlier site (is_before(), readutil.rs:304-310) -- is what a larger
  * virtual position does too.  Every fetch maps a grouped batch's rows back: (handle, virtual position) -> (tids[k], position - voff[k])
- * with k the last contig whose voff is <= the (first) position of the row; row order stays the (tid, pos) order when tids ascend.
+ * with k the last contig whose voff is <= the (first) position of the row + 1 (a contig's call at position -1 lies at voff - 1 and comes
+ * back as -1); row order stays the (tid, pos) order when tids ascend.
  * The reservoir draw of FDRP / qFDRP (keyed by tid and position) is made on the mapped-back site.
  * voff: ascending, voff[0] >= 0, voff[k + 1] >= voff[k] + contig k's extent + max_span + 152 + 202 (checked only for order), all
  * virtual positions below 2^31 - 1.  mth_group_clear forgets all groups (results fetched afterwards would keep their handles).
@@ -423,9 +436,18 @@ int  mth_decoded_contigs(mth_ctx_t *ctx, uint32_t cap, int32_t *tids, uint64_t *
  * values) and the groups are registered.  Returns per group g < *n_groups: the contigs [first_contig[g], first_contig[g + 1]) and
  * batch_tid[g] = the group's handle, or the contig's own tid for a group of one; the caller batches a group with
  * mth_decoded_batch(ctx, read_beg[first_contig[g]], read_end[first_contig[g + 1] - 1], batch_tid[g], 0, -1, &b).
- * *n_groups = 0: nothing was changed (tids not ascending, a call at position -1, or a previous grouping in place). */
+ * When some contig holds a call at position -1 (the word 0x7fffffff, see mth_batch_t), every group starts at virtual position
+ * MTH_GROUP_MINUS_ONE_BASE instead of 0 and a group of one contig is registered (and shifted) like any other: no batch carries the word.
+ * *n_groups = 0: nothing was changed (tids not ascending, a read without an aligned base, a previous grouping in place, or nothing to
+ * merge and no call at -1).
+ * mth_decoded_group_each: the same with ONE contig per group -- only the contigs that hold a call at -1 are shifted (by
+ * MTH_GROUP_MINUS_ONE_BASE: batch_tid[g] is a handle, and a region of such a contig is given in shifted positions, from BASE - 1 to own
+ * the site at -1); the others come back under their own tid, untouched.  For callers that batch per contig or per region. */
+#define MTH_GROUP_MINUS_ONE_BASE 4096
 int  mth_decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, const uint64_t *read_beg, const uint64_t *read_end,
                        uint32_t *n_groups, uint32_t *first_contig /* [n_contigs + 1] */, int32_t *batch_tid /* [n_contigs] */);
+int  mth_decoded_group_each(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, const uint64_t *read_beg, const uint64_t *read_end,
+                            uint32_t *n_groups, uint32_t *first_contig /* [n_contigs + 1] */, int32_t *batch_tid /* [n_contigs] */);
 /* re-order the decoded stream by (tid, start), stably, on the device -- for the measures whose result does not depend on the
  * record order (lpmd.rs:175-200, me.rs:106-125, pm.rs:101-121): an input that is not coordinate-sorted or not grouped by contig
  * can then be batched like a sorted one.  Every record must have a contig and an aligned base (flags bit0 / bit1 clear). */

@@ -32,7 +32,10 @@ def group_device_batches(engines, batches, lengths, max_span=150, vmax=(1 << 31)
     "contig groups"): contigs packed greedily into virtual coordinate spaces of at most `vmax` positions, offsets a multiple of 4096
     with a gap of max_span + 1024 after every contig -- what mth_decoded_group does to a decoded stream, done here with torch for
     batches that never were one.  The groups are defined on every engine of `engines` (same order: same handles).  Returns the
-    Batches (a group of one contig stays the contig's own Batch)."""
+    Batches (a group of one contig stays the contig's own Batch).
+    Calls at position -1 (the word 0x7fffffff, include/metheor_hip.h): the 31-bit sum below puts such a call at voff - 1, as k_grp_shift
+    does, for every contig at an offset above 0; groups start at offset 0 here, so a group's FIRST contig (or a group of one) that holds
+    the word keeps it and the engine refuses the batch with MTH_ERR_RANGE -- mth_decoded_group is the path that lifts such contigs."""
     import torch
     groups, cur, vlen = [], [], 0
     for b, ln in zip(batches, lengths):
@@ -54,7 +57,7 @@ def group_device_batches(engines, batches, lengths, max_span=150, vmax=(1 << 31)
             o = k[3].to(torch.int64) & 0xffffffff
             off.append(o[:-1] + base); base += int(o[-1].item())
             p = k[4].to(torch.int64) & 0xffffffff
-            pos.append(((p & 0x7fffffff) + vo) | (p & 0x80000000))
+            pos.append(((p + vo) & 0x7fffffff) | (p & 0x80000000))
             rel.append(k[5])
         off.append(torch.tensor([base], device=rs[0].device, dtype=torch.int64))
         as_i32 = lambda x: torch.where(x >= (1 << 31), x - (1 << 32), x).to(torch.int32).contiguous()       # u32 bit patterns in an int32 tensor

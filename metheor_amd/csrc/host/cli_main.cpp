@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <sys/stat.h>
 #include <thread>
@@ -288,6 +289,10 @@ struct Contig {
     std::vector<uint8_t> o_mapq;
     std::vector<uint32_t> o_pos;
     std::vector<uint16_t> o_rel;
+    // host-decoded input: the contig holds a call at position -1 and was shifted up by MTH_GROUP_MINUS_ONE_BASE (the o_ copies); it goes
+    // in as a contig group of one, defined by load() on the context the batches go to
+    bool lifted = false;
+    int32_t group = 0;
 };
 
 struct Input {
@@ -650,21 +655,31 @@ bool batch_decoded(Input &in, const std::vector<int32_t> &tids, const std::vecto
     // has 24 to a few thousand contigs.  The library shifts the decoded positions into one virtual coordinate space per group and maps
     // the rows back at the fetch, so nothing below this line knows.  Not under a shard / region plan (those own parts of contigs);
     // METHEOR_GROUP=0 keeps one batch per contig (A/B, tests).
-    if (!g_shard.planned() && in.contigs.size() > 1 && !(getenv("METHEOR_GROUP") && atoi(getenv("METHEOR_GROUP")) == 0)) {
-        Phase pg("  contig groups");
+    // A contig that holds a call at position -1 (a record at 0 under a shifted flag calling on its first base) is shifted too, also when
+    // it is the only one, under METHEOR_GROUP=0 and under a region plan: one group per contig then (mth_decoded_group_each), which leaves
+    // every other contig as it is.
+    const bool merge = !g_shard.planned() && in.contigs.size() > 1 && !(getenv("METHEOR_GROUP") && atoi(getenv("METHEOR_GROUP")) == 0);
+    if (!in.contigs.empty()) {
+        std::unique_ptr<Phase> pg(merge ? new Phase("  contig groups") : nullptr);
         const uint32_t nc = (uint32_t)in.contigs.size();
         std::vector<int32_t> gt(nc), bt(nc);
         std::vector<uint64_t> gb(nc), ge(nc);
         std::vector<uint32_t> first((size_t)nc + 1);
         for (uint32_t k = 0; k < nc; ++k) { gt[k] = in.contigs[k].tid; gb[k] = in.contigs[k].r0; ge[k] = in.contigs[k].r1; }
         uint32_t ng = 0;
-        check(in.ctx, mth_decoded_group(in.ctx, nc, gt.data(), gb.data(), ge.data(), &ng, first.data(), bt.data()));
+        check(in.ctx, (merge ? mth_decoded_group : mth_decoded_group_each)(in.ctx, nc, gt.data(), gb.data(), ge.data(), &ng, first.data(), bt.data()));
         if (ng) {
             std::vector<Contig> grouped((size_t)ng);
             for (uint32_t g = 0; g < ng; ++g) {
                 Contig &c = grouped[g];
                 c.tid = bt[g]; c.r0 = gb[first[g]]; c.r1 = ge[first[g + 1] - 1]; c.n_reads = (size_t)(c.r1 - c.r0); c.n_cpgs = 0;
                 c.region_beg = 0; c.region_end = -1;
+                if (!merge) {     // one contig each: its region stays, in shifted positions where the contig was shifted (from BASE - 1: the site at -1)
+                    const Contig &o = in.contigs[first[g]];
+                    const int32_t up = bt[g] <= -2 ? MTH_GROUP_MINUS_ONE_BASE : 0;
+                    c.region_beg = o.region_beg + up - (up && o.region_beg == 0 ? 1 : 0);
+                    c.region_end = o.region_end < 0 ? -1 : (int32_t)std::min<int64_t>((int64_t)o.region_end + up, INT32_MAX);
+                }
             }
             in.contigs.swap(grouped);
         }
@@ -697,7 +712,8 @@ bool reads_in_order(const int32_t *tid, const int32_t *st, int64_t n) {
     return true;
 }
 
-Input load(const std::string &path, const char *cpg_set, bool host_only = false) {
+// group_ctx: the context the batches of a host-only load go to, when the caller has one already (`all`)
+Input load(const std::string &path, const char *cpg_set, bool host_only = false, mth_ctx_t *group_ctx = nullptr) {
     Phase ph_all("load: open+decode+batch");
     Input in;
     char err[1024];
@@ -784,7 +800,28 @@ Input load(const std::string &path, const char *cpg_set, bool host_only = false)
             c.start = c.o_start.data(); c.end = c.o_end.data(); c.mapq = c.o_mapq.data(); c.pos = c.o_pos.data(); c.rel = c.o_rel.data();
             c.n_reads = c.o_start.size(); c.n_cpgs = c.o_pos.size();
         }
+        // a call at position -1 (the word 0x7fffffff; the first call of a read at 0): no batch may carry it -- the contig is copied
+        // MTH_GROUP_MINUS_ONE_BASE positions up and goes in as a contig group of one (make_batch), the fetch maps its rows back
+        for (size_t r = 0; r < c.n_reads && c.start[r] == 0 && !c.lifted; ++r)
+            c.lifted = c.off[r + 1] > c.off[r] && (c.pos[c.off[r]] & 0x7fffffffu) == 0x7fffffffu;
+        if (c.lifted) {
+            if (c.o_start.empty()) {
+                c.o_start.assign(c.start, c.start + c.n_reads); c.o_end.assign(c.end, c.end + c.n_reads); c.o_mapq.assign(c.mapq, c.mapq + c.n_reads);
+                c.o_pos.assign(c.pos, c.pos + c.n_cpgs); c.o_rel.assign(c.rel, c.rel + c.n_cpgs);
+            }
+            for (int32_t &v : c.o_start) v += MTH_GROUP_MINUS_ONE_BASE;
+            for (int32_t &v : c.o_end) v += MTH_GROUP_MINUS_ONE_BASE;
+            for (uint32_t &w : c.o_pos) w = ((w + (uint32_t)MTH_GROUP_MINUS_ONE_BASE) & 0x7fffffffu) | (w & 0x80000000u);
+            c.start = c.o_start.data(); c.end = c.o_end.data(); c.mapq = c.o_mapq.data(); c.pos = c.o_pos.data(); c.rel = c.o_rel.data();
+            c.max_end += MTH_GROUP_MINUS_ONE_BASE;
+        }
         i = e;
+    }
+    for (Contig &c : in.contigs) {
+        if (!c.lifted) continue;
+        if (!in.ctx) in.ctx = group_ctx ? group_ctx : make_ctx();
+        const int64_t voff = MTH_GROUP_MINUS_ONE_BASE;
+        check(in.ctx, mth_group_define(in.ctx, 1, &c.tid, &voff, &c.group));
     }
     return in;
 }
@@ -800,7 +837,7 @@ mth_batch_t make_batch(const Input &in, const Contig &c) {
             die("an alignment spans " + std::to_string(b.max_span) + " bp: set METHEOR_SHARD_HALO to at least " + std::to_string(b.max_span + 202));
         return b;
     }
-    b.tid = c.tid;
+    b.tid = c.lifted ? c.group : c.tid;
     b.region_beg = 0;
     b.region_end = (int32_t)std::min<int64_t>((int64_t)c.max_end + 2, INT32_MAX);      // to the end of the data, not the header's LN
     b.max_span = c.max_span;
@@ -1245,7 +1282,7 @@ int run_all(const Args &a) {
                 die("metheor (MI355X path): the decoded stream could not be batched after the device sort");
         } else {
             g_shard.order_free = true;
-            host_in = load(input, cpg_set, true);
+            host_in = load(input, cpg_set, true, ctx);
             bin = &host_in;
         }
         mp.want = (w_lpmd ? MTH_MULTI_LPMD : 0u) | ((w_me || w_pm) ? MTH_MULTI_QUARTET : 0u) | (w_pairs ? MTH_MULTI_PAIRS : 0u);

@@ -135,7 +135,8 @@ int ungroup_rows(mth_ctx *ctx, uint64_t n, int32_t *tid, int32_t *pos_a, int str
         if (gi >= ctx->groups.size()) return fail(ctx, MTH_ERR_STATE, "a result row carries the handle of a contig group that is not defined (any more)");
         const mth_ctx::ContigGroup &g = ctx->groups[gi];
         const int64_t v = pos_a[i * (uint64_t)stride];
-        const size_t k = (size_t)(std::upper_bound(g.voff.begin(), g.voff.end(), v) - g.voff.begin());
+        // (v + 1: a contig's call at position -1 lies at voff - 1, in the gap nothing else of the group reaches)
+        const size_t k = (size_t)(std::upper_bound(g.voff.begin(), g.voff.end(), v + 1) - g.voff.begin());
         if (k == 0) return fail(ctx, MTH_ERR_STATE, "a grouped batch's row lies before the group's first contig");
         const int32_t off = (int32_t)g.voff[k - 1];
         tid[i] = g.tids[k - 1];
@@ -152,8 +153,9 @@ int sync_and_check(mth_ctx *ctx) {
     const uint32_t e = ctx->h_state->err;
     ctx->notes |= ctx->h_state->pad_;          // non-fatal findings of the device decode (sticky on the host: mth_reset clears the device word)
     if (e & ERRB_UNSORTED) return fail(ctx, MTH_ERR_UNSORTED, "reads of a batch are not sorted by start position");
+    // (before the span: the word of position -1 in a batch reads as a call 2^31 positions past its read to the tile kernels)
+    if (e & ERRB_RANGE) return fail(ctx, MTH_ERR_RANGE, "CpG position outside the declared range (a batch carries the word of position -1: such a contig goes in as a contig group, or a record without a contig carries calls)");
     if (e & ERRB_SPAN) return fail(ctx, MTH_ERR_SPAN, "a read spans more reference bases than batch.max_span");
-    if (e & ERRB_RANGE) return fail(ctx, MTH_ERR_RANGE, "CpG position outside the declared range");
     if (e & ERRB_CAPACITY) return fail(ctx, MTH_ERR_CAPACITY, "capacity exceeded (a read with more than 16384 CpGs in MHL, or FDRP max_depth above 16384)");
     if (e & ERRB_CRC) return fail(ctx, MTH_ERR_FORMAT, "corrupt BGZF block (CRC32 mismatch)");
     if (e & ERRB_FORMAT) return fail(ctx, MTH_ERR_FORMAT, "corrupt BGZF block or malformed BAM record (DEFLATE / ISIZE / block_size / field lengths inconsistent)");
@@ -188,6 +190,16 @@ void prepared_free(mth_ctx *ctx, Prepared *pr) {
     delete pr;
 }
 
+// a HOST batch that carries the word of position -1 (include/metheor_hip.h, mth_batch_t.cpg_pos: the first call of a read that starts at
+// 0) is refused here, before anything is copied or launched; a device-resident one by the read index build (index_minus_one)
+bool host_batch_minus_one(const mth_batch_t &b) {
+    if (b.mem != MTH_MEM_HOST || !b.n_cpgs || !b.read_start || !b.cpg_off || !b.cpg_pos) return false;
+    for (uint32_t r = 0; r < b.n_reads && b.read_start[r] <= 0; ++r)
+        if (b.read_start[r] == 0 && b.cpg_off[r + 1] > b.cpg_off[r] && b.cpg_off[r] < b.n_cpgs && (b.cpg_pos[b.cpg_off[r]] & 0x7fffffffu) == 0x7fffffffu) return true;
+    return false;
+}
+static const char *kMinusOneMsg = "CpG position outside the declared range (the batch carries the word of position -1: such a contig goes in as a contig group)";
+
 int stage_batch(mth_ctx *ctx, const mth_batch_t &b, mth_batch_t &d, bool join) {
     if (b.region_end < b.region_beg || b.max_span < 0) return fail(ctx, MTH_ERR_INVALID, "bad region / max_span");
     // a contig group's handle must be defined -- checked here, before any accumulate entry point has recorded anything of the batch
@@ -212,6 +224,7 @@ int stage_batch(mth_ctx *ctx, const mth_batch_t &b, mth_batch_t &d, bool join) {
         return fail(ctx, MTH_ERR_INVALID, "batch arrays missing");
     if (b.n_cpgs && (!b.cpg_pos || (!b.cpg_rel == !b.cpg_rel16)))
         return fail(ctx, MTH_ERR_INVALID, "exactly one of cpg_rel / cpg_rel16 must be given");
+    if (host_batch_minus_one(b)) return fail(ctx, MTH_ERR_RANGE, kMinusOneMsg);
     if (join || b.mem == MTH_MEM_HOST) MTH_ENTER(ctx);      // (host batches: the single set of staging buffers is reused -> always joined)
     else MTH_HIP(ctx, hipSetDevice(ctx->device));
     d = b;
@@ -372,6 +385,7 @@ int mth_batch_prepare(mth_ctx_t *ctx, const mth_batch_t *batch, mth_batch_t *pre
     if (b.n_reads && (!b.read_start || !b.read_end || !b.read_mapq || !b.cpg_off)) return mth::fail(ctx, MTH_ERR_INVALID, "batch arrays missing");
     if (b.n_cpgs && (!b.cpg_pos || (!b.cpg_rel == !b.cpg_rel16))) return mth::fail(ctx, MTH_ERR_INVALID, "exactly one of cpg_rel / cpg_rel16 must be given");
     if (b.mem != MTH_MEM_HOST && b.mem != MTH_MEM_DEVICE) return mth::fail(ctx, MTH_ERR_INVALID, "batch.mem");
+    if (mth::host_batch_minus_one(b)) return mth::fail(ctx, MTH_ERR_RANGE, mth::kMinusOneMsg);
     std::unique_ptr<mth::Prepared> pr(new mth::Prepared());
     auto drop = [&]() { for (mth::DevBuf &x : pr->own) x.release(); pr->idx.release(); if (pr->st) (void)hipFree(pr->st); };
 #define PREP_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { drop(); return mth::fail(ctx, MTH_ERR_HIP, #call, e__); } } while (0)

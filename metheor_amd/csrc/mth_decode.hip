@@ -260,12 +260,13 @@ __device__ __forceinline__ uint32_t grp_run_of(const unsigned long long *__restr
     return lo;
 }
 
-// ext[k] = last covered position + 1 over run k's reads; st[0] = widest read, st[1] = calls at position -1 (a reverse read at 0:
-// not representable once shifted) + reads without an aligned base
+// ext[k] = last covered position + 1 over run k's reads; neg[k] != 0: run k holds a call at position -1 (the word 0x7fffffff: a record at
+// position 0 under a shifted flag calling on its first base, readutil.rs:338 -- its first call); st[0] = widest read, st[1] = reads
+// without an aligned base
 __global__ __launch_bounds__(256) void k_grp_extent(const int32_t *__restrict__ start, const int32_t *__restrict__ end,
                                                     const unsigned long long *__restrict__ off, const uint32_t *__restrict__ pos,
                                                     unsigned long long r0, unsigned long long n, const unsigned long long *__restrict__ run_beg,
-                                                    uint32_t n_runs, uint32_t *__restrict__ ext, uint32_t *__restrict__ st) {
+                                                    uint32_t n_runs, uint32_t *__restrict__ ext, uint32_t *__restrict__ neg, uint32_t *__restrict__ st) {
     for (unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (unsigned long long)gridDim.x * 256) {
         const unsigned long long i = r0 + t;
         const int32_t s = start[i], e = end[i];
@@ -274,9 +275,7 @@ __global__ __launch_bounds__(256) void k_grp_extent(const int32_t *__restrict__ 
         // (sorted reads: a wave's ends are close to each other -- the maximum rarely moves, so most atomics are skipped)
         if ((uint32_t)e + 1u > ext[k]) atomicMax(&ext[k], (uint32_t)e + 1u);
         if ((uint32_t)(e - s + 1) > st[0]) atomicMax(&st[0], (uint32_t)(e - s + 1));
-        if (s == 0)
-            for (unsigned long long c = off[i]; c < off[i + 1]; ++c)
-                if ((pos[c] & 0x7fffffffu) == 0x7fffffffu) atomicAdd(&st[1], 1u);
+        if (s == 0 && off[i + 1] > off[i] && (pos[off[i]] & 0x7fffffffu) == 0x7fffffffu) neg[k] = 1u;
     }
 }
 
@@ -295,7 +294,8 @@ __global__ __launch_bounds__(256) void k_grp_shift(int32_t *__restrict__ start, 
         const int32_t v = run_voff[grp_run_of(run_beg, n_runs, i)];
         if (!v) continue;
         start[i] += v; end[i] += v;
-        for (unsigned long long c = off[i]; c < off[i + 1]; ++c) { const uint32_t w = pos[c]; pos[c] = ((w & 0x7fffffffu) + (uint32_t)v) | (w & 0x80000000u); }
+        // (31-bit sum: the word 0x7fffffff, position -1, lands on v - 1 and leaves the state bit alone)
+        for (unsigned long long c = off[i]; c < off[i + 1]; ++c) { const uint32_t w = pos[c]; pos[c] = ((w + (uint32_t)v) & 0x7fffffffu) | (w & 0x80000000u); }
     }
 }
 
@@ -577,11 +577,12 @@ int mth_decoded_fetch(mth_ctx_t *ctx, int32_t *tid, int32_t *start, int32_t *end
     return MTH_OK;
 }
 
-int mth_decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, const uint64_t *read_beg, const uint64_t *read_end,
-                      uint32_t *n_groups, uint32_t *first_contig, int32_t *batch_tid) {
+// each: one group per contig (mth_decoded_group_each)
+static int decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, const uint64_t *read_beg, const uint64_t *read_end,
+                         uint32_t *n_groups, uint32_t *first_contig, int32_t *batch_tid, bool each) {
     if (!ctx || !n_groups || (n_contigs && (!tids || !read_beg || !read_end || !first_contig || !batch_tid))) return MTH_ERR_INVALID;
     *n_groups = 0;
-    if (n_contigs < 2 || ctx->dec_grouped || ctx->dec_contig_flags) return MTH_OK;
+    if (n_contigs < 1 || ctx->dec_grouped || ctx->dec_contig_flags) return MTH_OK;
     for (uint32_t k = 0; k < n_contigs; ++k) {
         if (tids[k] < 0 || read_end[k] < read_beg[k] || read_end[k] > ctx->dec_reads) return MTH_ERR_INVALID;
         if (k && (tids[k] <= tids[k - 1] || read_beg[k] != read_end[k - 1])) return MTH_OK;        // not one ascending, gap-free sequence of runs
@@ -591,30 +592,37 @@ int mth_decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, c
     const uint64_t r0 = read_beg[0], n = read_end[n_contigs - 1] - r0;
     if (n == 0) return MTH_OK;
     // device: the runs' first reads, their extents, two status words, later their offsets
-    MTH_HIP(ctx, ctx->dec_runs.reserve(((size_t)n_contigs + 1) * 16 + (size_t)n_contigs * 8 + 64, s));
+    MTH_HIP(ctx, ctx->dec_runs.reserve(((size_t)n_contigs + 1) * 16 + (size_t)n_contigs * 12 + 64, s));
     uint8_t *base = static_cast<uint8_t *>(ctx->dec_runs.p);
     unsigned long long *d_beg = reinterpret_cast<unsigned long long *>(base);          // n_contigs + 1 entries: the runs' first reads, then the end
     unsigned long long *d_coff = d_beg + n_contigs + 1;                                // the call offsets there
     uint32_t *d_ext = reinterpret_cast<uint32_t *>(d_coff + n_contigs + 1);
     int32_t *d_voff = reinterpret_cast<int32_t *>(d_ext + n_contigs);
-    uint32_t *d_st = reinterpret_cast<uint32_t *>(d_voff + n_contigs);
+    uint32_t *d_neg = reinterpret_cast<uint32_t *>(d_voff + n_contigs);
+    uint32_t *d_st = d_neg + n_contigs;
     std::vector<unsigned long long> hb(read_beg, read_beg + n_contigs);
     hb.push_back(read_end[n_contigs - 1]);
     MTH_HIP(ctx, hipMemcpyAsync(d_beg, hb.data(), ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, s));
-    MTH_HIP(ctx, hipMemsetAsync(d_ext, 0, (size_t)n_contigs * 8 + 16, s));
+    MTH_HIP(ctx, hipMemsetAsync(d_ext, 0, (size_t)n_contigs * 12 + 16, s));
     hipLaunchKernelGGL(k_grp_pick, dim3((n_contigs + 1 + 255) / 256), dim3(256), 0, s, ctx->dec_off.as<unsigned long long>(), d_beg, n_contigs + 1, d_coff);
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(k_grp_extent, dim3(grid), dim3(256), 0, s, ctx->dec_start.as<int32_t>(), ctx->dec_end.as<int32_t>(),
                        ctx->dec_off.as<unsigned long long>(), ctx->dec_pos.as<uint32_t>(), (unsigned long long)r0, (unsigned long long)n,
-                       d_beg, n_contigs, d_ext, d_st);
-    std::vector<uint32_t> ext(n_contigs);
+                       d_beg, n_contigs, d_ext, d_neg, d_st);
+    std::vector<uint32_t> ext(n_contigs), neg(n_contigs);
     uint32_t st[2] = {0, 0};
     std::vector<unsigned long long> coff((size_t)n_contigs + 1);
     MTH_HIP(ctx, hipMemcpyAsync(ext.data(), d_ext, (size_t)n_contigs * 4, hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipMemcpyAsync(neg.data(), d_neg, (size_t)n_contigs * 4, hipMemcpyDeviceToHost, s));
     MTH_HIP(ctx, hipMemcpyAsync(st, d_st, 8, hipMemcpyDeviceToHost, s));
     MTH_HIP(ctx, hipMemcpyAsync(coff.data(), d_coff, ((size_t)n_contigs + 1) * 8, hipMemcpyDeviceToHost, s));
     MTH_HIP(ctx, hipStreamSynchronize(s));
-    if (st[1]) return MTH_OK;                                  // a call at -1 / a read without an aligned base: leave the stream as it is
+    if (st[1]) return MTH_OK;                                  // a read without an aligned base: leave the stream as it is
+    // A call at position -1 has no word of its own in 31 bits: a contig that holds one never lies at offset 0 -- a group that holds such a
+    // contig starts MTH_GROUP_MINUS_ONE_BASE positions up, so the call lands on voff - 1, inside the gap below its contig (the fetch's
+    // look-up takes voff - 1 for the contig at voff); a lone such contig becomes a group of one
+    bool any_neg = false;
+    for (uint32_t k = 0; k < n_contigs; ++k) any_neg |= neg[k] != 0;
     // The gap after a contig: wider than anything a measure looks across -- a read's span, PDR's flush margin (pdr.rs:162: 150), the
     // FDRP window (fdrp.rs:10: 201) and the index quanta -- and a multiple of the dense tile width.
     const int64_t gap = (int64_t)st[0] + 1024;
@@ -634,11 +642,14 @@ int mth_decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, c
     for (uint32_t k = 0; k < n_contigs; ++k) {
         const int64_t e = (((int64_t)ext[k] + gap + 4095) / 4096) * 4096;
         const uint64_t kr = read_end[k] - read_beg[k], kc = coff[k + 1] - coff[k];
-        if (first.empty() || vlen + e > vmax || g_reads + kr >= (1ull << 32) - 1 || g_calls + kc >= (1ull << 32)) { first.push_back(k); vlen = 0; g_reads = g_calls = 0; }
+        if (first.empty() || each || vlen + e > vmax || g_reads + kr >= (1ull << 32) - 1 || g_calls + kc >= (1ull << 32)) {
+            first.push_back(k); g_reads = g_calls = 0;
+            vlen = (each ? neg[k] != 0 : any_neg) ? MTH_GROUP_MINUS_ONE_BASE : 0;
+        }
         voff[k] = (int32_t)vlen;
         vlen += e; g_reads += kr; g_calls += kc;
     }
-    if (first.size() == n_contigs) return MTH_OK;              // nothing to merge
+    if (first.size() == n_contigs && !any_neg) return MTH_OK;  // nothing to merge, nothing to lift
     MTH_HIP(ctx, hipMemcpyAsync(d_voff, voff.data(), (size_t)n_contigs * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_grp_shift, dim3(grid), dim3(256), 0, s, ctx->dec_start.as<int32_t>(), ctx->dec_end.as<int32_t>(),
                        ctx->dec_off.as<unsigned long long>(), ctx->dec_pos.as<uint32_t>(), (unsigned long long)r0, (unsigned long long)n,
@@ -650,7 +661,7 @@ int mth_decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, c
     for (size_t g = 0; g + 1 < first.size(); ++g) {
         const uint32_t k0 = first[g], k1 = first[g + 1];
         first_contig[g] = k0;
-        if (k1 - k0 == 1) { batch_tid[g] = tids[k0]; continue; }
+        if (k1 - k0 == 1 && voff[k0] == 0) { batch_tid[g] = tids[k0]; continue; }
         std::vector<int64_t> vo(voff.begin() + k0, voff.begin() + k1);
         const int rc = mth_group_define(ctx, k1 - k0, tids + k0, vo.data(), &batch_tid[g]);
         if (rc) return rc;
@@ -658,6 +669,16 @@ int mth_decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, c
     first_contig[first.size() - 1] = n_contigs;
     *n_groups = (uint32_t)first.size() - 1;
     return MTH_OK;
+}
+
+int mth_decoded_group(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, const uint64_t *read_beg, const uint64_t *read_end,
+                      uint32_t *n_groups, uint32_t *first_contig, int32_t *batch_tid) {
+    return decoded_group(ctx, n_contigs, tids, read_beg, read_end, n_groups, first_contig, batch_tid, false);
+}
+
+int mth_decoded_group_each(mth_ctx_t *ctx, uint32_t n_contigs, const int32_t *tids, const uint64_t *read_beg, const uint64_t *read_end,
+                           uint32_t *n_groups, uint32_t *first_contig, int32_t *batch_tid) {
+    return decoded_group(ctx, n_contigs, tids, read_beg, read_end, n_groups, first_contig, batch_tid, true);
 }
 
 int mth_decoded_batch(mth_ctx_t *ctx, uint64_t read_beg, uint64_t read_end, int32_t tid, int32_t region_beg, int32_t region_end,

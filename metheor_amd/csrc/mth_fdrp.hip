@@ -95,8 +95,8 @@ __device__ __forceinline__ int32_t sample_j(unsigned long long seed, int32_t tid
 // the reservoir draw of site c of the batch: on the site's own contig and position when the batch is a contig group
 __device__ __forceinline__ int32_t sample_site(const int32_t *__restrict__ grp_tab, uint32_t grp_n, unsigned long long seed, int32_t tid, int32_t c, int32_t total) {
     if (grp_tab) {
-        uint32_t lo = 0, hi = grp_n;                              // last contig whose offset is <= c
-        while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (grp_tab[mid] <= c) lo = mid; else hi = mid; }
+        uint32_t lo = 0, hi = grp_n;                              // last contig whose offset is <= c + 1 (a call at position -1 lies at voff - 1)
+        while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (grp_tab[mid] <= c + 1) lo = mid; else hi = mid; }
         tid = grp_tab[grp_n + lo];
         c -= grp_tab[lo];
     }
@@ -236,9 +236,11 @@ __global__ __launch_bounds__(256, (FD_NB == 8 && SLOTS == 64) ? 8 : 1) void k_fd
                     // mC: the positions the read calls; mM: those it calls methylated.  A read calls positions in
                     // [start - 1, end] only, so the one call that can lie outside the covered bases is its first, at start - 1
                     // (mA below).  Registers past the last call repeat it (see the walk): the same bit again.
+                    // (the look-ups are clamped to the window: a call outside it -- a span violation, reported as such, or the word of
+                    // position -1 in a batch, MTH_ERR_RANGE -- must not read outside bit_of)
                     auto add_call = [&](const uint32_t w) {
                         const uint32_t rel_p = (w & 0x7fffffffu) - (uint32_t)(c - FD_WIN);
-                        const unsigned long long b = 1ull << bit_of[rel_p];
+                        const unsigned long long b = 1ull << bit_of[min(rel_p, 2u * FD_WIN)];
                         mC |= b;
                         mM |= b & (unsigned long long)((long long)(int32_t)w >> 31);
                     };
@@ -248,7 +250,7 @@ __global__ __launch_bounds__(256, (FD_NB == 8 && SLOTS == 64) ? 8 : 1) void k_fd
                         if (any_long)
                             for (uint32_t t = FD_NB; t < r_n; ++t) add_call(a.cpg_pos[r_o0 + t]);
                         const uint32_t p0 = vw[0] & 0x7fffffffu;
-                        const unsigned long long b0 = 1ull << bit_of[p0 - (uint32_t)(c - FD_WIN)];
+                        const unsigned long long b0 = 1ull << bit_of[min(p0 - (uint32_t)(c - FD_WIN), 2u * FD_WIN)];
                         mA = ((int32_t)p0 >= r_s) ? mC : mC & ~b0;
                         mM &= mA;
                     }
@@ -755,12 +757,12 @@ __global__ __launch_bounds__(256, 8) void k_fdrp_walk4(const FdrpArgs a) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const uint32_t rel_p = (cw[k] & 0x7fffffffu) - (uint32_t)(c - FD_WIN);
-                const mask_t b = (mask_t)1 << bit_of[rel_p];
+                const mask_t b = (mask_t)1 << bit_of[min(rel_p, 2u * FD_WIN)];
                 mC |= b;
                 mM |= b & (mask_t)((long long)(int32_t)cw[k] >> 31);
             }
             const uint32_t p0 = cw[0] & 0x7fffffffu;
-            const mask_t b0 = (mask_t)1 << bit_of[p0 - (uint32_t)(c - FD_WIN)];
+            const mask_t b0 = (mask_t)1 << bit_of[min(p0 - (uint32_t)(c - FD_WIN), 2u * FD_WIN)];
             const mask_t mA = ((int32_t)p0 >= cs) ? mC : mC & ~b0;   // the one call that can lie outside the covered bases: start - 1
             mM &= mA;
             uint32_t *r = rows + 8 * __builtin_popcount(mh & ((1u << gl) - 1u));   // slot = arrival order

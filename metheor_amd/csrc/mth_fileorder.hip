@@ -69,7 +69,13 @@ struct FoArgs {
     DevState *st;
 };
 
-__device__ __forceinline__ unsigned long long fo_key(int32_t tid, uint32_t pos) { return (((unsigned long long)(uint32_t)tid << 32) | pos) + 1ull; }
+// Keys order as the reference's (tid, pos) does (readutil.rs:290-314), position -1 included: the low word holds position + 1, so the
+// decoded word 0x7fffffff (a call at -1: a record at 0 under a shifted flag calling on its first base) is 0, the first key of its contig.
+// pos: a decoded call word (the state bit is ignored)
+__device__ __forceinline__ unsigned long long fo_key(int32_t tid, uint32_t pos) { return (((unsigned long long)(uint32_t)tid << 32) | ((pos + 1u) & 0x7fffffffu)) + 1ull; }
+__device__ __forceinline__ int32_t fo_key_pos(unsigned long long key_minus_1) { return (int32_t)(uint32_t)key_minus_1 - 1; }
+// the position of a decoded call word, sign restored
+__device__ __forceinline__ int32_t fo_pos(uint32_t w) { return (int32_t)((w + 1u) & 0x7fffffffu) - 1; }
 
 // the oracle's orc_sample_j (see mth_fdrp.hip)
 __device__ __forceinline__ int32_t fo_sample_j(unsigned long long seed, int32_t tid, int32_t pos, int32_t total) {
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(256) void k_fo_attrs(const FoArgs a) {
     if (n && a.tid[t] < 0 && (flush || contrib)) atomicOr(&a.st->err, (uint32_t)ERRB_RANGE);
     if (n) {
         const uint32_t w0 = a.pos[o0];
-        if (flush) f = fo_key(a.tid[t], w0 & 0x7fffffffu);
+        if (flush) f = fo_key(a.tid[t], w0);
         if (a.measure == MTH_FO_PDR && contrib)
             for (unsigned long long k = o0 + 1; k < o1; ++k) d |= (uint8_t)((a.pos[k] ^ w0) >> 31);
     }
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(256) void k_fo_fill(const FoArgs a) {
     if (!n) return;
     const unsigned long long o0 = a.off[t], c0 = a.coff[t];
     const int32_t tid = a.tid[t];
-    for (uint32_t k = 0; k < n; ++k) { a.ckey[c0 + k] = fo_key(tid, a.pos[o0 + k] & 0x7fffffffu); a.cval[c0 + k] = t; }
+    for (uint32_t k = 0; k < n; ++k) { a.ckey[c0 + k] = fo_key(tid, a.pos[o0 + k]); a.cval[c0 + k] = t; }
 }
 
 // ---- 3: range maximum over F ------------------------------------------------------------------------------------------------------
@@ -167,7 +173,7 @@ __global__ __launch_bounds__(256) void k_fo_sites(const FoArgs a) {
     a.rowflag[i] = 0u; a.sel_a[i] = 0u; a.sel_b[i] = 0u;
     const unsigned long long key = a.ckey[i];
     if (i > 0 && a.ckey[i - 1] == key) return;            // not the first contribution of its site
-    const int32_t c = (int32_t)(uint32_t)(key - 1ull);
+    const int32_t c = fo_key_pos(key - 1ull);
     // stored reads of [x, y) for FDRP: the arrivals add_read does not drop (fdrp.rs:55-63), at most max_depth of them (81-85)
     auto qualifies = [&](uint32_t x, uint32_t y) {
         if (a.measure != MTH_FO_FDRP) return y - x >= a.min_depth;
@@ -274,7 +280,7 @@ __global__ __launch_bounds__(256) void k_fo_fdrp(const FoArgs a) {
             todo &= todo - 1ull;
             const uint32_t x = a.sel_a[i], y = a.sel_b[i];
             const unsigned long long key = a.ckey[i] - 1ull;
-            const int32_t c = (int32_t)(uint32_t)key, tid = (int32_t)(key >> 32);
+            const int32_t c = fo_key_pos(key), tid = (int32_t)(key >> 32);
             // add_read over the segment's arrivals (fdrp.rs:51-95), wave-uniform
             int32_t total = 0, sampled = 0;
             for (uint32_t r = x; r < y; ++r) {
@@ -319,12 +325,12 @@ __global__ __launch_bounds__(256) void k_fo_fdrp(const FoArgs a) {
                 const unsigned long long bi = a.off[ti + 1], bj = a.off[tj + 1];
                 while (ai < bi && aj < bj) {
                     const uint32_t wi = a.pos[ai], wj = a.pos[aj];
-                    const uint32_t pa = wi & 0x7fffffffu, pb = wj & 0x7fffffffu;
+                    const int32_t pa = fo_pos(wi), pb = fo_pos(wj);
                     if (pa == pb) {
                         // a call outside the 403-slot array around c is not in it (the reference would index out of bounds: mth_fdrp.hip)
-                        if ((uint32_t)((int32_t)pa - (c - FO_WIN)) <= 2u * FO_WIN) {
+                        if ((uint32_t)(pa - (c - FO_WIN)) <= 2u * FO_WIN) {
                             ncpg += 1;                                                            // qfdrp.rs:109-119
-                            ham += ((int32_t)pa >= mx && ((wi ^ wj) >> 31)) ? 1u : 0u;            // fdrp.rs:114-115
+                            ham += (pa >= mx && ((wi ^ wj) >> 31)) ? 1u : 0u;                     // fdrp.rs:114-115
                         }
                         ++ai; ++aj;
                     } else if (pa < pb) ++ai; else ++aj;
@@ -361,7 +367,7 @@ __global__ __launch_bounds__(256) void k_fo_emit(const FoArgs a, const uint32_t 
     if (i >= a.n_contrib || !a.rowflag[i]) return;
     const uint32_t o = rank[i];
     const unsigned long long key = a.ckey[i] - 1ull;
-    o_tid[o] = (int32_t)(key >> 32); o_pos[o] = (int32_t)(uint32_t)key;
+    o_tid[o] = (int32_t)(key >> 32); o_pos[o] = fo_key_pos(key);
     o_v0[o] = a.v0[i]; o_v1[o] = a.v1[i]; o_c0[o] = a.c0[i]; o_c1[o] = a.c1[i];
 }
 

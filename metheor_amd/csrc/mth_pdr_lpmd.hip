@@ -62,6 +62,28 @@ __device__ __forceinline__ void index_safe_hi(const uint32_t *__restrict__ cpg_o
     for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
     if (gtid == 0) st->safe_hi = best;
 }
+// The word of position -1 (include/metheor_hip.h, mth_batch_t.cpg_pos) must not reach a batch: only a read that starts at 0 can carry it,
+// as its first call -- looked for on the four reads of a thread whose first start is <= 0 (the reads are sorted: the batch's first few)
+__device__ __forceinline__ void index_minus_one(const uint32_t *__restrict__ cpg_off, const uint32_t *__restrict__ cpg_pos, const uint32_t n_reads,
+                                                const uint32_t n_cpgs, const uint32_t i0, const int32_t *sv, DevState *__restrict__ st) {
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k)
+        if (i0 + k < n_reads && sv[k] == 0) {
+            const uint32_t o = cpg_off[i0 + k];
+            if (cpg_off[i0 + k + 1] > o && o < n_cpgs && (cpg_pos[o] & 0x7fffffffu) == 0x7fffffffu) atomicOr(&st->err, (uint32_t)ERRB_RANGE);
+        }
+}
+// the same look for the run form of the dense kernel (MTH_TILE_RUNS=1), which builds no index: the reads are sorted, so every thread
+// but those of the batch's first reads leaves at its first read
+__global__ __launch_bounds__(256) void k_minus_one_check(const int32_t *__restrict__ read_start, const uint32_t *__restrict__ cpg_off,
+                                                         const uint32_t *__restrict__ cpg_pos, uint32_t n_reads, uint32_t n_cpgs, DevState *__restrict__ st) {
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n_reads; i += gridDim.x * 256) {
+        const int32_t s = read_start[i];
+        if (s > 0) break;
+        const uint32_t o = cpg_off[i];
+        if (s == 0 && cpg_off[i + 1] > o && o < n_cpgs && (cpg_pos[o] & 0x7fffffffu) == 0x7fffffffu) atomicOr(&st->err, (uint32_t)ERRB_RANGE);
+    }
+}
 template <int NIDX>
 __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict__ read_start,
                                                        uint32_t n_reads, int32_t idx_base, int32_t idx_base2, int qshift,
@@ -69,7 +91,8 @@ __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict
                                                        uint32_t *__restrict__ idx, uint32_t *__restrict__ idx2,
                                                        DevState *__restrict__ st, DevState *__restrict__ cst,
                                                        unsigned long long *__restrict__ bucket_sums, uint32_t n_bucket_words,
-                                                       const uint32_t *__restrict__ cpg_off, uint32_t n_cpgs) {
+                                                       const uint32_t *__restrict__ cpg_off, uint32_t n_cpgs,
+                                                       const uint32_t *__restrict__ chk_off, const uint32_t *__restrict__ chk_pos) {
     static_assert(NIDX == 1, "the tile-granular families are the specialisation's");
     // first kernel of a batch: its rows go after everything emitted so far, and the bucket sums start at zero
     // (nothing else runs between the previous batch's last kernel and this one on the stream)
@@ -104,6 +127,7 @@ __global__ __launch_bounds__(BLOCK) void k_build_index(const int32_t *__restrict
         // (taking the element before the group from the neighbouring lane -- one load instruction per lane less -- was measured
         // slower: 0.0171 against 0.0163 ms; the load hits the line its neighbour fetches and waits for nothing extra)
         if (i0 > 0 && i0 <= n_reads) sp[u] = read_start[i0 - 1];
+        if (chk_pos && i0 < n_reads && sv[u][0] <= 0) index_minus_one(chk_off, chk_pos, n_reads, n_cpgs, i0, sv[u], st);
     }
     // ---- the fine index (NIDX = 1), usual case: every thread's four reads open at most FAST_SPAN entries between them.  Entry q of
     // (g_prev, g_last] is the first of the four reads whose quantum reaches q: i0 + the number of reads whose quantum lies below q --
@@ -209,7 +233,8 @@ __global__ __launch_bounds__(BLOCK) void k_build_index<2>(const int32_t *__restr
                                                           uint32_t *__restrict__ idx, uint32_t *__restrict__ idx2,
                                                           DevState *__restrict__ st, DevState *__restrict__ cst,
                                                           unsigned long long *__restrict__ bucket_sums, uint32_t n_bucket_words,
-                                                          const uint32_t *__restrict__ cpg_off, uint32_t n_cpgs) {
+                                                          const uint32_t *__restrict__ cpg_off, uint32_t n_cpgs,
+                                                          const uint32_t *__restrict__ chk_off, const uint32_t *__restrict__ chk_pos) {
     static_assert(IDX2_WAVE_READS == 64 * 4, "one wave, four reads per lane");
     const uint32_t gtid = blockIdx.x * BLOCK + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
@@ -245,6 +270,7 @@ __global__ __launch_bounds__(BLOCK) void k_build_index<2>(const int32_t *__restr
     }
     const bool unsorted = (sv[0] < sp) | (sv[1] < sv[0]) | (sv[2] < sv[1]) | (sv[3] < sv[2]);
     const int32_t s_before = __builtin_amdgcn_readfirstlane(sp), s_last = __builtin_amdgcn_readlane(sv[3], 63);
+    if (s_before <= 0 && chk_pos) index_minus_one(chk_off, chk_pos, n_reads, n_cpgs, i0, sv, st);      // (wave-uniform: the batch's first waves only)
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
         uint32_t *__restrict__ out = f ? idx2 : idx;
@@ -1539,7 +1565,7 @@ int build_fine_index(mth_ctx *ctx, const mth_batch_t &b, int32_t idx_base, uint3
     const uint32_t nb = (b.n_reads / 4 + 1 + BLOCK * IDX_GROUPS - 1) / (BLOCK * IDX_GROUPS);
     hipLaunchKernelGGL(k_build_index<1>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, idx_base, 0, (int)IDX_QSHIFT, nq,
                        (int)((reinterpret_cast<uintptr_t>(b.read_start) & 15u) == 0), idx, (uint32_t *)nullptr, st,
-                       (DevState *)nullptr, (unsigned long long *)nullptr, 0u, b.cpg_off, b.n_cpgs);
+                       (DevState *)nullptr, (unsigned long long *)nullptr, 0u, b.cpg_off, b.n_cpgs, b.cpg_off, b.n_cpgs ? b.cpg_pos : nullptr);
     MTH_HIP(ctx, hipGetLastError());
     return MTH_OK;
 }
@@ -1565,7 +1591,7 @@ int build_read_index(mth_ctx *ctx, const mth_batch_t &b, int tile_w, int32_t &id
     const uint32_t nb = (b.n_reads / 4 + 1 + BLOCK * IDX_GROUPS - 1) / (BLOCK * IDX_GROUPS);
     hipLaunchKernelGGL(k_build_index<1>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, idx_base, 0, (int)IDX_QSHIFT, nq,
                        (int)((reinterpret_cast<uintptr_t>(b.read_start) & 15u) == 0), ctx->idx.as<uint32_t>(), (uint32_t *)nullptr, ctx->d_state,
-                       ctx->d_state, (unsigned long long *)nullptr, 0u, (const uint32_t *)nullptr, 0u);   // cur_base is rewritten by the next PDR batch's own index build
+                       ctx->d_state, (unsigned long long *)nullptr, 0u, (const uint32_t *)nullptr, b.n_cpgs, b.cpg_off, b.n_cpgs ? b.cpg_pos : nullptr);   // cur_base is rewritten by the next PDR batch's own index build
     return MTH_OK;
 }
 
@@ -1724,11 +1750,15 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
         if (coarse)
             hipLaunchKernelGGL(k_build_index<2>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, b.region_beg - b.max_span + 1, b.region_beg + 1,
                                DENSE_TILE_SHIFT, ntiles + 1u, al16, b_idx.as<uint32_t>(), b_idx.as<uint32_t>() + coarse_stride, lane_st,
-                               L ? (DevState *)nullptr : cst, b_bucket.as<unsigned long long>(), n_bucket_words, b.cpg_off, b.n_cpgs);
+                               L ? (DevState *)nullptr : cst, b_bucket.as<unsigned long long>(), n_bucket_words, b.cpg_off, b.n_cpgs, b.cpg_off,
+                               b.n_cpgs ? b.cpg_pos : nullptr);
         else
             hipLaunchKernelGGL(k_build_index<1>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, idx_base, 0, (int)IDX_QSHIFT, nq, al16,
                                b_idx.as<uint32_t>(), (uint32_t *)nullptr, lane_st, L ? (DevState *)nullptr : cst,
-                               b_bucket.as<unsigned long long>(), n_bucket_words, b.cpg_off, b.n_cpgs);
+                               b_bucket.as<unsigned long long>(), n_bucket_words, b.cpg_off, b.n_cpgs, b.cpg_off, b.n_cpgs ? b.cpg_pos : nullptr);
+    } else if (b.n_reads && b.n_cpgs) {      // the run form: no index kernel, so the look for the word of position -1 is a launch of its own
+        hipLaunchKernelGGL(k_minus_one_check, dim3(std::min<uint32_t>((b.n_reads + 255) / 256, 64u)), dim3(256), 0, s, b.read_start, b.cpg_off, b.cpg_pos,
+                           b.n_reads, b.n_cpgs, lane_st);
     }
     TileArgs a;
     a.read_start = b.read_start; a.read_mapq = b.read_mapq; a.cpg_off = b.cpg_off; a.cpg_pos = b.cpg_pos;

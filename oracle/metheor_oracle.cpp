@@ -220,9 +220,12 @@ orc_reads_t *orc_reads_from_soa(int64_t n, const int32_t *tid, const int32_t *st
         r.tid = tid[i]; r.start_pos = start[i]; r.end_pos = end[i];
         r.mapq = mapq[i]; r.fwd = fwd ? fwd[i] : 1;
         r.cpgs.reserve(cpg_off[i + 1] - cpg_off[i]);
-        for (uint64_t c = cpg_off[i]; c < cpg_off[i + 1]; ++c)
-            r.cpgs.push_back(CpG{(int32_t)cpg_rel[c], Pos{r.tid, (int32_t)(cpg_pos[c] & 0x7fffffffu)},
-                                 (cpg_pos[c] >> 31) != 0});
+        for (uint64_t c = cpg_off[i]; c < cpg_off[i + 1]; ++c) {
+            // 31 bits of position: the word 0x7fffffff is position -1 (a shifted-flag record at 0 calling on its first base,
+            // readutil.rs:338); no contig has a position 2^31 - 1
+            const uint32_t w = cpg_pos[c] & 0x7fffffffu;
+            r.cpgs.push_back(CpG{(int32_t)cpg_rel[c], Pos{r.tid, w == 0x7fffffffu ? -1 : (int32_t)w}, (cpg_pos[c] >> 31) != 0});
+        }
     }
     return out;
 }

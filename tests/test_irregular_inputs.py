@@ -114,7 +114,7 @@ def test_oracle_equals_the_transliteration(knob, seed):
         br = G.bismark_read(r)
         o0, o1 = int(soa["cpg_off"][i]), int(soa["cpg_off"][i + 1])
         assert (int(soa["start"][i]), int(soa["end"][i])) == (br["start_pos"], br["end_pos"]), i
-        assert [[int(a), int(p & 0x7fffffff), int(p >> 31)] for a, p in zip(soa["cpg_rel"][o0:o1], soa["cpg_pos"][o0:o1])] == \
+        assert [[int(a), U.signed_pos(p), int(p >> 31)] for a, p in zip(soa["cpg_rel"][o0:o1], soa["cpg_pos"][o0:o1])] == \
             [[c["relpos"], c["abspos"][1], int(c["methylated"])] for c in br["cpgs"]], i
     for p in (dict(min_depth=0, min_cpgs=0, min_qual=10), dict(min_depth=3, min_cpgs=2, min_qual=10)):
         t, want = rd.pdr(**p), G.pdr(recs, **p)

@@ -23,7 +23,7 @@ def test_oracle_equals_the_transliteration(case):
     for i, d in enumerate(case["decode"]):
         o0, o1 = int(soa["cpg_off"][i]), int(soa["cpg_off"][i + 1])
         assert (int(soa["start"][i]), int(soa["end"][i])) == (d["start"], d["end"]), i
-        got = [[int(r), int(p & 0x7fffffff), int(p >> 31)] for r, p in zip(soa["cpg_rel"][o0:o1], soa["cpg_pos"][o0:o1])]
+        got = [[int(r), U.signed_pos(p), int(p >> 31)] for r, p in zip(soa["cpg_rel"][o0:o1], soa["cpg_pos"][o0:o1])]
         assert got == d["cpgs"], (i, case["records"][i])
     ex = case["expect"]
     for e in ex.get("pdr", []):

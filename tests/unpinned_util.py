@@ -38,6 +38,12 @@ def records_of(case):
                          cig, [r["xm"].encode() for r in rs])
 
 
+def signed_pos(word):
+    """the position of a decoded call word (31 bits of position | methylated << 31) with its sign restored: 0x7fffffff is -1"""
+    p = int(word) & 0x7fffffff
+    return -1 if p == 0x7fffffff else p
+
+
 def from_bits(b):
     return np.array(b, dtype=np.uint32).view(np.float32)
 

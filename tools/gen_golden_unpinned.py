@@ -18,7 +18,7 @@ yield None per base; D and N advance the reference only (nothing yielded: no que
 ("Padding (Cigar::Pad) is not supported.") -- that last one is recalled, not verifiable here, and is not part of the cases.
 
 CHECKLIST for a maintainer with `cargo` (rust-htslib 0.50.0, hts-sys 2.2.0): everything below is RECALLED, not read -- the crate is not
-under /root/reference.  Each line is one assumption the 52 record sets depend on; the Rust one-liner next to it checks it.
+under /root/reference.  Each line is one assumption the 54 record sets depend on; the Rust one-liner next to it checks it.
   1. `Record::reference_positions_full()` yields exactly one item per query base (seq_len items; `H` and `P` add none).
   2. For `M`, `=`, `X` the item is Some(reference position), 0-based, ascending by one per base.
   3. For `I` and `S` the item is None (the base exists in the query, has no reference position).
@@ -625,7 +625,65 @@ def hand_cases():
             lpmd=[dict(min_distance=2, max_distance=16, min_qual=10), dict(min_distance=5, max_distance=4, min_qual=10)],
             mhl=[dict(min_depth=0, min_cpgs=1, min_qual=10), dict(min_depth=2, min_cpgs=4, min_qual=10)],
             quartet=[dict(min_qual=10)], fdrp=[dict(min_qual=10, min_depth=0, max_depth=40, min_overlap=10)])))
+    # -- a call at position -1: a record at position 0 whose flag is outside {0, 99, 147} reports abspos - 1 (readutil.rs:338) for a
+    # call on its first aligned base.  CpGPosition.pos is a plain i32: (tid, -1) is the first key of its contig in every BTreeMap, the
+    # pair (-1, 1) is an ordinary pair, and as a record's first CpG it flushes nothing on its own contig (no key is < (tid, -1) there).
+    ms, mu = contig_start_records()
+    minus_one = dict(ALL)
+    minus_one["pdr"] = ALL["pdr"] + [dict(min_depth=1, min_cpgs=0, min_qual=10)]
+    minus_one["mhl"] = ALL["mhl"] + [dict(min_depth=1, min_cpgs=1, min_qual=10)]
+    minus_one["fdrp"] = ALL["fdrp"] + [dict(min_qual=10, min_depth=1, max_depth=64, min_overlap=10)]
+    cs.append(("call_at_minus_one_sorted", ms, minus_one))
+    cs.append(("call_at_minus_one_unsorted", mu, minus_one, False))
     return cs
+
+
+CONTIG_START_SITES = [-1, 1, 3, 9, 20, 33, 47] + list(range(60, 400, 13))
+
+
+def contig_start_records():
+    """-> (sorted, unsorted) record lists of the two call_at_minus_one cases: two contigs, each with reads at position 0 under the
+    shifted flags 16, 1024 and 83 that call on their first base, and ordinary reads over positions 0-400 at depth 3-6"""
+    def read(tid, pos, n, flag, calls, mapq=40):
+        # calls: {site: methylated}; a shifted flag calls site s on the base at s + 1
+        fwd = flag in (0, 99, 147)
+        xm = ["."] * n
+        for s, m in calls.items():
+            i = (s if fwd else s + 1) - pos
+            assert 0 <= i < n, (pos, n, flag, s)
+            xm[i] = "Z" if m else "z"
+        return rec(tid, pos, "%dM" % n, "".join(xm), flag, mapq)
+
+    zero, rest = [], []
+    for tid in (0, 1):
+        rng = np.random.default_rng(4100 + tid)
+        level = {s: (0.85 if rng.random() < 0.6 else 0.2) for s in CONTIG_START_SITES}
+        draw = lambda sites: {s: bool(rng.random() < level[s]) for s in sites}
+        z = [
+            read(tid, 0, 30, 16, {-1: True, 9: False, 20: True}),
+            rec(tid, 0, "12M", "Z.Z.z" + "." * 7, 1024),                                     # forward, shifted: calls -1, 1, 3 -> the pair (-1, 1)
+            read(tid, 0, 50, 83, {-1: tid == 0, 1: True, 3: True, 9: True, 20: False, 33: True, 47: True}),   # quartets (-1, 1, 3, 9) ...
+            read(tid, 0, 30, 16, {-1: False, 9: True}, mapq=3),                              # below the cut
+            read(tid, 0, 201, 16, {-1: True, 199: False}),                                   # site -1's window ends at 200: kept (fdrp.rs:61)
+            read(tid, 0, 40, 0, draw([1, 3, 9, 20, 33])),                                    # flag 0 at position 0: no call at -1
+            read(tid, 0, 30, 1024, {-1: False, 1: True, 9: True, 20: tid == 1}),
+            read(tid, 0, 36, 83, draw([-1, 3, 9, 20, 33])),
+        ]
+        o = []
+        for k, pos in enumerate(range(2, 392, 11)):
+            n = 46 + 7 * (k % 3)
+            flag = 16 if k % 2 else 0
+            lo = pos if flag == 0 else pos - 1                                              # the sites this read's bases can report
+            o.append(read(tid, pos, n, flag, draw([s for s in CONTIG_START_SITES if lo <= s < lo + n]), mapq=40 if k % 9 != 4 else 7))
+        zero.append(z)
+        rest.append(o)
+    srt = zero[0] + rest[0] + zero[1] + rest[1]
+    # the position-0 reads behind later reads of their contig and behind reads of the other contig: site -1 is re-opened and
+    # overwritten, its first-CpG flush takes nothing on its own contig and every open site of a smaller tid
+    uns = (rest[0][:9] + zero[0][:3] + rest[0][9:20] + zero[0][3:5] + rest[0][20:] + rest[1][:7] + zero[0][5:] + zero[1][:4] +
+           rest[1][7:25] + zero[1][4:] + rest[1][25:])
+    assert sorted(map(id, srt)) == sorted(map(id, uns))
+    return srt, uns
 
 
 def enc_key(k):

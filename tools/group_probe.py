@@ -28,7 +28,7 @@ for g in groups:
         o = k[3].to(torch.int64)
         off.append(o[:-1] + base); base += int(o[-1].item())
         p = k[4].to(torch.int64) & 0xffffffff
-        pos.append((((p & 0x7fffffff) + vo) | (p & 0x80000000)).to(torch.int64))
+        pos.append((((p + vo) & 0x7fffffff) | (p & 0x80000000)).to(torch.int64))   # (31-bit sum, as k_grp_shift: a call at position -1 lands on vo - 1; a first contig that holds one is not lifted here)
         rel.append(k[5])
     off.append(torch.tensor([base], device=dev, dtype=torch.int64))
     cat = lambda xs: torch.cat(xs).contiguous()
