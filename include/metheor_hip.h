@@ -413,6 +413,48 @@ typedef struct {
 int  mth_bgzf_decode_straddle(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
                               const uint32_t *isize, uint64_t n_blocks, uint64_t first_byte, unsigned flags, mth_decoded_t *out,
                               mth_straddle_info_t *info);
+/* The record chain of a RUN of blocks of such a file, without decoding anything: what a shard of a multi-GPU run needs to know
+ * about its part of the file before any block has a verified entry.  The scheme of mth_bgzf_decode_straddle one level up: every
+ * run is scanned from a guessed entry, in parallel, and the caller then verifies the guesses against the serial chain (run 0
+ * enters at the header's end, run r where run r - 1 leaves; a run whose assumed entry differs is scanned again from the true one),
+ * so nothing of the guess rule enters the result.
+ * Arguments as mth_bgzf_decode_straddle's (file bytes, coff / csize / isize of n_blocks blocks), of which the first n_run are the
+ * run and the rest look-ahead: the caller passes blocks after the run until the stream reaches at least MTH_STRADDLE_LOOKAHEAD
+ * bytes past the run's end, or the file ends -- a block_size field or the 12 key bytes of a record that lie across a block's end
+ * can then be read, and a record that ends beyond the stream leaves at p + 4 + block_size, a value (not "cannot go on").
+ * entry: offset in the run's stream where the chain enters (it may lie past any number of the run's blocks: a record that started
+ * before the run covers them), or MTH_STRADDLE_ENTRY_GUESS: the run's first block guesses like every other block and the rounds
+ * settle relative to that guess; where a block finds no guess, or leaves at or past the END of the block behind it, the chain
+ * breaks and a new one starts at that block's own guess (no block has a certain entry yet, so an exit is believed only as far as
+ * the next block: a wrong guess whose block_size leads megabytes on must not overwrite good guesses one block per round).
+ * rows (host memory, n_run of them), per block of the run: start = offset inside the block of the first record that STARTS there
+ * (MTH_STRADDLE_NO_START: a record covers the whole block), ref_id / pos = that record's refID and pos as stored, exit = bytes
+ * past the block's end where the chain leaves it (MTH_STRADDLE_EXIT_BAD: it cannot go on from this block -- no entry, block_size
+ * < 32 or unreadable; under a guessed entry that says nothing about the file).  run: the entry that was used
+ * (MTH_STRADDLE_ENTRY_GUESS: the first block found no guess, or the chain breaks inside the run -- scan it again) and the run's exit relative to the first byte after the run.
+ * info as above (carry_bytes 0); the round bound and MTH_ERR_UNALIGNED as above.
+ * A second pass: the inflated bytes, the block table and the links of the latest scan stay in the context until its next call
+ * that inflates (or mth_reset), so mth_bgzf_straddle_rescan(ctx, entry, ...) -- the same run from the true entry -- costs repair
+ * rounds from block 0 only, no copy and no inflate: guesses that are 4 bytes short are common on look-alike data
+ * (profiles/straddle_walk.md), rescans are not rare.  MTH_ERR_INVALID when the context holds no scan. */
+#define MTH_STRADDLE_ENTRY_GUESS (~0ull)
+#define MTH_STRADDLE_NO_START    0xffffffffu
+#define MTH_STRADDLE_EXIT_BAD    (~0ull)
+#define MTH_STRADDLE_LOOKAHEAD   36
+typedef struct {
+    uint32_t start;
+    int32_t  ref_id, pos;
+    uint32_t pad_;
+    uint64_t exit;
+} mth_straddle_row_t;
+typedef struct {
+    uint64_t entry, exit;
+} mth_straddle_run_t;
+int  mth_bgzf_straddle_scan(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
+                            const uint32_t *isize, uint64_t n_blocks, uint64_t n_run, uint64_t entry, mth_straddle_row_t *rows,
+                            mth_straddle_run_t *run, mth_straddle_info_t *info);
+int  mth_bgzf_straddle_rescan(mth_ctx_t *ctx, uint64_t entry, mth_straddle_row_t *rows, mth_straddle_run_t *run,
+                              mth_straddle_info_t *info);
 /* Overlap of the NEXT chunk's host-to-device copy with the current chunk's kernels: announces file[0, n_bytes) (host memory
  * that stays valid) as the chunk after the one the next mth_bgzf_decode / mth_bgzf_inflate call is given.  That call starts a
  * helper thread which copies the announced bytes into a second staging buffer on a side stream while its own kernels run;

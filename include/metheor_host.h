@@ -115,6 +115,40 @@ typedef struct {
     int32_t  tid_end, pos_end;
 } mth_host_shard_t;
 int  mth_host_plan_shard(mth_host_t *h, int rank, int world, int64_t halo_bp, mth_host_shard_t *out);
+/* The same sharding for a file whose records STRADDLE BGZF blocks (blocks cut at a byte count: htsjdk / Picard / GATK, sambamba,
+ * biobambam).  No block of such a file has a known entry before its left neighbour's chain is known, so the plan is made in two steps.
+ * 1. mth_host_plan_straddle_run: the run of blocks shard `rank` SCANS (mth_bgzf_straddle_scan in metheor_hip.h) -- the same cuts
+ *    by compressed size; run 0 starts at block 0 and enters at the header's end, every other run enters at a guess
+ *    (MTH_HOST_STRADDLE_ENTRY_GUESS); blocks [block_end, ahead_end) are the look-ahead the scan is given (until the stream reaches
+ *    MTH_HOST_STRADDLE_LOOKAHEAD bytes past the run, or the data ends).  The caller verifies the runs' chain in run order (run r
+ *    enters where run r - 1 leaves; a run whose assumed entry differs is scanned again; an entry at or past the run's end passes
+ *    on: no record starts in the run) and so gets ONE table for the file, a row per block of mth_host_bgzf_blocks' table.
+ * 2. mth_host_plan_shard_straddle: mth_host_plan_shard from that table.  The keys come from the table, not from reading a record
+ *    at a block's first byte; a cut is moved forward to the next block in which a record starts; first_byte is the table's entry
+ *    of block_beg, an exact record start (mth_host_plan_region_at_record's convention: load with mth_bgzf_decode_straddle and
+ *    MTH_STRADDLE_DROP_TAIL); the right halo reaches the block that holds the END of the last record it needs (the table's exit
+ *    of the last halo block); a block in which no record starts is passed over.  MTH_HOST_ERR_FORMAT for a table with a chain
+ *    that does not go on.
+ * A row (the layout of mth_straddle_row_t): start = offset inside the block of the first record that starts there, ref_id / pos
+ * = its refID and pos as stored, exit = bytes past the block's end where the chain leaves it. */
+#define MTH_HOST_STRADDLE_ENTRY_GUESS (~0ull)
+#define MTH_HOST_STRADDLE_NO_START    0xffffffffu
+#define MTH_HOST_STRADDLE_EXIT_BAD    (~0ull)
+#define MTH_HOST_STRADDLE_LOOKAHEAD   36
+typedef struct {
+    uint32_t start;
+    int32_t  ref_id, pos;
+    uint32_t pad_;
+    uint64_t exit;
+} mth_host_straddle_row_t;
+typedef struct {
+    uint64_t block_beg, block_end;   /* the run */
+    uint64_t ahead_end;              /* look-ahead blocks [block_end, ahead_end) */
+    uint64_t entry;                  /* offset in the run's stream where it enters, or MTH_HOST_STRADDLE_ENTRY_GUESS */
+} mth_host_straddle_run_t;
+int  mth_host_plan_straddle_run(mth_host_t *h, int rank, int world, mth_host_straddle_run_t *out);
+int  mth_host_plan_shard_straddle(mth_host_t *h, const mth_host_straddle_row_t *rows, uint64_t n_rows, int rank, int world,
+                                  int64_t halo_bp, mth_host_shard_t *out);
 /* The same kind of plan from the BAM index (.bai, SAM spec 5.2; SURVEY 8(f).2 -- the reference's fixtures ship
  * tests/test{1..6}.bam.bai, its reader bamutil.rs:4-11 never opens them): the BGZF blocks that can hold records overlapping
  * [beg - halo_bp, end] of reference `tid`, and the owned interval [(tid, beg), (tid, end)).  bai_path NULL: <bam>.bai, then

@@ -16,7 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_decode_set_genome",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_decode_set_genome",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -90,6 +90,15 @@ class mth_straddle_info_t(C.Structure):
 
 MTH_STRADDLE_APPEND, MTH_STRADDLE_LAST, MTH_STRADDLE_DROP_TAIL = 1, 2, 4
 MTH_STRADDLE_MAX_ROUNDS = 64
+MTH_STRADDLE_ENTRY_GUESS = MTH_STRADDLE_EXIT_BAD = (1 << 64) - 1
+MTH_STRADDLE_NO_START = 0xffffffff
+MTH_STRADDLE_LOOKAHEAD = 36
+# mth_straddle_row_t (and mth_host_straddle_row_t: one layout), as a numpy record
+STRADDLE_ROW = np.dtype([("start", np.uint32), ("ref_id", np.int32), ("pos", np.int32), ("pad_", np.uint32), ("exit", np.uint64)])
+
+
+class mth_straddle_run_t(C.Structure):
+    _fields_ = [("entry", C.c_uint64), ("exit", C.c_uint64)]
 
 
 class mth_tag_out_t(C.Structure):
@@ -162,6 +171,9 @@ def lib():
         L.mth_bgzf_decode.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(mth_decoded_t)]
         L.mth_bgzf_decode_straddle.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint, C.POINTER(mth_decoded_t),
                                                C.POINTER(mth_straddle_info_t)]
+        L.mth_bgzf_straddle_scan.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.POINTER(mth_straddle_run_t),
+                                             C.POINTER(mth_straddle_info_t)]
+        L.mth_bgzf_straddle_rescan.argtypes = [vp, C.c_uint64, vp, C.POINTER(mth_straddle_run_t), C.POINTER(mth_straddle_info_t)]
         L.mth_bgzf_stage.argtypes = [vp, vp, C.c_uint64]
         L.mth_decode_reserve.argtypes = [vp, C.c_uint64, C.c_uint64]
         L.mth_tag_set_genome.argtypes = [vp, C.c_int32, vp, vp, vp]
@@ -530,6 +542,33 @@ class Engine:
         self._check(rc)
         self._decoded = d
         return int(d.n_reads), int(d.n_cpgs), self.straddle_info
+
+    def bgzf_straddle_scan(self, file_bytes, coff, csize, isize, n_run, entry=None):
+        """mth_bgzf_straddle_scan: the record chain of the first n_run of the given blocks (the rest is look-ahead), nothing decoded.
+        entry: offset in the run's stream, None = a guess.
+        -> (rows: STRADDLE_ROW array of n_run, dict(entry -- None: the first block found no guess --, exit -- None: the chain does
+        not go on --, rounds, repaired_blocks)); the context keeps the run for bgzf_straddle_rescan"""
+        fb = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(file_bytes, np.uint8)
+        coff = np.ascontiguousarray(coff, np.uint64); csize = np.ascontiguousarray(csize, np.uint32); isize = np.ascontiguousarray(isize, np.uint32)
+        rows = np.zeros(int(n_run), STRADDLE_ROW)
+        run, info = mth_straddle_run_t(), mth_straddle_info_t()
+        self._scan_rows = int(n_run)
+        self._check(self.L.mth_bgzf_straddle_scan(self.h, fb.ctypes.data, fb.size, coff.ctypes.data, csize.ctypes.data, isize.ctypes.data, len(coff),
+                                                  int(n_run), MTH_STRADDLE_ENTRY_GUESS if entry is None else int(entry), rows.ctypes.data,
+                                                  C.byref(run), C.byref(info)))
+        return rows, self._scan_summary(run, info)
+
+    def bgzf_straddle_rescan(self, entry):
+        """mth_bgzf_straddle_rescan: the run of the latest bgzf_straddle_scan again, from the exact entry -> as bgzf_straddle_scan"""
+        rows = np.zeros(self._scan_rows, STRADDLE_ROW)
+        run, info = mth_straddle_run_t(), mth_straddle_info_t()
+        self._check(self.L.mth_bgzf_straddle_rescan(self.h, int(entry), rows.ctypes.data, C.byref(run), C.byref(info)))
+        return rows, self._scan_summary(run, info)
+
+    @staticmethod
+    def _scan_summary(run, info):
+        return dict(entry=None if run.entry == MTH_STRADDLE_ENTRY_GUESS else int(run.entry), exit=None if run.exit == MTH_STRADDLE_EXIT_BAD else int(run.exit),
+                    rounds=int(info.rounds), repaired_blocks=int(info.repaired_blocks))
 
     def tag_set_genome(self, contigs):
         """contigs: [(header LN, bases as bytes)] in tid order (mth_tag_set_genome; tag.rs:419-431)"""

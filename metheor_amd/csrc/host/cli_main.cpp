@@ -13,6 +13,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <chrono>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -459,7 +460,8 @@ int window_to_device(void *user, const uint8_t *buf, const uint64_t *rec_off, ui
 // chunks go through mth_bgzf_decode_straddle instead -- under --region always (nothing else can load a part of such a file),
 // for a whole file when METHEOR_DEVICE_STRADDLE=1 (which route is the faster one there: profiles/straddle_walk.md) -- with a
 // phase line of its own.  Returns false, with the context reset, when the file is left to the host walk.
-// --gpus N keeps needing whole records per block: a shard's first block has no verified entry without its neighbour's chain.
+// --gpus N by default keeps needing whole records per block: a shard's first block has no verified entry without its neighbour's
+// chain.  METHEOR_SHARD_STRADDLE=1 opens it to such files (shard_straddle_load below).
 const char *const kStraddlePhase = "  device inflate + straddle walk + decode";
 
 // the chunk loop over blocks [blk_beg, bz.n_blocks) (bz.header_bytes: inflated bytes of the first block before the first record);
@@ -527,6 +529,113 @@ int load_chunks(Input &in, const mth_host_bgzf_t &bz, uint64_t blk_beg, bool str
     return MTH_OK;
 }
 
+// ---- --gpus N over a file whose records straddle blocks (METHEOR_SHARD_STRADDLE=1) ---------------------------------------------
+// The speculate-then-verify walk of mth_bgzf_decode_straddle one level up.  Every shard scans its own run of blocks on its own context
+// from a guessed entry (mth_bgzf_straddle_scan: inflate + record chain, nothing decoded), all at once; the shards then meet once and
+// the last to arrive verifies the runs against the serial chain -- run 0 enters at the header's end, run r where run r - 1 leaves, a
+// run whose assumed entry differs is scanned again from the true one (mth_bgzf_straddle_rescan: the run's bytes and links are still on
+// its context, repair rounds only), an entry at or past a run's end passes on -- which leaves ONE table for the file.  Every shard
+// plans from it (mth_host_plan_shard_straddle) and loads its blocks as --region loads such a file.  The inflate is paid twice, scan
+// and load: profiles/shard_straddle.md.
+struct ShardMeet {                    // the shards' threads meet: the last to arrive runs `last` for all of them
+    std::mutex mu;
+    std::condition_variable cv;
+    int arrived = 0;
+    uint64_t gen = 0;
+    template <class F> void meet(int world, F &&last) {
+        std::unique_lock<std::mutex> lk(mu);
+        if (++arrived == world) { last(); arrived = 0; ++gen; cv.notify_all(); }
+        else { const uint64_t g = gen; cv.wait(lk, [&] { return gen != g; }); }
+    }
+};
+struct ShardStraddle {
+    ShardMeet meet;
+    bool aligned_failed = false;      // some shard's aligned plan or load met a record that straddles blocks: every shard takes this route
+    bool unsettled = false;           // a scan did not settle within the round bound: the refusal stays
+    struct Run { mth_host_straddle_run_t plan; mth_straddle_run_t got; mth_ctx_t *ctx = nullptr; uint32_t rounds = 0; };
+    std::vector<Run> runs;
+    std::vector<mth_host_straddle_row_t> table;        // a row per block of the file
+} g_sx;
+static_assert(sizeof(mth_host_straddle_row_t) == sizeof(mth_straddle_row_t) && offsetof(mth_host_straddle_row_t, exit) == offsetof(mth_straddle_row_t, exit),
+              "the device writes its rows straight into the host planner's table");
+
+bool shard_straddle_on() { const char *e = getenv("METHEOR_SHARD_STRADDLE"); return e && atoi(e) != 0; }
+
+// run in run order by the last shard to arrive, every scan done
+void shard_straddle_verify(const mth_host_bgzf_t &bz) {
+    uint64_t entry = bz.header_bytes;            // where the chain enters the run at hand, from the run's first byte
+    unsigned n_runs = 0, rescans = 0, rounds = 0;
+    for (ShardStraddle::Run &r : g_sx.runs) {
+        rounds += r.rounds;
+        const uint64_t b0 = r.plan.block_beg, b1 = r.plan.block_end;
+        if (b1 == b0) continue;                  // an empty run passes its entry on
+        ++n_runs;
+        uint64_t run_len = 0;
+        for (uint64_t b = b0; b < b1; ++b) run_len += bz.isize[b];
+        if (entry >= run_len) {                  // a record that started before the run covers it: nothing starts here
+            uint64_t left = entry;
+            for (uint64_t b = b0; b < b1; ++b) { left -= bz.isize[b]; g_sx.table[b] = mth_host_straddle_row_t{MTH_HOST_STRADDLE_NO_START, INT32_MIN, INT32_MIN, 0, left}; }
+            entry -= run_len;
+            continue;
+        }
+        if (r.got.entry != entry) {
+            mth_straddle_info_t info;
+            const int rc = mth_bgzf_straddle_rescan(r.ctx, entry, reinterpret_cast<mth_straddle_row_t *>(g_sx.table.data() + b0), &r.got, &info);
+            ++rescans;
+            rounds += info.rounds;
+            if (rc == MTH_ERR_UNALIGNED) { g_sx.unsettled = true; return; }
+            if (rc == MTH_ERR_FORMAT) die_decode_format(r.ctx, "corrupt BGZF block or BAM record");
+            check(r.ctx, rc);
+        }
+        if (r.got.exit == MTH_STRADDLE_EXIT_BAD) die("Error reading BAM record. corrupt BGZF block or BAM record");   // block_size < 32 on the verified chain
+        entry = r.got.exit;
+    }
+    if (n_runs && entry != 0) die("Error reading BAM record. corrupt BGZF block or BAM record");       // the file ends inside a record
+    if (getenv("METHEOR_TIMING")) fprintf(stderr, "[metheor straddle] shard scan: %u runs, %u scanned again, %u rounds\n", n_runs, rescans, rounds);
+}
+
+// -> false: a scan did not settle (the caller refuses the file as before)
+bool shard_straddle_load(Input &in, mth_host_bgzf_t bz) {
+    const int rank = g_shard.rank, world = g_shard.world;
+    ShardStraddle::Run run;
+    run.ctx = in.ctx;
+    run.got = mth_straddle_run_t{0, 0};
+    if (mth_host_plan_straddle_run(in.h, rank, world, &run.plan) != 0) die(mth_host_last_error(in.h));
+    std::vector<mth_straddle_row_t> rows((size_t)(run.plan.block_end - run.plan.block_beg));
+    bool settled = true;
+    if (!rows.empty()) {
+        Phase ph("  device inflate + straddle scan");
+        const uint64_t b0 = run.plan.block_beg, n = run.plan.ahead_end - b0, base = bz.coff[b0];
+        std::vector<uint64_t> rel((size_t)n);
+        for (uint64_t k = 0; k < n; ++k) rel[(size_t)k] = bz.coff[b0 + k] - base;
+        const uint64_t nbytes = bz.coff[b0 + n - 1] + bz.csize[b0 + n - 1] + 8 - base;      // incl. the last block's CRC32 + ISIZE trailer
+        mth_straddle_info_t info;
+        const int rc = mth_bgzf_straddle_scan(in.ctx, bz.file + base, nbytes, rel.data(), bz.csize + b0, bz.isize + b0, n, rows.size(), run.plan.entry,
+                                              rows.data(), &run.got, &info);
+        run.rounds = info.rounds;
+        if (rc == MTH_ERR_UNALIGNED) settled = false;
+        else if (rc == MTH_ERR_FORMAT) die_decode_format(in.ctx, "corrupt BGZF block or BAM record");
+        else check(in.ctx, rc);
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_sx.meet.mu);
+        if (g_sx.runs.empty()) {                 // sized by whoever comes first, filled by all
+            g_sx.table.assign((size_t)bz.n_blocks, mth_host_straddle_row_t{MTH_HOST_STRADDLE_NO_START, INT32_MIN, INT32_MIN, 0, 0});
+            g_sx.runs.resize((size_t)world);
+        }
+        if (!settled) g_sx.unsettled = true;
+        g_sx.runs[(size_t)rank] = run;
+        if (!rows.empty()) memcpy(g_sx.table.data() + run.plan.block_beg, rows.data(), rows.size() * sizeof rows[0]);
+    }
+    g_sx.meet.meet(world, [&] { if (!g_sx.unsettled) shard_straddle_verify(bz); });
+    if (g_sx.unsettled) return false;
+    if (mth_host_plan_shard_straddle(in.h, g_sx.table.data(), g_sx.table.size(), rank, world, g_shard.halo, &g_shard.plan) != 0) die(mth_host_last_error(in.h));
+    bz.n_blocks = g_shard.plan.block_end;
+    bz.header_bytes = g_shard.plan.first_byte;
+    Phase ph(kStraddlePhase);
+    return load_chunks(in, bz, g_shard.plan.block_beg, true, true) == MTH_OK;
+}
+
 bool load_bgzf_on_device(Input &in) {
     mth_host_bgzf_t bz;
     if (mth_host_bgzf_blocks(in.h, &bz) != 0) die(mth_host_last_error(in.h));
@@ -541,15 +650,32 @@ bool load_bgzf_on_device(Input &in) {
             const char *bai = g_shard.bai.empty() ? nullptr : g_shard.bai.c_str();
             if ((at_record ? mth_host_plan_region_at_record : mth_host_plan_region)(in.h, bai, tid, g_shard.r_beg, g_shard.r_end, g_shard.halo, &g_shard.plan) != 0)
                 die(mth_host_last_error(in.h));
-        } else if (mth_host_plan_shard(in.h, g_shard.rank, g_shard.world, g_shard.halo, &g_shard.plan) != 0) die(mth_host_last_error(in.h));
+        } else {
+            const int rc = mth_host_plan_shard(in.h, g_shard.rank, g_shard.world, g_shard.halo, &g_shard.plan);
+            if (rc == MTH_HOST_ERR_FORMAT && shard_straddle_on()) return false;       // a run does not start at a record boundary
+            if (rc != 0) die(mth_host_last_error(in.h));
+        }
         blk_beg = g_shard.plan.block_beg;
         bz.n_blocks = g_shard.plan.block_end;
         bz.header_bytes = g_shard.plan.first_byte;
+        return true;
     };
-    if (g_shard.planned()) plan(false);
-    {
+    const bool sharded_straddle = g_shard.world > 1 && shard_straddle_on();
+    bool aligned = !g_shard.planned() || plan(false);
+    if (aligned) {
         Phase ph("  device inflate + walk + decode");
-        if (load_chunks(in, bz, blk_beg, false, false) == MTH_OK) return true;
+        aligned = load_chunks(in, bz, blk_beg, false, false) == MTH_OK;
+        if (aligned && !sharded_straddle) return true;
+    }
+    if (sharded_straddle) {
+        // the aligned planner can accept such a file by accident (or have nothing to load) where its neighbour's fails: the route is
+        // the run's, not the shard's, so the shards agree on it first
+        { std::lock_guard<std::mutex> lk(g_sx.meet.mu); if (!aligned) g_sx.aligned_failed = true; }
+        g_sx.meet.meet(g_shard.world, [] {});
+        if (!g_sx.aligned_failed) return true;
+        if (aligned) check(in.ctx, mth_reset(in.ctx));        // what this shard decoded belongs to a plan the others could not follow
+        bz.n_blocks = all_blocks; bz.header_bytes = file_header;
+        return shard_straddle_load(in, bz);
     }
     const char *e = getenv("METHEOR_DEVICE_STRADDLE");
     if (g_shard.world > 1 || !(g_shard.region || (e && atoi(e) != 0))) return false;

@@ -251,6 +251,24 @@ int mth_host_bgzf_blocks(mth_host_t *h, mth_host_bgzf_t *out) {
     return MTH_HOST_OK;
 }
 
+// the data blocks [D, E) of the file (D holds the first record, at inflated offset d_off; E drops trailing empty blocks) and the
+// first block of run k of `world` runs of about equal compressed size -- the cuts of mth_host_plan_shard
+static void data_blocks(const mth_host *h, const BgzfMap &m, uint64_t &D, uint64_t &d_off, uint64_t &E) {
+    uint64_t cum = 0;
+    D = 0; E = m.coff.size();
+    while (D < E && cum + m.isize[D] <= h->header_bytes) cum += m.isize[D++];
+    d_off = h->header_bytes - cum;
+    while (E > D && m.isize[E - 1] == 0) --E;
+}
+static uint64_t size_cut(const BgzfMap &m, uint64_t D, uint64_t E, int k, int world) {
+    if (k <= 0) return D;
+    if (k >= world) return E;
+    const uint64_t total = m.coff[E - 1] + m.csize[E - 1] - m.coff[D];
+    const uint64_t want = m.coff[D] + (uint64_t)((unsigned __int128)total * (unsigned)k / (unsigned)world);
+    const auto it = std::lower_bound(m.coff.begin() + (ptrdiff_t)D, m.coff.begin() + (ptrdiff_t)E, want);
+    return (uint64_t)(it - m.coff.begin());
+}
+
 // first record of BGZF block `b` at inflated offset `off`: (refID, pos); refID -1 (no contig) sorts last
 static bool peek_record(const BgzfMap &m, uint64_t b, uint64_t off, int32_t &tid, int32_t &pos) {
     const uint32_t isz = m.isize[b];
@@ -282,19 +300,10 @@ int mth_host_plan_shard(mth_host_t *h, int rank, int world, int64_t halo_bp, mth
     memset(out, 0, sizeof *out);
     out->tid_beg = -1; out->tid_end = INT32_MAX;
     // data blocks [D, E): D holds the first record (at inflated offset d_off), E drops trailing empty blocks (the EOF marker)
-    uint64_t D = 0, cum = 0, E = bz.n_blocks;
-    while (D < E && cum + m.isize[D] <= h->header_bytes) cum += m.isize[D++];
-    const uint64_t d_off = h->header_bytes - cum;
-    while (E > D && m.isize[E - 1] == 0) --E;
+    uint64_t D, d_off, E;
+    data_blocks(h, m, D, d_off, E);
     if (D >= E) { out->block_beg = out->block_end = 0; out->first_byte = 0; return MTH_HOST_OK; }   // no record at all
-    auto cut = [&](int k) -> uint64_t {      // first block of run k: runs of about equal compressed size
-        if (k <= 0) return D;
-        if (k >= world) return E;
-        const uint64_t total = m.coff[E - 1] + m.csize[E - 1] - m.coff[D];
-        const uint64_t want = m.coff[D] + (uint64_t)((unsigned __int128)total * (unsigned)k / (unsigned)world);
-        const auto it = std::lower_bound(m.coff.begin() + (ptrdiff_t)D, m.coff.begin() + (ptrdiff_t)E, want);
-        return (uint64_t)(it - m.coff.begin());
-    };
+    auto cut = [&](int k) { return size_cut(m, D, E, k, world); };      // first block of run k: runs of about equal compressed size
     auto first_of = [&](uint64_t b, int32_t &t, int32_t &p) { return peek_record(m, b, b == D ? d_off : 0, t, p); };
     const uint64_t B0 = cut(rank), B1 = cut(rank + 1);
     auto fail = [&]() { h->last_error = "a shard does not start at a record boundary (records straddle BGZF blocks)"; return MTH_HOST_ERR_FORMAT; };
@@ -332,6 +341,89 @@ int mth_host_plan_shard(mth_host_t *h, int rank, int world, int64_t halo_bp, mth
     if (empty || L >= R) { out->block_beg = out->block_end = L; out->first_byte = 0; return MTH_HOST_OK; }
     if (L <= D) { out->block_beg = 0; out->first_byte = h->header_bytes; }    // from the top of the file: the header comes along
     else { out->block_beg = L; out->first_byte = 0; }
+    out->block_end = R;
+    return MTH_HOST_OK;
+}
+
+int mth_host_plan_straddle_run(mth_host_t *h, int rank, int world, mth_host_straddle_run_t *out) {
+    if (!h || !out || world < 1 || rank < 0 || rank >= world) return MTH_HOST_ERR_INVALID;
+    mth_host_bgzf_t bz;
+    const int rc = mth_host_bgzf_blocks(h, &bz);
+    if (rc != MTH_HOST_OK) return rc;
+    const BgzfMap &m = *h->bgzf;
+    uint64_t D, d_off, E;
+    data_blocks(h, m, D, d_off, E);
+    memset(out, 0, sizeof *out);
+    out->entry = rank == 0 ? h->header_bytes : MTH_HOST_STRADDLE_ENTRY_GUESS;
+    if (D >= E) return MTH_HOST_OK;                       // no record at all: every run is empty
+    out->block_beg = rank == 0 ? 0 : size_cut(m, D, E, rank, world);     // (run 0 brings the header blocks: its entry is the header's end)
+    out->block_end = size_cut(m, D, E, rank + 1, world);
+    out->ahead_end = out->block_end;
+    for (uint64_t ahead = 0; out->ahead_end < E && ahead < MTH_HOST_STRADDLE_LOOKAHEAD;) ahead += m.isize[out->ahead_end++];
+    return MTH_HOST_OK;
+}
+
+int mth_host_plan_shard_straddle(mth_host_t *h, const mth_host_straddle_row_t *rows, uint64_t n_rows, int rank, int world, int64_t halo_bp,
+                                 mth_host_shard_t *out) {
+    if (!h || !rows || !out || world < 1 || rank < 0 || rank >= world || halo_bp < 0) return MTH_HOST_ERR_INVALID;
+    mth_host_bgzf_t bz;
+    const int rc = mth_host_bgzf_blocks(h, &bz);
+    if (rc != MTH_HOST_OK) return rc;
+    const BgzfMap &m = *h->bgzf;
+    uint64_t D, d_off, E;
+    data_blocks(h, m, D, d_off, E);
+    if (n_rows < E) return MTH_HOST_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->tid_beg = -1; out->tid_end = INT32_MAX;
+    if (D >= E) { out->block_beg = out->block_end = 0; out->first_byte = 0; return MTH_HOST_OK; }   // no record at all
+    auto fail = [&](const char *why) { h->last_error = std::string("the record table of the file does not hold: ") + why; return MTH_HOST_ERR_FORMAT; };
+    for (uint64_t b = D; b < E; ++b) {
+        const mth_host_straddle_row_t &r = rows[b];
+        if (r.exit == MTH_HOST_STRADDLE_EXIT_BAD) return fail("a block's chain does not go on (corrupt record, or a table that was not verified)");
+        if (r.start != MTH_HOST_STRADDLE_NO_START && (r.start >= m.isize[b] || r.ref_id < -1 || r.pos < -1)) return fail("a record start outside its block, or without a readable refID / pos");
+    }
+    if (rows[D].start != d_off) return fail("the first record does not start at the header's end");
+    auto has = [&](uint64_t b) { return rows[b].start != MTH_HOST_STRADDLE_NO_START; };
+    auto key = [&](uint64_t b, int32_t &t, int32_t &p) { t = rows[b].ref_id < 0 ? INT32_MAX : rows[b].ref_id; p = rows[b].pos; };   // refID -1 (no contig) sorts last
+    // a cut by compressed size, moved forward to the next block in which a record starts
+    auto cut = [&](int k) { uint64_t b = size_cut(m, D, E, k, world); while (b < E && !has(b)) ++b; return b; };
+    const uint64_t B0 = cut(rank), B1 = cut(rank + 1);
+    uint64_t L = D, R = E;
+    if (rank > 0) {
+        if (B0 >= E) { out->tid_beg = INT32_MAX; out->pos_beg = 0; L = E; }
+        else {
+            int32_t t, p;
+            key(B0, t, p);
+            out->tid_beg = t; out->pos_beg = p;
+            // left halo: back to the block in which the last record starts that starts before p - halo_bp (or on an earlier contig)
+            L = B0;
+            while (L > D) {
+                --L;
+                if (!has(L)) continue;                    // inside one record: passed over (D has a start, the loop ends on one)
+                int32_t tj, pj;
+                key(L, tj, pj);
+                if (tj != t || (int64_t)pj < (int64_t)p - halo_bp) break;
+            }
+        }
+    }
+    if (rank < world - 1 && B1 < E) {
+        int32_t t, p;
+        key(B1, t, p);
+        out->tid_end = t; out->pos_end = p;
+        // right halo: the blocks in which reads start exactly at p ...
+        R = B1 + 1;
+        while (R < E) {
+            int32_t tj, pj;
+            if (has(R)) { key(R, tj, pj); if (tj != t || pj != p) break; }
+            ++R;
+        }
+        // ... and on to the block that holds the END of the last record that starts in them
+        for (uint64_t left = rows[R - 1].exit; R < E && left > 0; ++R) left -= std::min<uint64_t>(left, m.isize[R]);
+    }
+    const bool empty = out->tid_beg == out->tid_end && out->pos_beg == out->pos_end;
+    if (empty || L >= R) { out->block_beg = out->block_end = L; out->first_byte = 0; return MTH_HOST_OK; }
+    if (L <= D) { out->block_beg = 0; out->first_byte = h->header_bytes; }    // from the top of the file: the header comes along
+    else { out->block_beg = L; out->first_byte = rows[L].start; }             // an exact record start (as mth_host_plan_region_at_record's)
     out->block_end = R;
     return MTH_HOST_OK;
 }

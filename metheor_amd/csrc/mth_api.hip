@@ -500,6 +500,7 @@ int mth_reset(mth_ctx_t *ctx) {
     ctx->f_rows_bound = 0;
     for (uint64_t &k : ctx->multi_stats) k = 0;
     ctx->carry_bytes = 0;                  // mth_bgzf_decode_straddle: the unfinished record of the previous call
+    ctx->scan_valid = false;               // mth_bgzf_straddle_scan: nothing left to rescan
     return MTH_OK;
 }
 

@@ -163,6 +163,13 @@ struct mth_ctx {
     // the other), and the bytes of the record the previous call's stream ended in (they come first in the next call's stream)
     mth::DevBuf inf_links, inf_carry;
     uint64_t carry_bytes = 0;
+    // mth_bgzf_straddle_scan: the run's inflated bytes (inf_raw), block table (inf_tab) and links (inf_links) stay for
+    // mth_bgzf_straddle_rescan until the next call that inflates (or mth_reset)
+    bool scan_valid = false;
+    uint64_t scan_n_run = 0, scan_total = 0;
+    uint64_t *scan_uoff = nullptr;
+    uint32_t *scan_isize = nullptr;
+    int scan_cur = 0;
     // `tag` (mth_tag.hip): the genome (contigs back to back), per-contig offsets + header lengths, per-record work arrays,
     // and the host copies mth_tag_records hands out
     mth::DevBuf tag_genome, tag_goff, tag_ncol, tag_coloff, tag_xmlen, tag_cols, tag_xm;

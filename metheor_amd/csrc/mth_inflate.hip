@@ -30,6 +30,16 @@
 // ERRB_FORMAT: block_size < 32, or a finished stream that ends inside a record) and decode_core as ever.  A call whose stream ends
 // inside a record keeps the bytes from that record's start on the device (ctx->inf_carry); they come first in the next call's
 // stream, whose block 0 then begins at offset 0.
+//
+// mth_bgzf_straddle_scan: the same scheme one level up, for the shards of a multi-GPU run over such a file.  A RUN of blocks is
+// inflated and its chain found from a guessed entry (block 0 guesses like the others), nothing is decoded, and the caller verifies
+// the runs against each other as the rounds verify the blocks: run r must enter where run r - 1 left.  Two things differ.  No block
+// of a guessed run has a certain entry, so an exit is believed only as far as the next block: where a block has no guess, or leaves
+// at or past the end of the block behind it, the chain breaks and that block keeps its own guess; k_straddle_keys counts the breaks
+// and such a run is scanned again.  And
+// the stream carries look-ahead blocks behind the run, so a record that ends beyond it leaves at p + 4 + block_size, a value the
+// next run is held against.  The second pass, mth_bgzf_straddle_rescan, takes the true entry and the state the context kept
+// (inflated bytes, block table, links): repair rounds from block 0, no copy and no inflate.
 #include "mth_ctx.h"
 
 namespace mth {
@@ -498,7 +508,8 @@ constexpr uint64_t STR_PAST = 1ull << 62;     // exit of a walk that cannot go o
 
 // mismatch / first_bad: blocks that do not enter where their predecessor left, and the first of them (k_straddle_check);
 // tail: where the unfinished (or bogus) record starts, else the stream's end
-struct StrState { uint32_t mismatch, first_bad, repaired, pad_; unsigned long long tail; };
+// broken: blocks of a scan from a guess that do not continue their predecessor's chain (k_straddle_keys)
+struct StrState { uint32_t mismatch, first_bad, repaired, broken; unsigned long long tail; };
 struct StrArgs {
     const uint8_t *raw;            // the call's stream: the carry, then the inflated blocks
     const uint64_t *uoff;          // per block: offset of its bytes in raw (block 0 also owns the carry in front of it)
@@ -514,6 +525,10 @@ struct StrArgs {
     uint64_t *rec_off;                       // fill: record offsets + the closing offset
     int last;                                // fill: the stream ends here and may not end inside a record (MTH_STRADDLE_LAST)
     uint32_t *err;
+    // mth_bgzf_straddle_scan (n_blocks = the run's blocks; raw / total also hold the look-ahead behind them):
+    int scan;                                // a record whose block_size is readable and leads past the stream leaves at that offset, not STR_PAST
+    int guess_first;                         // block 0 guesses like every other block and is its own reference (str_want)
+    mth_straddle_row_t *rows;                // k_straddle_keys: one row per block of the run
 };
 __device__ __forceinline__ uint32_t str_ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 // do the 36 bytes at p look like the fixed part of a BAM record (SAM spec 4.2)?  next = where its block_size leads.
@@ -539,7 +554,7 @@ __global__ __launch_bounds__(256) void k_straddle_guess(const StrArgs a) {
     if (blk >= a.n_blocks) return;
     const uint64_t b0 = blk ? uni64(a.uoff[blk]) : 0ull, b1 = uni64(a.uoff[blk]) + uni(a.isize[blk]);
     uint64_t g = STR_NONE;
-    if (b0 <= a.first_byte) {
+    if (b0 <= a.first_byte && !a.guess_first) {
         g = a.first_byte;                        // the records start in (or after) this block: no guess needed
     } else {
         for (uint64_t q = b0; q < b1; q += 64) {
@@ -569,6 +584,7 @@ __device__ __forceinline__ uint64_t str_walk(const StrArgs &a, uint32_t blk, uin
             bogus = (int32_t)bs < 32;
             cut = !bogus && p + 4 + (uint64_t)bs > a.total;
         }
+        if (!FILL && a.scan && cut && p + 4 <= a.total) { ++n; return p + 4 + (uint64_t)bs; }   // ends in blocks the caller did not pass: a value
         if (cut || bogus) {
             if (FILL) {
                 if (bogus || a.last) atomicOr(a.err, (uint32_t)ERRB_FORMAT);
@@ -599,7 +615,20 @@ __global__ __launch_bounds__(256) void k_straddle_walk(const StrArgs a) {
 // to change, a wrong entry would only move on, one block per round, with the correction chasing it.  A predecessor can agree and
 // still be wrong (two guesses on one chain of decoys); walking from a wrong offset nearly always ends on an unreadable block_size,
 // so an exit that says "cannot go on" is believed only of the block whose predecessors are final.
-__device__ __forceinline__ uint64_t str_want(const StrArgs &a, uint32_t blk) { return blk ? a.exit_in[blk - 1] : a.first_byte; }
+// A scan from a guess has no block whose entry is certain: block 0 has no reference but itself, and what a chain head says about the
+// blocks behind it is believed only as far as the NEXT block.  A block whose predecessor found no guess, or left at or past this
+// block's end (STR_PAST; a block_size read at a wrong offset -- the look-alike 4 bytes before a record start of profiles/
+// straddle_walk.md leads 5.5 MB on, and block after block would take that exit over its own good guess, one per round; or a record
+// that does cover the block), keeps its own guess: the chain breaks there and a new one starts.  k_straddle_keys counts the breaks;
+// a run with one is scanned again from its true entry, where the first block in doubt IS certain and a record over k blocks costs
+// its k rounds.
+__device__ __forceinline__ bool str_breaks(const StrArgs &a, uint32_t blk) {
+    return a.guess_first && blk && (a.entry_in[blk - 1] == STR_NONE || a.exit_in[blk - 1] >= a.uoff[blk] + a.isize[blk]);
+}
+__device__ __forceinline__ uint64_t str_want(const StrArgs &a, uint32_t blk) {
+    if (a.guess_first && (blk == 0 || str_breaks(a, blk))) return a.entry_in[blk];
+    return blk ? a.exit_in[blk - 1] : a.first_byte;
+}
 __global__ __launch_bounds__(256) void k_straddle_check(const StrArgs a) {
     const uint32_t blk = blockIdx.x * 256 + threadIdx.x;
     if (blk >= a.n_blocks || a.entry_in[blk] == str_want(a, blk)) return;
@@ -614,13 +643,31 @@ __global__ __launch_bounds__(256) void k_straddle_repair(const StrArgs a) {
     const uint64_t want = str_want(a, blk);
     if (entry != want) {
         const bool pred_agrees = blk == 0 || a.entry_in[blk - 1] == str_want(a, blk - 1);
-        if (blk == a.st->first_bad || (pred_agrees && want < STR_PAST)) {
+        // (want <= total: an exit past the stream -- STR_PAST, or under `scan` where a block_size read at a wrong offset leads -- is
+        // believed only of the first block in doubt)
+        if (blk == a.st->first_bad || (pred_agrees && want <= a.total)) {
             entry = want;
             x = str_walk<false>(a, blk, entry, a.uoff[blk] + a.isize[blk], n);
             atomicAdd(&a.st->repaired, 1u);
         }
     }
     a.entry_out[blk] = entry; a.exit_out[blk] = x; a.cnt_out[blk] = n;
+}
+// mth_bgzf_straddle_scan: the settled chain as one row per block -- a thread per block reads refID and pos of the first record that
+// starts in it from the contiguous stream (the 12 bytes may lie across the block's end: the look-ahead holds them)
+__global__ __launch_bounds__(256) void k_straddle_keys(const StrArgs a) {
+    const uint32_t blk = blockIdx.x * 256 + threadIdx.x;
+    if (blk >= a.n_blocks) return;
+    const uint64_t b0 = a.uoff[blk], b1 = b0 + a.isize[blk], e = a.entry_in[blk], x = a.exit_in[blk];
+    mth_straddle_row_t r;
+    r.start = MTH_STRADDLE_NO_START; r.ref_id = r.pos = INT32_MIN; r.pad_ = 0;
+    if (e != STR_NONE && e >= b0 && e < b1) {
+        r.start = (uint32_t)(e - b0);
+        if (e + 12 <= a.total) { r.ref_id = (int32_t)str_ld32(a.raw + e + 4); r.pos = (int32_t)str_ld32(a.raw + e + 8); }
+    }
+    r.exit = (x >= STR_PAST || x < b1) ? MTH_STRADDLE_EXIT_BAD : x - b1;
+    a.rows[blk] = r;
+    if (str_breaks(a, blk)) atomicAdd(&a.st->broken, 1u);
 }
 
 }  // namespace mth
@@ -647,6 +694,7 @@ static int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, cons
                           const uint32_t *isize, uint64_t n_blocks, uint64_t &total, uint64_t *&d_uoff, uint32_t *&d_isize, uint64_t stream_base = 0) {
     if (n_blocks >= (1ull << 31)) return fail(ctx, MTH_ERR_CAPACITY, "too many BGZF blocks in one call: split the file");
     MTH_ENTER(ctx);
+    ctx->scan_valid = false;                  // inf_raw / inf_tab are this call's now
     hipStream_t s = ctx->stream;
     const size_t nb = (size_t)n_blocks;
     // output offsets of the blocks + validation of the table against the byte range given
@@ -787,7 +835,126 @@ static int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, cons
     return MTH_OK;
 }
 
+// per block, two generations of (entry, exit, count) behind the state words: a round reads one and writes the other
+struct StrLinks { StrState *st; uint64_t *entry[2], *exit_[2]; uint32_t *cnt[2]; };
+static int straddle_links(mth_ctx *ctx, size_t nb, StrLinks &k) {
+    const size_t gen = nb * 8;
+    MTH_HIP(ctx, ctx->inf_links.reserve(64 + 4 * gen + 2 * nb * 4 + 16, ctx->stream));
+    uint8_t *const lk = static_cast<uint8_t *>(ctx->inf_links.p);
+    k.st = reinterpret_cast<StrState *>(lk);
+    k.entry[0] = reinterpret_cast<uint64_t *>(lk + 64); k.entry[1] = reinterpret_cast<uint64_t *>(lk + 64 + gen);
+    k.exit_[0] = reinterpret_cast<uint64_t *>(lk + 64 + 2 * gen); k.exit_[1] = reinterpret_cast<uint64_t *>(lk + 64 + 3 * gen);
+    k.cnt[0] = reinterpret_cast<uint32_t *>(lk + 64 + 4 * gen); k.cnt[1] = reinterpret_cast<uint32_t *>(lk + 64 + 4 * gen + nb * 4);
+    return MTH_OK;
+}
+// rounds: separate launches, the host reads one mismatch counter per round; generation `cur` is final when nothing mismatches
+// (settled), else the round bound was reached
+static int straddle_rounds(mth_ctx *ctx, StrArgs &a, const StrLinks &k, int &cur, uint32_t &rounds, bool &settled) {
+    hipStream_t s = ctx->stream;
+    const dim3 per_thread((a.n_blocks + 255) / 256);
+    rounds = 0;
+    settled = false;
+    for (;;) {
+        const uint32_t none[2] = {0u, 0xffffffffu};                  // mismatch, first_bad
+        MTH_HIP(ctx, hipMemcpyAsync(k.st, none, sizeof none, hipMemcpyHostToDevice, s));
+        a.entry_in = k.entry[cur]; a.exit_in = k.exit_[cur]; a.cnt_in = k.cnt[cur];
+        a.entry_out = k.entry[cur ^ 1]; a.exit_out = k.exit_[cur ^ 1]; a.cnt_out = k.cnt[cur ^ 1];
+        { LaunchTimer lt(ctx, K_STR_REPAIR); hipLaunchKernelGGL(k_straddle_check, per_thread, dim3(256), 0, s, a); }
+        uint32_t mismatch = 0;
+        MTH_HIP(ctx, hipMemcpyAsync(&mismatch, &k.st->mismatch, 4, hipMemcpyDeviceToHost, s));
+        MTH_HIP(ctx, hipStreamSynchronize(s));
+        if (mismatch == 0) { settled = true; break; }
+        if (rounds == MTH_STRADDLE_MAX_ROUNDS) break;
+        { LaunchTimer lt(ctx, K_STR_REPAIR); hipLaunchKernelGGL(k_straddle_repair, per_thread, dim3(256), 0, s, a); }
+        cur ^= 1;
+        ++rounds;
+    }
+    return MTH_OK;
+}
+static const char *const kNotSettled = "the record offsets did not settle within the round bound (records far longer than a BGZF block, or data that looks like record headers): use the host walk";
+
+// the rounds of a scan from the state the context holds, then the rows and the run's summary
+static int straddle_scan_finish(mth_ctx *ctx, uint64_t first_byte, int guess_first, mth_straddle_row_t *rows, mth_straddle_run_t *run, mth_straddle_info_t *info) {
+    hipStream_t s = ctx->stream;
+    const size_t nb = ctx->scan_n_run;
+    StrLinks k;
+    int rc = straddle_links(ctx, nb, k);
+    if (rc) return rc;
+    StrArgs a{};
+    a.raw = ctx->inf_raw.as<uint8_t>(); a.uoff = ctx->scan_uoff; a.isize = ctx->scan_isize; a.n_blocks = (uint32_t)nb;
+    a.first_byte = first_byte; a.total = ctx->scan_total; a.st = k.st; a.err = &ctx->d_state->err;
+    a.scan = 1; a.guess_first = guess_first;
+    uint32_t rounds = 0;
+    bool settled = false;
+    if ((rc = straddle_rounds(ctx, a, k, ctx->scan_cur, rounds, settled))) return rc;
+    StrState hs{};
+    if ((rc = sync_and_check(ctx))) return rc;              // a corrupt block
+    if (!settled) {
+        MTH_HIP(ctx, hipMemcpy(&hs, k.st, sizeof hs, hipMemcpyDeviceToHost));
+        if (info) { info->rounds = rounds; info->repaired_blocks = hs.repaired; }
+        ctx->scan_valid = false;
+        return fail(ctx, MTH_ERR_UNALIGNED, kNotSettled);
+    }
+    MTH_HIP(ctx, ctx->inf_base.reserve(nb * sizeof(mth_straddle_row_t) + 16, s));
+    a.entry_in = k.entry[ctx->scan_cur]; a.exit_in = k.exit_[ctx->scan_cur];
+    a.rows = ctx->inf_base.as<mth_straddle_row_t>();
+    { LaunchTimer lt(ctx, K_STR_WALK); hipLaunchKernelGGL(k_straddle_keys, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, a); }
+    uint64_t e0 = 0;
+    MTH_HIP(ctx, hipMemcpyAsync(rows, a.rows, nb * sizeof(mth_straddle_row_t), hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipMemcpyAsync(&e0, a.entry_in, 8, hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipMemcpyAsync(&hs, k.st, sizeof hs, hipMemcpyDeviceToHost, s));
+    MTH_HIP(ctx, hipStreamSynchronize(s));
+    if (info) { info->rounds = rounds; info->repaired_blocks = hs.repaired; }
+    if (run) {
+        // a chain that breaks inside the run says nothing past the break: no entry to hold the true one against
+        run->entry = (e0 == STR_NONE || hs.broken) ? MTH_STRADDLE_ENTRY_GUESS : e0;
+        run->exit = rows[nb - 1].exit;                      // past the last block of the run = past the run
+    }
+    return MTH_OK;
+}
+
 extern "C" {
+
+int mth_bgzf_straddle_scan(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
+                           const uint32_t *isize, uint64_t n_blocks, uint64_t n_run, uint64_t entry, mth_straddle_row_t *rows,
+                           mth_straddle_run_t *run, mth_straddle_info_t *info) {
+    if (!ctx || !rows || !file || !coff || !csize || !isize || n_run == 0 || n_run > n_blocks) return MTH_ERR_INVALID;
+    if (info) *info = mth_straddle_info_t{0, 0, 0};
+    ctx->carry_bytes = 0;                     // the stream of a scan is its own
+    uint64_t total = 0, *d_uoff = nullptr;
+    uint32_t *d_isize = nullptr;
+    int rc = inflate_blocks(ctx, file, n_bytes, coff, csize, isize, n_blocks, total, d_uoff, d_isize);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t nb = (size_t)n_run;
+    ctx->scan_n_run = n_run; ctx->scan_total = total; ctx->scan_uoff = d_uoff; ctx->scan_isize = d_isize; ctx->scan_cur = 0;
+    StrLinks k;
+    if ((rc = straddle_links(ctx, nb, k))) return rc;
+    MTH_HIP(ctx, hipMemsetAsync(k.st, 0, sizeof(StrState), s));
+    const bool guess = entry == MTH_STRADDLE_ENTRY_GUESS;
+    StrArgs a{};
+    a.raw = ctx->inf_raw.as<uint8_t>(); a.uoff = d_uoff; a.isize = d_isize; a.n_blocks = (uint32_t)nb;
+    a.first_byte = guess ? 0 : entry; a.total = total; a.st = k.st; a.err = &ctx->d_state->err;
+    a.scan = 1; a.guess_first = guess ? 1 : 0;
+    a.entry_out = k.entry[0];
+    { LaunchTimer lt(ctx, K_STR_GUESS); hipLaunchKernelGGL(k_straddle_guess, dim3((uint32_t)((nb + 3) / 4)), dim3(256), 0, s, a); }
+    a.entry_in = k.entry[0]; a.exit_out = k.exit_[0]; a.cnt_out = k.cnt[0];
+    { LaunchTimer lt(ctx, K_STR_WALK); hipLaunchKernelGGL((k_straddle_walk<false>), dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, s, a); }
+    ctx->scan_valid = true;
+    return straddle_scan_finish(ctx, a.first_byte, a.guess_first, rows, run, info);
+}
+
+int mth_bgzf_straddle_rescan(mth_ctx_t *ctx, uint64_t entry, mth_straddle_row_t *rows, mth_straddle_run_t *run, mth_straddle_info_t *info) {
+    if (!ctx || !rows || entry == MTH_STRADDLE_ENTRY_GUESS) return MTH_ERR_INVALID;
+    if (info) *info = mth_straddle_info_t{0, 0, 0};
+    if (!ctx->scan_valid) return fail(ctx, MTH_ERR_INVALID, "mth_bgzf_straddle_rescan: the context holds no scan (another load call came in between)");
+    MTH_ENTER(ctx);
+    StrLinks k;
+    int rc = straddle_links(ctx, (size_t)ctx->scan_n_run, k);
+    if (rc) return rc;
+    MTH_HIP(ctx, hipMemsetAsync(k.st, 0, sizeof(StrState), ctx->stream));
+    return straddle_scan_finish(ctx, entry, 0, rows, run, info);
+}
 
 int mth_bgzf_stage(mth_ctx_t *ctx, const void *file, uint64_t n_bytes) {
     if (!ctx || (n_bytes && !file)) return MTH_ERR_INVALID;
@@ -866,15 +1033,12 @@ int mth_bgzf_decode_straddle(mth_ctx_t *ctx, const void *file, uint64_t n_bytes,
         tail = 0;                             // nothing but the carry: still unfinished
         if (carry && (flags & MTH_STRADDLE_LAST)) return fail(ctx, MTH_ERR_FORMAT, "the BAM stream ends inside a record");
     } else {
-        // per block, two generations of (entry, exit, count): a round reads one and writes the other
-        const size_t gen = nb * 8;
-        MTH_HIP(ctx, ctx->inf_links.reserve(64 + 4 * gen + 2 * nb * 4 + 16, s));
+        StrLinks k;
+        if ((rc = straddle_links(ctx, nb, k))) return rc;
         MTH_HIP(ctx, ctx->inf_base.reserve((nb + 1) * 8 + 16, s));
-        uint8_t *const lk = static_cast<uint8_t *>(ctx->inf_links.p);
-        StrState *const st = reinterpret_cast<StrState *>(lk);
-        uint64_t *const entry[2] = {reinterpret_cast<uint64_t *>(lk + 64), reinterpret_cast<uint64_t *>(lk + 64 + gen)};
-        uint64_t *const exit_[2] = {reinterpret_cast<uint64_t *>(lk + 64 + 2 * gen), reinterpret_cast<uint64_t *>(lk + 64 + 3 * gen)};
-        uint32_t *const cnt[2] = {reinterpret_cast<uint32_t *>(lk + 64 + 4 * gen), reinterpret_cast<uint32_t *>(lk + 64 + 4 * gen + nb * 4)};
+        StrState *const st = k.st;
+        uint64_t *const *const entry = k.entry;
+        uint32_t *const *const cnt = k.cnt;
         MTH_HIP(ctx, hipMemsetAsync(st, 0, sizeof(StrState), s));
         StrArgs a{};
         a.raw = ctx->inf_raw.as<uint8_t>(); a.uoff = d_uoff; a.isize = d_isize; a.n_blocks = (uint32_t)nb;
@@ -882,33 +1046,18 @@ int mth_bgzf_decode_straddle(mth_ctx_t *ctx, const void *file, uint64_t n_bytes,
         const dim3 per_thread((uint32_t)((nb + 255) / 256));
         a.entry_out = entry[0];
         { LaunchTimer lt(ctx, K_STR_GUESS); hipLaunchKernelGGL(k_straddle_guess, dim3((uint32_t)((nb + 3) / 4)), dim3(256), 0, s, a); }
-        a.entry_in = entry[0]; a.exit_out = exit_[0]; a.cnt_out = cnt[0];
+        a.entry_in = entry[0]; a.exit_out = k.exit_[0]; a.cnt_out = cnt[0];
         { LaunchTimer lt(ctx, K_STR_WALK); hipLaunchKernelGGL((k_straddle_walk<false>), per_thread, dim3(256), 0, s, a); }
-        // rounds: separate launches, the host reads one mismatch counter per round; generation `cur` is final when nothing mismatches
         int cur = 0;
         uint32_t rounds = 0;
         bool settled = false;
-        for (;;) {
-            const uint32_t none[2] = {0u, 0xffffffffu};                  // mismatch, first_bad
-            MTH_HIP(ctx, hipMemcpyAsync(st, none, sizeof none, hipMemcpyHostToDevice, s));
-            a.entry_in = entry[cur]; a.exit_in = exit_[cur]; a.cnt_in = cnt[cur];
-            a.entry_out = entry[cur ^ 1]; a.exit_out = exit_[cur ^ 1]; a.cnt_out = cnt[cur ^ 1];
-            { LaunchTimer lt(ctx, K_STR_REPAIR); hipLaunchKernelGGL(k_straddle_check, per_thread, dim3(256), 0, s, a); }
-            uint32_t mismatch = 0;
-            MTH_HIP(ctx, hipMemcpyAsync(&mismatch, &st->mismatch, 4, hipMemcpyDeviceToHost, s));
-            MTH_HIP(ctx, hipStreamSynchronize(s));
-            if (mismatch == 0) { settled = true; break; }
-            if (rounds == MTH_STRADDLE_MAX_ROUNDS) break;
-            { LaunchTimer lt(ctx, K_STR_REPAIR); hipLaunchKernelGGL(k_straddle_repair, per_thread, dim3(256), 0, s, a); }
-            cur ^= 1;
-            ++rounds;
-        }
+        if ((rc = straddle_rounds(ctx, a, k, cur, rounds, settled))) return rc;
         StrState hs{};
         if (!settled) {
             if ((rc = sync_and_check(ctx))) return rc;      // a corrupt block explains it better
             MTH_HIP(ctx, hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
             if (info) { info->rounds = MTH_STRADDLE_MAX_ROUNDS; info->repaired_blocks = hs.repaired; }
-            return fail(ctx, MTH_ERR_UNALIGNED, "the record offsets did not settle within the round bound (records far longer than a BGZF block, or data that looks like record headers): use the host walk");
+            return fail(ctx, MTH_ERR_UNALIGNED, kNotSettled);
         }
         unsigned long long tot_rec = 0;
         rc = scan_u32_to_u64(ctx, cnt[cur], (uint32_t)nb, 0ull, ctx->inf_base.as<unsigned long long>(), &tot_rec);

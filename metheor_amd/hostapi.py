@@ -9,7 +9,7 @@ _LIB = None
 
 SYMBOLS = [
     "mth_host_open", "mth_host_close", "mth_host_last_error", "mth_host_notes", "mth_host_n_refs", "mth_host_ref_name",
-    "mth_host_ref_len", "mth_host_ref_tid", "mth_host_first_flag", "mth_host_set_xm_min_mapq", "mth_host_decode", "mth_host_decode_stream", "mth_host_bgzf_blocks", "mth_host_plan_shard", "mth_host_plan_region", "mth_host_plan_region_at_record", "mth_host_cpg_set_keys", "mth_host_n_reads", "mth_host_n_cpgs",
+    "mth_host_ref_len", "mth_host_ref_tid", "mth_host_first_flag", "mth_host_set_xm_min_mapq", "mth_host_decode", "mth_host_decode_stream", "mth_host_bgzf_blocks", "mth_host_plan_shard", "mth_host_plan_straddle_run", "mth_host_plan_shard_straddle", "mth_host_plan_region", "mth_host_plan_region_at_record", "mth_host_cpg_set_keys", "mth_host_n_reads", "mth_host_n_cpgs",
     "mth_host_read_tid", "mth_host_read_start", "mth_host_read_end", "mth_host_read_mapq",
     "mth_host_read_fwd", "mth_host_cpg_off", "mth_host_cpg_pos", "mth_host_cpg_rel", "mth_host_format_f32", "mth_host_write_synthetic_bam",
     "mth_host_write_synthetic_bam_multi", "mth_host_write_synthetic_bam_repeat", "mth_host_header_text", "mth_host_path", "mth_host_sam_format", "mth_host_fasta_open", "mth_host_fasta_close",
@@ -26,6 +26,15 @@ class _Shard(C.Structure):     # mth_host_shard_t
     _fields_ = [("block_beg", C.c_uint64), ("block_end", C.c_uint64), ("first_byte", C.c_uint64),
                 ("tid_beg", C.c_int32), ("pos_beg", C.c_int32), ("tid_end", C.c_int32), ("pos_end", C.c_int32)]
 
+
+class _StraddleRun(C.Structure):     # mth_host_straddle_run_t
+    _fields_ = [("block_beg", C.c_uint64), ("block_end", C.c_uint64), ("ahead_end", C.c_uint64), ("entry", C.c_uint64)]
+
+
+# mth_host_straddle_row_t (the layout of metheor_hip.h's mth_straddle_row_t), as a numpy record
+STRADDLE_ROW = np.dtype([("start", np.uint32), ("ref_id", np.int32), ("pos", np.int32), ("pad_", np.uint32), ("exit", np.uint64)])
+STRADDLE_NO_START = 0xffffffff
+STRADDLE_EXIT_BAD = (1 << 64) - 1
 
 WINDOW_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)   # mth_host_window_cb
 
@@ -64,6 +73,8 @@ def lib():
             getattr(L, "mth_host_" + f).argtypes = [vp]; getattr(L, "mth_host_" + f).restype = vp
         L.mth_host_bgzf_blocks.argtypes = [vp, vp]
         L.mth_host_plan_shard.argtypes = [vp, C.c_int, C.c_int, C.c_int64, vp]
+        L.mth_host_plan_straddle_run.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.mth_host_plan_shard_straddle.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int64, vp]
         L.mth_host_plan_region.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp]
         L.mth_host_plan_region_at_record.argtypes = L.mth_host_plan_region.argtypes
         L.mth_host_format_f32.argtypes = [C.c_float, C.c_char_p]
@@ -184,6 +195,25 @@ class BamFile:
         """mth_host_plan_shard: the BGZF blocks shard `rank` of `world` loads and the (tid, pos) interval it owns"""
         sh = _Shard()
         rc = self.L.mth_host_plan_shard(self.h, int(rank), int(world), int(halo_bp), C.byref(sh))
+        if rc != 0:
+            raise HostError(rc, self.L.mth_host_last_error(self.h).decode())
+        return dict(block_beg=int(sh.block_beg), block_end=int(sh.block_end), first_byte=int(sh.first_byte),
+                    beg=(int(sh.tid_beg), int(sh.pos_beg)), end=(int(sh.tid_end), int(sh.pos_end)))
+
+    def plan_straddle_run(self, rank, world):
+        """mth_host_plan_straddle_run: the blocks run `rank` of `world` scans, its look-ahead, its entry (None: a guess)"""
+        r = _StraddleRun()
+        rc = self.L.mth_host_plan_straddle_run(self.h, int(rank), int(world), C.byref(r))
+        if rc != 0:
+            raise HostError(rc, self.L.mth_host_last_error(self.h).decode())
+        return dict(block_beg=int(r.block_beg), block_end=int(r.block_end), ahead_end=int(r.ahead_end),
+                    entry=None if r.entry == (1 << 64) - 1 else int(r.entry))
+
+    def plan_shard_straddle(self, rows, rank, world, halo_bp=65536):
+        """mth_host_plan_shard_straddle: plan_shard from the file's verified record table (STRADDLE_ROW, a row per block)"""
+        rows = np.ascontiguousarray(rows, STRADDLE_ROW)
+        sh = _Shard()
+        rc = self.L.mth_host_plan_shard_straddle(self.h, rows.ctypes.data, len(rows), int(rank), int(world), int(halo_bp), C.byref(sh))
         if rc != 0:
             raise HostError(rc, self.L.mth_host_last_error(self.h).decode())
         return dict(block_beg=int(sh.block_beg), block_end=int(sh.block_end), first_byte=int(sh.first_byte),
