@@ -10,7 +10,11 @@
 //                   tile, decided per wave of 256 consecutive reads on the scalar unit from the element before the wave and
 //                   the wave's last read (ballots + popcounts where a boundary is crossed; nothing per read but the
 //                   compares).  <1>, for every other kernel: "first read starting at or after q*32 bp", four reads a thread.
-//   k_pdr_lpmd_tile one 256-thread workgroup per 4096-bp tile of the contig.  The tile's site
+//   k_pdr_lpmd_tile one workgroup per 4096-bp tile of the contig: 128 threads for pipelined batches with 8-bit relative positions (two waves, each
+//                   taking two chunks of 64 reads per loop trip on two register sets whose loads travel half a trip apart; a thread
+//                   compacts 32 positions; no counter margins, 17.8 KB of LDS, NINE workgroups on a CU -- with four waves per
+//                   workgroup a SIMD's 8 wave slots allow 8), 256 threads for 16-bit ones and for a batch outside a pipelined run, where
+//                   the kernel has the chip to itself (MTH_TILE_B=128|256 forces either; profiles/tile_two_waves.md).  The tile's site
 //                   accumulators are DENSE in LDS (one 32-bit word per reference position holding both
 //                   16-bit counts, 16 KiB; tiles with > 65535 candidate reads run two half-tile passes with
 //                   32-bit counters), so the scatter is an LDS atomic and HBM only sees the streamed SoA.
@@ -395,7 +399,7 @@ __device__ __forceinline__ uint32_t tile_compact(const TileArgs &a, const uint32
             below = __builtin_amdgcn_alignbit(below, (x.x & 0xffffu) - a.min_cov, 31);
         }
 #endif
-        qual = ~below & (PER == 32 ? 0xffffffffu : (1u << PER) - 1u);
+        qual = ~below & (uint32_t)((1ull << PER) - 1ull);      // (PER = 32, the 128-thread form: every bit of the mask is a position)
     }
     {   // only the pass's positions [0, Wp) exist (the last tile of a region is short)
         const int32_t left = (int32_t)Wp - tid * PER;
@@ -403,13 +407,20 @@ __device__ __forceinline__ uint32_t tile_compact(const TileArgs &a, const uint32
     }
     const uint32_t mine = __builtin_popcount(qual);
     const uint32_t incl = wave_scan_incl(mine);
-    static_assert(B == 256, "four wave totals in one 16-byte LDS word");
+    static_assert(B == 256 || B == 128, "the B / 64 wave totals in one 16- or 8-byte LDS word");
     if (lane == 63) wave_off[wave] = incl;
     __syncthreads();
     // every thread adds up the totals of the waves before its own (a single thread doing the prefix cost a second barrier)
-    const uint4 wt = *reinterpret_cast<const uint4 *>(wave_off);
-    const uint32_t before = (wave > 0 ? wt.x : 0u) + (wave > 1 ? wt.y : 0u) + (wave > 2 ? wt.z : 0u);
-    const uint32_t total = wt.x + wt.y + wt.z + wt.w;
+    uint32_t before, total;
+    if constexpr (B == 256) {
+        const uint4 wt = *reinterpret_cast<const uint4 *>(wave_off);
+        before = (wave > 0 ? wt.x : 0u) + (wave > 1 ? wt.y : 0u) + (wave > 2 ? wt.z : 0u);
+        total = wt.x + wt.y + wt.z + wt.w;
+    } else {
+        const uint2 wt = *reinterpret_cast<const uint2 *>(wave_off);
+        before = wave > 0 ? wt.x : 0u;
+        total = wt.x + wt.y;
+    }
     uint32_t o = out_base + before + incl - mine;
     SiteRec *__restrict__ out = a.scratch + (size_t)t * W;
     while (qual) {
@@ -472,37 +483,28 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
     // (the caller has cleared the counters and built the slot tables)
 
     uint32_t lp_c = 0, lp_d = 0, n_read = 0, n_valid = 0, bad = 0;
-    uint32_t i = lo + tid;
-    int32_t s = 0;
-    uint32_t o0 = 0, n = 0, mq = 0;
     // PF (the plain-load instantiation with 8-bit relpos): ONE round trip per iteration.  Only the read's two call offsets are
     // fetched ahead (two registers); its calls, relative positions, start and mapq are then requested together -- the calls
     // unconditionally: every read of such a tile has its 8-slot window inside the arrays (safe_hi) -- and the NEXT read's
     // offsets right behind them, so that they travel during this read's arithmetic.  (The version that fetched the whole next
     // record ahead cost the registers of the 8th wave; profiles/r02_tile_latency.md.)
     constexpr bool PF = MTH_TILE_PF && !CLAMP && sizeof(RelT) == 1 && NB == 8;
-    uint32_t o1 = 0;
-    if (PF) { if (i < hi) { o0 = a.cpg_off[i]; o1 = a.cpg_off[i + 1]; } }
-    else if (i < hi) { s = a.read_start[i]; o0 = a.cpg_off[i]; n = a.cpg_off[i + 1] - o0; mq = a.read_mapq[i]; }
-    while (i < hi) {
-        const uint32_t inext = i + B;
-        const bool more = inext < hi;
-        uint32_t v[NB];
-        int32_t r[NB];
-        uint32_t rraw0 = 0, rraw1 = 0;                         // PACKED: the 8 relpos bytes as they lie in memory
-        uint32_t o0n = 0, o1n = 0;
-        if constexpr (PF) {
-            n = o1 - o0;
-            const uint32_t *__restrict__ cp = a.cpg_pos + o0;
+    constexpr bool TWO = PF && B == 128;       // two chunks of reads per trip, every load unconditional: see the loop below
+    // PF: what a read's iteration asks for at its top (calls, relative positions, start, mapq)
+    auto request = [&](const uint32_t i, const uint32_t o0, uint32_t (&v)[NB], uint32_t &rraw0, uint32_t &rraw1, int32_t &s, uint32_t &mq) __attribute__((always_inline)) {
+        const uint32_t *__restrict__ cp = a.cpg_pos + o0;
 #pragma unroll
-            for (int k4 = 0; k4 < NB / 4; ++k4) {
-                const u32x4_a4 x = *reinterpret_cast<const u32x4_a4 *>(cp + 4 * k4);
-                v[4 * k4] = x.x; v[4 * k4 + 1] = x.y; v[4 * k4 + 2] = x.z; v[4 * k4 + 3] = x.w;
-            }
-            if (do_lp) { const u32x2_a1 x = *reinterpret_cast<const u32x2_a1 *>(reinterpret_cast<const RelT *>(a.cpg_rel) + o0); rraw0 = x.x; rraw1 = x.y; }
-            s = a.read_start[i]; mq = a.read_mapq[i];
-            if (more) { o0n = a.cpg_off[inext]; o1n = a.cpg_off[inext + 1]; }
+        for (int k4 = 0; k4 < NB / 4; ++k4) {
+            const u32x4_a4 x = *reinterpret_cast<const u32x4_a4 *>(cp + 4 * k4);
+            v[4 * k4] = x.x; v[4 * k4 + 1] = x.y; v[4 * k4 + 2] = x.z; v[4 * k4 + 3] = x.w;
         }
+        if (do_lp || TWO) { const u32x2_a1 x = *reinterpret_cast<const u32x2_a1 *>(reinterpret_cast<const RelT *>(a.cpg_rel) + o0); rraw0 = x.x; rraw1 = x.y; }
+        s = a.read_start[i]; mq = a.read_mapq[i];
+    };
+    // One read per lane, 64 reads per wave: everything between a read's loads and its scatter.  The lanes of a wave that have a read call it
+    // together (the votes below are among them).  PF: v / rraw0 / rraw1 arrive requested; otherwise they are loaded here.
+    auto chunk = [&](const int32_t s, const uint32_t mq, const uint32_t o0, const uint32_t n, uint32_t (&v)[NB], uint32_t rraw0, uint32_t rraw1) __attribute__((always_inline)) {
+        int32_t r[NB];
         const bool owned = (s >= T0) && (s < T1);
         // lpmd.rs:176-179
         const bool lp_ok = do_lp && owned && (mq >= a.lpmd_min_qual);
@@ -703,11 +705,64 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
             }
         }
         }   // work
-        // the thread's next read.  (Requesting it together with the calls above and parking it in LDS -- one round
-        // trip per iteration instead of two -- was built and measured: no change, profiles/r02_tile_latency.md.)
-        if (PF) { o0 = o0n; o1 = o1n; }
-        else if (more) { s = a.read_start[inext]; o0 = a.cpg_off[inext]; n = a.cpg_off[inext + 1] - o0; mq = a.read_mapq[inext]; }
-        i = inext;
+    };
+    // TWO (the 128-thread form of the PF loop): a wave takes two chunks of 64 reads per trip on two register sets, A and B -- wave w the
+    // chunks lo + 128 j + 64 w for j = 2 m and 2 m + 1 -- one inlined body called twice.  The two are requested half a trip apart: while
+    // the wave works on one set, the loads of the other are on their way,
+    //     offsets A(t+1), request B(t) | chunk A(t) | offsets B(t+1), request A(t+1) | chunk B(t) | ...
+    // so that after a tile's first round trips a wave waits for memory only where a chunk's arithmetic is shorter than the latency (two
+    // waves per workgroup have half the loads of four in flight otherwise: 0.0896-0.0911 ms a step against 0.0806-0.0817; both chunks
+    // requested together at the top of a trip: 0.0837-0.0856; profiles/tile_two_waves.md).  A wait for the older of two requests has
+    // to know how many loads were issued behind it, which the compiler counts along straight code only: every load here is unconditional,
+    // with the index of a read that does not exist clamped to the tile's last read (hi <= safe_hi: the 8-slot window of every read
+    // below hi lies inside the arrays, and cpg_off has an entry behind every read) -- a second chunk that does not exist costs its five
+    // loads, not its arithmetic (a branch on the exec mask).
+    if constexpr (TWO) {
+        uint32_t ia = lo + tid, ib = ia + B;
+        if (ia < hi) {
+            const uint32_t last = hi - 1u;
+            uint32_t oa0, oa1, ob0, ob1, va[NB], vb[NB], ra0, ra1, rb0, rb1, mqa, mqb;
+            int32_t sa, sb;
+            { const uint32_t jb = min(ib, last); oa0 = a.cpg_off[ia]; oa1 = a.cpg_off[ia + 1]; ob0 = a.cpg_off[jb]; ob1 = a.cpg_off[jb + 1]; }
+            request(ia, oa0, va, ra0, ra1, sa, mqa);
+            while (ia < hi) {
+                const uint32_t ian = ia + 2 * B, ibn = ib + 2 * B;
+                const uint32_t ja = min(ian, last), jb = min(ibn, last);
+                // (loads come back in the order they were asked for: the offsets go out before the request of the same half, so that the
+                // wait for them, half a trip on, leaves that request in flight)
+                const uint32_t oa0n = a.cpg_off[ja], oa1n = a.cpg_off[ja + 1];
+                request(min(ib, last), ob0, vb, rb0, rb1, sb, mqb);
+                chunk(sa, mqa, oa0, oa1 - oa0, va, ra0, ra1);
+                const uint32_t ob0n = a.cpg_off[jb], ob1n = a.cpg_off[jb + 1];
+                request(ja, oa0n, va, ra0, ra1, sa, mqa);
+                if (ib < hi) chunk(sb, mqb, ob0, ob1 - ob0, vb, rb0, rb1);
+                ia = ian; ib = ibn; oa0 = oa0n; oa1 = oa1n; ob0 = ob0n; ob1 = ob1n;
+            }
+        }
+    } else {
+        uint32_t i = lo + tid;
+        int32_t s = 0;
+        uint32_t o0 = 0, o1 = 0, n = 0, mq = 0;
+        if (PF) { if (i < hi) { o0 = a.cpg_off[i]; o1 = a.cpg_off[i + 1]; } }
+        else if (i < hi) { s = a.read_start[i]; o0 = a.cpg_off[i]; n = a.cpg_off[i + 1] - o0; mq = a.read_mapq[i]; }
+        while (i < hi) {
+            const uint32_t inext = i + B;
+            const bool more = inext < hi;
+            uint32_t v[NB];
+            uint32_t rraw0 = 0, rraw1 = 0;                         // PACKED: the 8 relpos bytes as they lie in memory
+            uint32_t o0n = 0, o1n = 0;
+            if constexpr (PF) {
+                n = o1 - o0;
+                request(i, o0, v, rraw0, rraw1, s, mq);
+                if (more) { o0n = a.cpg_off[inext]; o1n = a.cpg_off[inext + 1]; }
+            }
+            chunk(s, mq, o0, n, v, rraw0, rraw1);
+            // the thread's next read.  (Requesting it together with the calls above and parking it in LDS -- one round
+            // trip per iteration instead of two -- was built and measured: no change, profiles/r02_tile_latency.md.)
+            if (PF) { o0 = o0n; o1 = o1n; }
+            else if (more) { s = a.read_start[inext]; o0 = a.cpg_off[inext]; n = a.cpg_off[inext + 1] - o0; mq = a.read_mapq[inext]; }
+            i = inext;
+        }
     }
 #ifdef MTH_TILE_TRACE
     g_tk4 = __builtin_readcyclecounter();
@@ -739,8 +794,11 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
 #ifndef MTH_TILE_OCC
 #define MTH_TILE_OCC 8      // workgroups per CU the kernel is compiled for (7 / 6 / 5: 72 / 80 / 96 VGPRs -- A/B in round 5)
 #endif
+// (the second launch bound is waves per SIMD.  Four waves per workgroup: 8 workgroups are the 8 waves a SIMD holds, 64 VGPRs each, whatever the
+// LDS would admit.  Two waves per workgroup, B = 128: the LDS decides -- without the counter margins a workgroup takes 17.8 KB and NINE fit a
+// CU's 160 KB, 18 waves, 5 on a SIMD at most and up to 102 VGPRs each; that ninth workgroup is what the two-wave form is for)
 template <int W, int B, int NB, typename RelT, int MG>
-__global__ __launch_bounds__(B, MTH_TILE_OCC) void k_pdr_lpmd_tile(const TileArgs a, const uint32_t ntiles) {
+__global__ __launch_bounds__(B, B == 128 ? 5 : MTH_TILE_OCC) void k_pdr_lpmd_tile(const TileArgs a, const uint32_t ntiles) {
     static_assert(MG == 0 || (MG >= 64 && MG % 4 == 0), "the wide passes keep their trash words in the high margin");
     __shared__ __attribute__((aligned(16))) uint32_t cnt[MG ? MG + W + MG : W + 64];   // [margin,] counters, then margin / one trash word per lane
     __shared__ uint32_t red[4][B / 64];
@@ -778,7 +836,7 @@ __global__ __launch_bounds__(B, MTH_TILE_OCC) void k_pdr_lpmd_tile(const TileArg
         for (int i = threadIdx.x; i < W / 4; i += B) reinterpret_cast<uint4 *>(cnt + MG)[i] = make_uint4(0, 0, 0, 0);
     };
     clear();
-    slot_tabs_init(tabs, threadIdx.x);
+    slot_tabs_init<B>(tabs, threadIdx.x);
     MTH_TK(1);
     __syncthreads();
     MTH_TK(2);
@@ -1519,11 +1577,15 @@ __global__ void k_pipe_seed(const DevState *__restrict__ st, DevState *__restric
 // ---------------------------------------------------------------------------------------------
 constexpr int DENSE_TILE_SHIFT = 12;   // the dense kernel's 4096-bp tiles
 constexpr int TILE_MARGIN = 256;   // counter margins on either side of a tile for batches with max_span <= 256
+#ifndef MTH_TILE_B_DEFAULT
+#define MTH_TILE_B_DEFAULT 128     // threads per workgroup of the dense kernel on 8-bit relpos batches (launch_pdr_lpmd)
+#endif
 template <int W, int B, typename RelT>
 static void launch_tile(const TileArgs &a, uint32_t ntiles, hipStream_t s) {
     const uint32_t grid = ((ntiles + 7) / 8) * 8;   // whole rows of 8 XCDs (remap in the kernel)
     static const bool no_margin = getenv("MTH_TILE_NO_MARGIN") != nullptr;   // A/B switch
-    if (a.max_span <= TILE_MARGIN && !no_margin) hipLaunchKernelGGL((k_pdr_lpmd_tile<W, B, 8, RelT, TILE_MARGIN>), dim3(grid), dim3(B), 0, s, a, ntiles);
+    // (two waves per workgroup: never the margins -- their 2 KB are the ninth workgroup of a CU, worth more than the clamp per slot they save)
+    if (B == 256 && a.max_span <= TILE_MARGIN && !no_margin) hipLaunchKernelGGL((k_pdr_lpmd_tile<W, 256, 8, RelT, TILE_MARGIN>), dim3(grid), dim3(256), 0, s, a, ntiles);
     else hipLaunchKernelGGL((k_pdr_lpmd_tile<W, B, 8, RelT, 0>), dim3(grid), dim3(B), 0, s, a, ntiles);
 }
 
@@ -1731,6 +1793,14 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
     const char *runs_env = getenv("MTH_TILE_RUNS");          // (read per call: the tests switch it per case)
     const bool runs = wide_shift == 0 && b.cpg_rel != nullptr && b.n_cpgs < (1u << 30) && runs_env && atoi(runs_env) == 1;
     const uint32_t G = runs ? runs_grid(ntiles) : 0u;
+    // threads per workgroup of the one-tile-per-workgroup form: 128 (two waves, two chunks of reads per trip, nine workgroups on a CU;
+    // profiles/tile_two_waves.md) for pipelined batches with 8-bit relative positions, 256 for 16-bit ones (built for 256 only) and for
+    // a batch outside a pipelined run -- a job's first batch, MTH_PIPELINE=0, site discovery through a sink: alone on the chip the
+    // four-wave kernel is the faster one (75.8 against 82.2 us on config 2); the two-wave form wins where the index build, the gather
+    // and the other lane's tile kernel run beside it.  MTH_TILE_B=128 / 256 forces either for 8-bit batches (read per call: the tests
+    // run both in one process).
+    int tile_b = L ? MTH_TILE_B_DEFAULT : 256;
+    if (const char *e = getenv("MTH_TILE_B")) { const int k = atoi(e); if (k == 128 || k == 256) tile_b = k; }
     MTH_HIP(ctx, b_tile_cnt.reserve((size_t)ntiles * 4 * (runs ? 4 : 1), s));
     const uint32_t nbk = (ntiles + (1u << TILE_BUCKET_SHIFT) - 1) >> TILE_BUCKET_SHIFT;
     const uint32_t n_bucket_words = nbk * 5u;      // rows, 4 LPMD sums per bucket
@@ -1797,6 +1867,7 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
         if (wide_shift && fq && ntiles <= fq->max_tiles) { launch_tile_fused(a, *fq, ntiles, wide_shift, r8, s); fq->taken = true; fq->ntiles = ntiles; }
         else if (wide_shift) launch_tile_wide(a, ntiles, wide_shift, r8, s);
         else if (runs) launch_runs(a, ra, ntiles, G, s);
+        else if (r8 && tile_b == 128) launch_tile<(1 << DENSE_TILE_SHIFT), 128, uint8_t>(a, ntiles, s);
         else if (r8) launch_tile<(1 << DENSE_TILE_SHIFT), 256, uint8_t>(a, ntiles, s); else launch_tile<(1 << DENSE_TILE_SHIFT), 256, uint16_t>(a, ntiles, s);
     }
     {

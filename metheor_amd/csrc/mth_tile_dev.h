@@ -98,9 +98,12 @@ struct SlotTabs {
     uint32_t dtab[9][8];
     LpMask   m8[9][8];
 };
-__device__ __forceinline__ void slot_tabs_init(SlotTabs &T, const int tid) {      // needs >= 144 threads
-    if (tid < 144) (&T.m8[0][0].w0)[tid] = lpmd_bytes_mask((uint32_t)tid >> 4, ((uint32_t)tid >> 1) & 7u, (uint32_t)tid & 1u);
-    if (tid < 72) {
+// B = threads of the workgroup: 144 or more fill the tables in one step each (the loops fold into the guards they were), the dense
+// kernel's 128-thread form takes two for the mask table
+template <int B = 256>
+__device__ __forceinline__ void slot_tabs_init(SlotTabs &T, const int tid0) {
+    for (int tid = tid0; tid < 144; tid += B) (&T.m8[0][0].w0)[tid] = lpmd_bytes_mask((uint32_t)tid >> 4, ((uint32_t)tid >> 1) & 7u, (uint32_t)tid & 1u);
+    for (int tid = tid0; tid < 72; tid += B) {
         const uint32_t nn = (uint32_t)tid >> 3, c = (uint32_t)tid & 7u;
         T.mtab[nn][c] = c < nn ? 0xffffffffu : 0u;
         auto dead = [&](uint32_t k) { return k >= 8u ? 0x2400u : (k >= nn ? 0x400u * (k + 1u) : 0u); };
