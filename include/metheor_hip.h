@@ -543,6 +543,39 @@ typedef struct {
 int  mth_tag_set_genome(mth_ctx_t *ctx, int32_t n_refs, const int64_t *ref_len, const uint8_t *const *seq, const int64_t *seq_len);
 int  mth_tag_records(mth_ctx_t *ctx, const void *raw, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
                      int is_paired_end, mth_tag_out_t *out);
+/* mth_tag_set_genome with the FASTA read on the device: the same genome (bytes, offsets, header lengths) straight from the
+ * file's text, plain or bgzip-compressed -- what faidx_fetch_seq(name, 0, LN) returns for every contig, with no host pass over
+ * the bases.
+ *   file / n_bytes  the FASTA file in HOST memory (a read-only mapping will do)
+ *   blocks          NULL for plain text; for a BGZF file its block table as mth_bgzf_inflate takes it (payload offset / payload
+ *                   bytes / inflated bytes per block, blocks with isize 0 left out; the 8 trailer bytes of every block inside
+ *                   the file bytes)
+ *   rows[t]         per header contig, tid order: src_off = offset of base 0 in the UNCOMPRESSED stream (.fai column 3), n_bases =
+ *                   bases to take = min(LN + 1, .fai length), line_bases / line_width = .fai columns 4 and 5; name (may be NULL)
+ *                   only serves the messages
+ * The stream is taken in windows (a byte range of a plain file; a run of whole BGZF blocks, inflated and CRC-checked as
+ * mth_bgzf_inflate does) of METHEOR_FASTA_CHUNK bytes (default 256 MiB; at least one block), the next window's bytes travelling
+ * while k_fasta_pack gathers the current one: base i of a contig is the byte at src_off + (i / line_bases) * line_width +
+ * i % line_bases.  That equals what faidx keeps (the isgraph bytes from src_off on) exactly when every gathered byte is isgraph
+ * and every byte skipped between two gathered bases is not, and the kernel verifies just that for every byte of every contig's
+ * source span.  MTH_ERR_FORMAT: a contig's span leaves the stream ("FASTA shorter than its index says", found before anything is
+ * launched), the text does not have the layout the rows state (the message names the contig), or a BGZF block fails its inflate,
+ * ISIZE or CRC32.  A call that fails leaves the context's genome as it was. */
+typedef struct {
+    const uint64_t *coff;
+    const uint32_t *csize, *isize;
+    uint64_t        n_blocks;
+} mth_fasta_blocks_t;
+typedef struct {
+    uint64_t    src_off;
+    int64_t     n_bases, line_bases, line_width;
+    const char *name;
+} mth_fasta_row_t;
+int  mth_tag_set_genome_fasta(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const mth_fasta_blocks_t *blocks, int32_t n_refs,
+                              const int64_t *ref_len, const mth_fasta_row_t *rows);
+/* n bases of contig tid from base beg on, as the device genome holds them, to dst_host (MTH_ERR_INVALID past the bases the
+ * genome holds of the contig; MTH_ERR_STATE without a genome) */
+int  mth_tag_genome_fetch(mth_ctx_t *ctx, int32_t tid, int64_t beg, int64_t n, void *dst_host);
 /* derive the calls from the genome of mth_tag_set_genome instead of the records' XM:Z (what `metheor tag` followed by
  * the measure computes): applies to the following mth_decode_records / mth_bgzf_decode calls.  is_paired_end =
  * bamutil.rs:27-37.  enabled != 0 before mth_tag_set_genome: MTH_ERR_STATE.

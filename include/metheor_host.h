@@ -68,6 +68,35 @@ int  mth_host_fasta_open(const char *path, mth_fasta_t **out, char *errbuf, int 
 void mth_host_fasta_close(mth_fasta_t *f);
 const char *mth_host_fasta_last_error(const mth_fasta_t *f);
 int  mth_host_fasta_fetch(mth_fasta_t *f, const char *name, int64_t end_incl, const uint8_t **seq, int64_t *len);
+/* bgzip-compressed FASTA (genome.fa.gz + genome.fa.gz.fai; htslib's faidx reads it, tag.rs:412-431).  mth_host_fasta_open tells
+ * the kind of file by its first bytes: BGZF needs <path>.fai next to it (its offsets are those of the uncompressed stream; a
+ * .gzi is neither needed nor read: nothing here seeks) and the open fails without one, naming the index -- htslib would build it,
+ * this reader writes nothing; gzip that is not BGZF is refused as htslib refuses it; anything else is text, as before.
+ * There is no host inflate for FASTA: mth_host_fasta_fetch of a compressed file fails with a message that says so, and the bases
+ * are read on the device (mth_tag_set_genome_fasta in metheor_hip.h) from the two calls below, which serve plain files as well.
+ * mth_host_fasta_map: the file mapped read-only (populated) and, for a compressed file, its BGZF block table as
+ * mth_host_bgzf_blocks gives a BAM's (the same walk); stream_bytes = the uncompressed size.  Valid until close.
+ * mth_host_fasta_layout: where mth_host_fasta_fetch(name, end_incl) would read -- the layout row mth_tag_set_genome_fasta takes
+ * (the layout of mth_fasta_row_t): offset of base 0 in the uncompressed stream, min(end_incl + 1, length) bases, bases and bytes
+ * per line.  The errors and texts of the fetch: "sequence not in the FASTA: NAME", and "FASTA shorter than its index says: PATH"
+ * for a row whose last base lies past the end of the stream. */
+typedef struct {
+    const uint8_t  *file;
+    uint64_t        file_bytes;
+    uint64_t        stream_bytes;
+    int             compressed;      /* 1: BGZF, the table below is set; 0: text, no table */
+    const uint64_t *coff;
+    const uint32_t *csize, *isize;
+    uint64_t        n_blocks;
+} mth_host_fasta_map_t;
+typedef struct {
+    uint64_t    src_off;
+    int64_t     n_bases, line_bases, line_width;
+    const char *name;                /* the contig's name as the index holds it (valid until close) */
+} mth_host_fasta_row_t;
+int  mth_host_fasta_compressed(const mth_fasta_t *f);
+int  mth_host_fasta_map(mth_fasta_t *f, mth_host_fasta_map_t *out);
+int  mth_host_fasta_layout(mth_fasta_t *f, const char *name, int64_t end_incl, mth_host_fasta_row_t *row);
 
 /* Decode ALL remaining records of the file into one SoA held by the handle, in file order.
  * cpg_set_path may be NULL.  After success the arrays below are valid until close/decode. */

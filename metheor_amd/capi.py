@@ -16,7 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_decode_set_genome",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -41,6 +41,15 @@ class mth_decoded_t(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_cpgs", C.c_uint64), ("tid", C.c_void_p), ("start", C.c_void_p),
                 ("end", C.c_void_p), ("mapq", C.c_void_p), ("fwd", C.c_void_p), ("cpg_off", C.c_void_p),
                 ("cpg_pos", C.c_void_p), ("cpg_rel", C.c_void_p)]
+
+
+class mth_fasta_blocks_t(C.Structure):
+    _fields_ = [("coff", C.c_void_p), ("csize", C.c_void_p), ("isize", C.c_void_p), ("n_blocks", C.c_uint64)]
+
+
+class mth_fasta_row_t(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("n_bases", C.c_int64), ("line_bases", C.c_int64), ("line_width", C.c_int64),
+                ("name", C.c_char_p)]
 
 
 class mth_pdr_lpmd_params_t(C.Structure):
@@ -177,6 +186,8 @@ def lib():
         L.mth_bgzf_stage.argtypes = [vp, vp, C.c_uint64]
         L.mth_decode_reserve.argtypes = [vp, C.c_uint64, C.c_uint64]
         L.mth_tag_set_genome.argtypes = [vp, C.c_int32, vp, vp, vp]
+        L.mth_tag_set_genome_fasta.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, vp, vp]
+        L.mth_tag_genome_fetch.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp]
         L.mth_tag_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_tag_out_t)]
         L.mth_decode_set_genome.argtypes = [vp, C.c_int, C.c_int]
         L.mth_decoded_fetch.argtypes = [vp] * 9
@@ -578,6 +589,34 @@ class Engine:
         bufs = [np.frombuffer(bytes(c[1]), np.uint8) for c in contigs]
         ptr = (C.c_void_p * max(n, 1))(*[b.ctypes.data if len(b) else None for b in bufs])
         self._check(self.L.mth_tag_set_genome(self.h, n, ln, ptr, got))
+
+    def tag_set_genome_fasta(self, file_bytes, ref_len, rows, blocks=None):
+        """mth_tag_set_genome_fasta: the genome packed on the device from the FASTA file's bytes (bytes / uint8 array, host).
+        ref_len: the header's LN per contig; rows: per contig (src_off, n_bases, line_bases, line_width[, name]) or objects with
+        those attributes (hostapi.FastaRow); blocks: None for plain text, (coff, csize, isize) of a BGZF file"""
+        fb = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(file_bytes, np.uint8)
+        n = len(rows)
+        ln = (C.c_int64 * max(n, 1))(*[int(x) for x in ref_len])
+        rr = (mth_fasta_row_t * max(n, 1))()
+        for i, r in enumerate(rows):
+            t = r if isinstance(r, (tuple, list)) else (r.src_off, r.n_bases, r.line_bases, r.line_width, r.name)
+            rr[i].src_off, rr[i].n_bases, rr[i].line_bases, rr[i].line_width = int(t[0]), int(t[1]), int(t[2]), int(t[3])
+            nm = t[4] if len(t) > 4 else None
+            rr[i].name = nm.encode() if isinstance(nm, str) else nm
+        bp, keep = None, None
+        if blocks is not None:
+            coff = np.ascontiguousarray(blocks[0], np.uint64); csize = np.ascontiguousarray(blocks[1], np.uint32); isize = np.ascontiguousarray(blocks[2], np.uint32)
+            keep = (coff, csize, isize)
+            b = mth_fasta_blocks_t(coff.ctypes.data, csize.ctypes.data, isize.ctypes.data, len(coff))
+            bp = C.addressof(b)
+        self._check(self.L.mth_tag_set_genome_fasta(self.h, fb.ctypes.data if fb.size else None, fb.size, bp, n, ln, rr))
+        del keep
+
+    def tag_genome_fetch(self, tid, beg, n):
+        """mth_tag_genome_fetch: n bases of contig tid from base beg on, as the device genome holds them -> bytes"""
+        out = np.zeros(int(n), np.uint8)
+        self._check(self.L.mth_tag_genome_fetch(self.h, int(tid), int(beg), int(n), out.ctypes.data if n else None))
+        return out.tobytes()
 
     def tag_records(self, raw, rec_off, is_paired_end=False):
         """raw: the inflated BAM records (bytes), rec_off: uint64[n_rec + 1]; -> list of XM strings (bytes), tag.rs:130-384"""

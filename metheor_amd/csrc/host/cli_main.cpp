@@ -391,6 +391,12 @@ struct Genome {
     std::vector<std::vector<uint8_t>> seqs;
     std::vector<const uint8_t *> ptr;
     std::vector<int64_t> ln, got;
+    // the device route (mth_tag_set_genome_fasta): a bgzip-compressed FASTA, or a plain one under METHEOR_GENOME_DEVICE=1.  The
+    // FASTA stays open: every context packs its genome from the one mapping, by the one set of layout rows
+    bool device = false;
+    mth_fasta_t *fa = nullptr;
+    mth_host_fasta_map_t map{};
+    std::vector<mth_fasta_row_t> rows;
 };
 Genome g_genome;
 
@@ -416,15 +422,70 @@ void genome_fetch(mth_fasta_t *fa, mth_host_t *h, Genome &g, F on_fail) {
     }
     g.loaded = true;
 }
-void genome_upload(mth_ctx_t *ctx, const Genome &g) {
+bool genome_wants_device(const mth_fasta_t *fa) {
+    const char *e = getenv("METHEOR_GENOME_DEVICE");
+    return mth_host_fasta_compressed(fa) || (e && atoi(e) != 0);
+}
+// the device route's host part: the mapping (populated) and every @SQ contig's layout row, with the fetch's errors and texts
+template <class F>
+void genome_layout(mth_fasta_t *fa, mth_host_t *h, Genome &g, F on_fail) {
+    auto fail = [&] { on_fail(); die("Error fetching reference genome sequence.: " + std::string(mth_host_fasta_last_error(fa))); };
+    const int n_refs = mth_host_n_refs(h);
+    g.ln.assign((size_t)n_refs, 0); g.rows.assign((size_t)n_refs, mth_fasta_row_t{});
+    for (int t = 0; t < n_refs; ++t) {
+        mth_host_fasta_row_t r;
+        g.ln[(size_t)t] = mth_host_ref_len(h, t);
+        if (mth_host_fasta_layout(fa, mth_host_ref_name(h, t), g.ln[(size_t)t], &r) != 0) fail();
+        g.rows[(size_t)t] = mth_fasta_row_t{r.src_off, r.n_bases, r.line_bases, r.line_width, r.name};
+    }
+    if (mth_host_fasta_map(fa, &g.map) != 0) fail();
+    g.fa = fa; g.device = true; g.loaded = true;
+}
+// the genome into a context: the host copy's bases, or the FASTA's bytes packed on the device.  A plain file whose text does not
+// have the layout its index states (METHEOR_GENOME_DEVICE=1: the device route verifies every byte) falls back to the host read,
+// which gives today's result or today's error; on a compressed file the same finding ends the run.
+template <class F>
+void genome_upload(mth_ctx_t *ctx, mth_host_t *h, Genome &g, F on_fail) {
+    static std::mutex mu;                  // --gpus N: the shards share g
+    bool device;
+    { std::lock_guard<std::mutex> lk(mu); device = g.device; }
+    if (device) {
+        const bool timing = getenv("METHEOR_TIMING") != nullptr;
+        if (timing) mth_timing_enable(ctx, 1);
+        int rc;
+        {
+            Phase ph("  genome FASTA -> device");
+            const mth_fasta_blocks_t blk{g.map.coff, g.map.csize, g.map.isize, g.map.n_blocks};
+            rc = mth_tag_set_genome_fasta(ctx, g.map.file, g.map.file_bytes, g.map.compressed ? &blk : nullptr, (int32_t)g.ln.size(), g.ln.data(), g.rows.data());
+        }
+        if (timing) {
+            for (const char *k : {"k_inflate", "k_crc32", "k_fasta_pack"}) {
+                double ms = 0;
+                uint64_t n = 0;
+                if (mth_timing_get(ctx, k, &ms, &n) == MTH_OK && n) fprintf(stderr, "[metheor timing]     genome/%-14s %.3f ms in %llu launches\n", k, ms * (double)n, (unsigned long long)n);
+            }
+            mth_timing_reset(ctx); mth_timing_enable(ctx, 0);
+        }
+        if (rc == MTH_OK) return;
+        if (rc != MTH_ERR_FORMAT) check(ctx, rc);
+        std::lock_guard<std::mutex> lk(mu);
+        if (g.map.compressed) { on_fail(); die("Error fetching reference genome sequence.: " + std::string(mth_last_error(ctx))); }
+        if (timing) fprintf(stderr, "[metheor timing]   genome FASTA -> device refused (%s): host read instead\n", mth_last_error(ctx));
+        if (g.device) { genome_fetch(g.fa, h, g, on_fail); g.device = false; }
+    }
     check(ctx, mth_tag_set_genome(ctx, (int32_t)g.ln.size(), g.ln.data(), g.ptr.data(), g.got.data()));
 }
 // --genome of a measure: read once, before any output file exists
 template <class F>
 void genome_read_once(mth_host_t *h, F on_fail) {
     if (g_genome.path.empty() || g_genome.loaded) return;
-    Phase ph("  genome FASTA read");
     mth_fasta_t *fa = genome_open(g_genome.path, on_fail);
+    if (genome_wants_device(fa)) {
+        Phase ph("  genome FASTA map + layout");
+        genome_layout(fa, h, g_genome, on_fail);
+        return;
+    }
+    Phase ph("  genome FASTA read");
     genome_fetch(fa, h, g_genome, on_fail);
     mth_host_fasta_close(fa);
 }
@@ -708,7 +769,7 @@ bool load_on_device(Input &in, const char *cpg_set, CtxFuture &cf) {
     in.ctx = cf.get();
     if (!g_genome.path.empty()) {
         Phase ph("  genome -> device");
-        genome_upload(in.ctx, g_genome);
+        genome_upload(in.ctx, in.h, g_genome, [] {});
         check(in.ctx, mth_decode_set_genome(in.ctx, 1, first_flag >= 0 && (first_flag & 1)));
     }
     if (cpg_set) check(in.ctx, mth_decode_set_cpg_filter(in.ctx, keys, n_keys, 1));
@@ -1514,8 +1575,9 @@ int run_tag(const Args &a) {
     {
         Phase ph("genome -> device");
         Genome g;
-        genome_fetch(fa, h, g, [&] { fflush(out); });
-        genome_upload(ctx, g);
+        if (genome_wants_device(fa)) genome_layout(fa, h, g, [&] { fflush(out); });
+        else genome_fetch(fa, h, g, [&] { fflush(out); });
+        genome_upload(ctx, h, g, [&] { fflush(out); });
     }
     printf("Done!\n");
     fflush(stdout);

@@ -192,6 +192,25 @@ int mth_host_fasta_fetch(mth_fasta_t *f, const char *name, int64_t end_incl, con
     return MTH_HOST_OK;
 }
 
+int mth_host_fasta_compressed(const mth_fasta_t *f) { return f && f->fa.compressed() ? 1 : 0; }
+int mth_host_fasta_map(mth_fasta_t *f, mth_host_fasta_map_t *out) {
+    if (!f || !out) return MTH_HOST_ERR_INVALID;
+    const BgzfMap *m = f->fa.map(f->last_error);
+    if (!m) return MTH_HOST_ERR_OPEN;
+    memset(out, 0, sizeof *out);
+    out->file = m->file; out->file_bytes = m->file_bytes; out->stream_bytes = f->fa.stream_bytes();
+    out->compressed = f->fa.compressed() ? 1 : 0;
+    if (out->compressed) { out->coff = m->coff.data(); out->csize = m->csize.data(); out->isize = m->isize.data(); out->n_blocks = m->coff.size(); }
+    return MTH_HOST_OK;
+}
+int mth_host_fasta_layout(mth_fasta_t *f, const char *name, int64_t end_incl, mth_host_fasta_row_t *row) {
+    if (!f || !name || !row) return MTH_HOST_ERR_INVALID;
+    Fasta::Row r;
+    if (!f->fa.layout(name, end_incl, r, f->last_error)) return MTH_HOST_ERR_FORMAT;
+    row->src_off = r.src_off; row->n_bases = r.n_bases; row->line_bases = r.line_bases; row->line_width = r.line_width; row->name = r.key;
+    return MTH_HOST_OK;
+}
+
 int mth_host_set_xm_min_mapq(mth_host_t *h, int min_mapq) {
     if (!h) return MTH_HOST_ERR_INVALID;
     h->xm_min_mapq = min_mapq;

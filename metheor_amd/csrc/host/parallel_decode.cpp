@@ -231,7 +231,7 @@ static void prefault_parallel(const uint8_t *file, size_t fsz) {
     for (auto &x : th) x.join();
 }
 
-bool bgzf_map(const std::string &path, BgzfMap &out, std::string &err) {
+bool file_map(const std::string &path, BgzfMap &out, std::string &err) {
     const int fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) { err = "cannot open " + path; return false; }
     struct stat st;
@@ -243,6 +243,13 @@ bool bgzf_map(const std::string &path, BgzfMap &out, std::string &err) {
     out.file = file; out.file_bytes = fsz;
     out.coff.clear(); out.csize.clear(); out.isize.clear();
     prefault_parallel(file, fsz);
+    return true;
+}
+
+bool bgzf_map(const std::string &path, BgzfMap &out, std::string &err) {
+    if (!file_map(path, out, err)) return false;
+    const uint8_t *const file = out.file;
+    const size_t fsz = out.file_bytes;
     size_t o = 0;
     while (o < fsz) {
         if (o + 18 > fsz || file[o] != 31 || file[o + 1] != 139 || file[o + 2] != 8 || !(file[o + 3] & 4)) { err = "not a BGZF file (bad block header)"; return false; }

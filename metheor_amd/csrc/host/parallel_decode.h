@@ -35,6 +35,8 @@ struct BgzfMap {
     ~BgzfMap();
 };
 bool bgzf_map(const std::string &path, BgzfMap &out, std::string &err);
+// the mapping alone (populated the same way), the table left empty: any file
+bool file_map(const std::string &path, BgzfMap &out, std::string &err);
 
 // header_bytes: uncompressed size of the BAM header (records start right after it).
 // target: --cpg-set keys (tid << 32 | pos) or nullptr.  err_kind: 1 format/IO, 2 record without XM.

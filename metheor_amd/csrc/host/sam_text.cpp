@@ -23,6 +23,7 @@
 
 #include "../../../include/metheor_host.h"
 #include "bam_reader.h"
+#include "parallel_decode.h"
 #include "sam_text.h"
 
 namespace mthh {
@@ -342,8 +343,21 @@ bool Fasta::open(const std::string &path, std::string &err) {
     path_ = path;
     FILE *f = fopen(path.c_str(), "rb");
     if (!f) { err = (errno == ENOENT ? "file not found: " : "unable to open: ") + path; return false; }   // rust-htslib Error::FileNotFound
+    // the kind of file, from its first bytes: BGZF (gzip with FEXTRA and the BC subfield, SAM spec 4.1), other gzip, or text
+    uint8_t head[18];
+    const size_t nh = fread(head, 1, sizeof head, f);
     fclose(f);
+    if (nh >= 2 && head[0] == 31 && head[1] == 139) {
+        bool bc = false;
+        if (nh == sizeof head && head[2] == 8 && (head[3] & 4)) {
+            const uint32_t xlen = (uint32_t)head[10] | ((uint32_t)head[11] << 8);
+            bc = xlen >= 6 && head[12] == 'B' && head[13] == 'C' && head[14] == 2 && head[15] == 0;      // (bgzip writes it first)
+        }
+        if (!bc) { err = "gzip-compressed but not BGZF (recompress with bgzip; htslib refuses it too): " + path; return false; }
+        bgzf_ = true;
+    }
     std::ifstream fai(path + ".fai");
+    if (bgzf_ && !fai) { err = "a bgzip-compressed FASTA needs its index " + path + ".fai (`samtools faidx` makes it): " + path; return false; }
     if (fai) {
         std::string line;
         while (std::getline(fai, line)) {
@@ -390,6 +404,7 @@ bool Fasta::fetch(const std::string &name, int64_t end_incl, std::vector<uint8_t
     if (it == index_.end()) { err = "sequence not in the FASTA: " + name; return false; }
     const Entry &e = it->second;
     const int64_t n = std::min<int64_t>(end_incl + 1, e.length);         // faidx_fetch_seq(name, 0, end): [0, end] clipped to the sequence
+    if (bgzf_) { err = "a bgzip-compressed FASTA is read on the device (mth_tag_set_genome_fasta); there is no host inflate for it: " + path_; return false; }
     if (n <= 0) return true;
     FILE *f = fopen(path_.c_str(), "rb");
     if (!f) { err = "unable to open: " + path_; return false; }
@@ -402,6 +417,40 @@ bool Fasta::fetch(const std::string &name, int64_t end_incl, std::vector<uint8_t
     seq.reserve((size_t)n);
     for (size_t k = 0; k < got && (int64_t)seq.size() < n; ++k) if (isgraph(buf[k])) seq.push_back(buf[k]);   // faidx keeps isgraph() characters
     if ((int64_t)seq.size() != n) { err = "FASTA shorter than its index says: " + path_; return false; }
+    return true;
+}
+
+Fasta::Fasta() = default;
+Fasta::~Fasta() { delete map_; }
+
+const BgzfMap *Fasta::map(std::string &err) {
+    if (map_) return map_;
+    BgzfMap *m = new BgzfMap;
+    std::string e;
+    if (!(bgzf_ ? bgzf_map(path_, *m, e) : file_map(path_, *m, e))) { delete m; err = e + ": " + path_; return nullptr; }
+    stream_bytes_ = m->file_bytes;
+    if (bgzf_) { stream_bytes_ = 0; for (const uint32_t z : m->isize) stream_bytes_ += z; }
+    map_ = m;
+    return map_;
+}
+
+bool Fasta::layout(const std::string &name, int64_t end_incl, Row &row, std::string &err) {
+    const auto it = index_.find(name);
+    if (it == index_.end()) { err = "sequence not in the FASTA: " + name; return false; }
+    if (!map(err)) return false;
+    const Entry &e = it->second;
+    row = Row{};
+    row.key = it->first.c_str();
+    row.n_bases = std::max<int64_t>(0, std::min<int64_t>(end_incl + 1, e.length));
+    row.src_off = (uint64_t)e.offset; row.line_bases = e.line_bases; row.line_width = e.line_width;
+    if (row.n_bases == 0) return true;
+    // the contig's last wanted base inside the stream (what fetch finds out when its read comes back short)
+    const unsigned __int128 last = (unsigned __int128)(row.n_bases - 1);
+    const bool sane = e.offset >= 0 && e.line_bases > 0 && e.line_width >= e.line_bases;
+    if (!sane || (unsigned __int128)e.offset + last / (uint64_t)e.line_bases * (uint64_t)e.line_width + last % (uint64_t)e.line_bases + 1 > (unsigned __int128)stream_bytes_) {
+        err = "FASTA shorter than its index says: " + path_;
+        return false;
+    }
     return true;
 }
 

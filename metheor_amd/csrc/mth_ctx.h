@@ -174,6 +174,10 @@ struct mth_ctx {
     // and the host copies mth_tag_records hands out
     mth::DevBuf tag_genome, tag_goff, tag_ncol, tag_coloff, tag_xmlen, tag_cols, tag_xm;
     int32_t tag_n_refs = -1;
+    std::vector<uint64_t> tag_h_goff;        // host copy of the n_refs + 1 contig offsets (mth_tag_genome_fetch)
+    // mth_tag_set_genome_fasta (mth_fasta.hip): the genome being packed -- it becomes tag_genome only when the whole file has
+    // passed verification -- and the segment table + error word of the window in flight
+    mth::DevBuf fa_genome, fa_tab;
     // mth_decode_set_genome: the decode derives its calls from tag_genome (mth_decode_genome.hip) instead of XM:Z
     bool dec_genome = false, dec_genome_paired = false;
     unsigned long long tag_cols_total = 0;   // column scratch of the decode call in progress (count pass -> fill pass)
@@ -292,6 +296,9 @@ int stage_batch(mth_ctx *ctx, const mth_batch_t &b, mth_batch_t &dev, bool join 
 int scan_u32_to_u64(mth_ctx *ctx, const uint32_t *n, uint32_t count, unsigned long long base, unsigned long long *off,
                     unsigned long long *total_host);
 int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint64_t n_rec, int append, mth_decoded_t *out);
+// mth_tag.hip: the tail of the two genome entry points -- the genome's bytes are in ctx->tag_genome, contig t at off[t]: the
+// offsets and header lengths go up, the stream is drained and the genome is the context's from there on
+int genome_commit(mth_ctx *ctx, int32_t n_refs, const std::vector<uint64_t> &off, const int64_t *ref_len);
 // mth_tag.hip: the XM strings of n device-resident records into ctx->tag_xm (offsets tag_coloff, lengths tag_xmlen); *total = bytes
 int tag_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint32_t n, int is_paired_end, unsigned long long *total);
 struct DecArgs;

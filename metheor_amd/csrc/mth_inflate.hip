@@ -41,6 +41,7 @@
 // next run is held against.  The second pass, mth_bgzf_straddle_rescan, takes the true entry and the state the context kept
 // (inflated bytes, block table, links): repair rounds from block 0, no copy and no inflate.
 #include "mth_ctx.h"
+#include "mth_inflate.h"
 
 namespace mth {
 
@@ -48,8 +49,7 @@ namespace mth {
 // stops it.  A literal costs at most 15 bits (the direct-lookup width LROOT is not the code length limit: DEFLATE codes go up to 15
 // bits) = 120 KiB of input for 64 Ki literals; a match costs at most 15 + 5 + 15 + 13 bits and yields >= 3 bytes: less per output
 // byte.  The staging buffers carry 160 KiB of zeroed padding, so the bit reader's scalar loads always stay inside the allocation
-// and read defined bytes (the CRC / ISIZE checks then flag the block).
-constexpr size_t INF_FILE_PAD = 160 * 1024;
+// and read defined bytes (the CRC / ISIZE checks then flag the block): INF_FILE_PAD, mth_inflate.h.
 
 constexpr int LROOT = 10, DROOT = 9;          // direct-lookup bits of the literal/length and distance tables
 struct InflArgs {
@@ -688,10 +688,56 @@ static void crc_zero_operators(uint32_t (*mat)[32]) {
 
 // (Splitting a pageable host-to-device copy over 4 / 8 host threads that enqueue slices into the same stream was measured:
 // no gain at 4, slower at 8 -- profiles/r02_e2e.md.)
+namespace mth {
+
+int stage_take(mth_ctx *ctx, const void *file, uint64_t n_bytes, bool &staged) {
+    hipStream_t s = ctx->stream;
+    // the helper thread of the previous call (copying THIS call's bytes, if they were announced) has to be done first
+    if (ctx->stage_thread.joinable()) {
+        ctx->stage_thread.join();
+        if (ctx->stage_rc != MTH_OK) return fail(ctx, MTH_ERR_HIP, "staging the next chunk's file bytes failed");
+    }
+    staged = ctx->staged_src && ctx->staged_src == file && ctx->staged_bytes == n_bytes;
+    if (staged) {
+        // copied on the side stream while the previous chunk was in flight: take that buffer
+        std::swap(ctx->inf_file, ctx->inf_file2);
+        MTH_HIP(ctx, hipStreamWaitEvent(s, ctx->staged_ev, 0));
+    } else {
+        MTH_HIP(ctx, ctx->inf_file.reserve((size_t)n_bytes + INF_FILE_PAD, s));
+    }
+    ctx->staged_src = nullptr;
+    return MTH_OK;
+}
+
+int stage_start_next(mth_ctx *ctx) {
+    // the chunk announced by mth_bgzf_stage: its bytes travel on the side stream, from a helper thread (a pageable copy
+    // blocks its caller), while this call's kernels run.  The thread owns inf_file2 / copy_stream / staged_* until joined.
+    if (ctx->next_src && ctx->next_bytes) {
+        if (!ctx->copy_stream) {
+            MTH_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+            MTH_HIP(ctx, hipEventCreateWithFlags(&ctx->staged_ev, hipEventDisableTiming));
+        }
+        const void *src = ctx->next_src;
+        const uint64_t nbytes = ctx->next_bytes;
+        ctx->next_src = nullptr;
+        ctx->stage_rc = MTH_OK;
+        ctx->stage_thread = std::thread([ctx, src, nbytes] {
+            auto ok = [&](hipError_t e) { if (e != hipSuccess) ctx->stage_rc = MTH_ERR_HIP; return e == hipSuccess; };
+            if (!ok(hipSetDevice(ctx->device))) return;
+            if (!ok(ctx->inf_file2.reserve((size_t)nbytes + INF_FILE_PAD, ctx->copy_stream))) return;
+            if (!ok(hipMemcpyAsync(ctx->inf_file2.p, src, (size_t)nbytes, hipMemcpyHostToDevice, ctx->copy_stream))) return;
+            if (!ok(hipMemsetAsync(static_cast<uint8_t *>(ctx->inf_file2.p) + nbytes, 0, INF_FILE_PAD, ctx->copy_stream))) return;
+            if (!ok(hipEventRecord(ctx->staged_ev, ctx->copy_stream))) return;
+            ctx->staged_src = src; ctx->staged_bytes = nbytes;
+        });
+    }
+    return MTH_OK;
+}
+
 // stage the file bytes + block table and launch the inflate; on return d_uoff / d_isize point at the device table
 // (the blocks' output starts at stream_base in inf_raw; total includes it)
-static int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
-                          const uint32_t *isize, uint64_t n_blocks, uint64_t &total, uint64_t *&d_uoff, uint32_t *&d_isize, uint64_t stream_base = 0) {
+int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
+                   const uint32_t *isize, uint64_t n_blocks, uint64_t &total, uint64_t *&d_uoff, uint32_t *&d_isize, uint64_t stream_base) {
     if (n_blocks >= (1ull << 31)) return fail(ctx, MTH_ERR_CAPACITY, "too many BGZF blocks in one call: split the file");
     MTH_ENTER(ctx);
     ctx->scan_valid = false;                  // inf_raw / inf_tab are this call's now
@@ -706,20 +752,8 @@ static int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, cons
     }
     total = uoff[nb];
     // stage: compressed bytes (padded: the bit reader loads whole words), the table, the inflated stream
-    // the helper thread of the previous call (copying THIS call's bytes, if they were announced) has to be done first
-    if (ctx->stage_thread.joinable()) {
-        ctx->stage_thread.join();
-        if (ctx->stage_rc != MTH_OK) return fail(ctx, MTH_ERR_HIP, "staging the next chunk's file bytes failed");
-    }
-    const bool staged = ctx->staged_src && ctx->staged_src == file && ctx->staged_bytes == n_bytes;
-    if (staged) {
-        // copied on the side stream while the previous chunk was in flight: take that buffer
-        std::swap(ctx->inf_file, ctx->inf_file2);
-        MTH_HIP(ctx, hipStreamWaitEvent(s, ctx->staged_ev, 0));
-    } else {
-        MTH_HIP(ctx, ctx->inf_file.reserve((size_t)n_bytes + INF_FILE_PAD, s));
-    }
-    ctx->staged_src = nullptr;
+    bool staged = false;
+    { const int rc = stage_take(ctx, file, n_bytes, staged); if (rc) return rc; }
     MTH_HIP(ctx, ctx->inf_tab.reserve(nb * 24 + 64, s));
     MTH_HIP(ctx, ctx->inf_raw.reserve((size_t)total + 64, s));
     // METHEOR_COPY_PIECE_MB=k (default 0 = off): an in-line copy (the first chunk of a file, or every chunk under METHEOR_NO_STAGE)
@@ -743,27 +777,7 @@ static int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, cons
         MTH_HIP(ctx, hipMemcpyAsync(ctx->crc_mat.p, mat, sizeof mat, hipMemcpyHostToDevice, s));
         MTH_HIP(ctx, hipStreamSynchronize(s));            // mat is a local
     }
-    // the chunk announced by mth_bgzf_stage: its bytes travel on the side stream, from a helper thread (a pageable copy
-    // blocks its caller), while this call's kernels run.  The thread owns inf_file2 / copy_stream / staged_* until joined.
-    if (ctx->next_src && ctx->next_bytes) {
-        if (!ctx->copy_stream) {
-            MTH_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-            MTH_HIP(ctx, hipEventCreateWithFlags(&ctx->staged_ev, hipEventDisableTiming));
-        }
-        const void *src = ctx->next_src;
-        const uint64_t nbytes = ctx->next_bytes;
-        ctx->next_src = nullptr;
-        ctx->stage_rc = MTH_OK;
-        ctx->stage_thread = std::thread([ctx, src, nbytes] {
-            auto ok = [&](hipError_t e) { if (e != hipSuccess) ctx->stage_rc = MTH_ERR_HIP; return e == hipSuccess; };
-            if (!ok(hipSetDevice(ctx->device))) return;
-            if (!ok(ctx->inf_file2.reserve((size_t)nbytes + INF_FILE_PAD, ctx->copy_stream))) return;
-            if (!ok(hipMemcpyAsync(ctx->inf_file2.p, src, (size_t)nbytes, hipMemcpyHostToDevice, ctx->copy_stream))) return;
-            if (!ok(hipMemsetAsync(static_cast<uint8_t *>(ctx->inf_file2.p) + nbytes, 0, INF_FILE_PAD, ctx->copy_stream))) return;
-            if (!ok(hipEventRecord(ctx->staged_ev, ctx->copy_stream))) return;
-            ctx->staged_src = src; ctx->staged_bytes = nbytes;
-        });
-    }
+    { const int rc = stage_start_next(ctx); if (rc) return rc; }
     uint8_t *tab = static_cast<uint8_t *>(ctx->inf_tab.p);
     uint64_t *d_coff = reinterpret_cast<uint64_t *>(tab);
     d_uoff = reinterpret_cast<uint64_t *>(tab + nb * 8);
@@ -834,6 +848,8 @@ static int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, cons
     }
     return MTH_OK;
 }
+
+}  // namespace mth
 
 // per block, two generations of (entry, exit, count) behind the state words: a round reads one and writes the other
 struct StrLinks { StrState *st; uint64_t *entry[2], *exit_[2]; uint32_t *cnt[2]; };

@@ -75,6 +75,17 @@ int tag_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint32_t
     return MTH_OK;
 }
 
+int genome_commit(mth_ctx *ctx, int32_t n_refs, const std::vector<uint64_t> &off, const int64_t *ref_len) {
+    hipStream_t s = ctx->stream;
+    MTH_HIP(ctx, ctx->tag_goff.reserve(((size_t)n_refs + 1) * 8 + (size_t)n_refs * 8 + 16, s));
+    MTH_HIP(ctx, hipMemcpyAsync(ctx->tag_goff.p, off.data(), ((size_t)n_refs + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_refs) MTH_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->tag_goff.p) + ((size_t)n_refs + 1) * 8, ref_len, (size_t)n_refs * 8, hipMemcpyHostToDevice, s));
+    MTH_HIP(ctx, hipStreamSynchronize(s));                      // the caller's buffers may go away
+    ctx->tag_h_goff = off;
+    ctx->tag_n_refs = n_refs;
+    return MTH_OK;
+}
+
 }  // namespace mth
 
 using namespace mth;
@@ -91,13 +102,20 @@ int mth_tag_set_genome(mth_ctx_t *ctx, int32_t n_refs, const int64_t *ref_len, c
         off[t + 1] = off[t] + (uint64_t)seq_len[t];
     }
     MTH_HIP(ctx, ctx->tag_genome.reserve((size_t)off[n_refs] + 16, s));
-    MTH_HIP(ctx, ctx->tag_goff.reserve(((size_t)n_refs + 1) * 8 + (size_t)n_refs * 8 + 16, s));
     for (int32_t t = 0; t < n_refs; ++t)
         if (seq_len[t]) MTH_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->tag_genome.p) + off[t], seq[t], (size_t)seq_len[t], hipMemcpyHostToDevice, s));
-    MTH_HIP(ctx, hipMemcpyAsync(ctx->tag_goff.p, off.data(), ((size_t)n_refs + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_refs) MTH_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->tag_goff.p) + ((size_t)n_refs + 1) * 8, ref_len, (size_t)n_refs * 8, hipMemcpyHostToDevice, s));
-    MTH_HIP(ctx, hipStreamSynchronize(s));                      // the caller's buffers may go away
-    ctx->tag_n_refs = n_refs;
+    return genome_commit(ctx, n_refs, off, ref_len);
+}
+
+int mth_tag_genome_fetch(mth_ctx_t *ctx, int32_t tid, int64_t beg, int64_t n, void *dst_host) {
+    if (!ctx || beg < 0 || n < 0 || (n && !dst_host)) return MTH_ERR_INVALID;
+    if (ctx->tag_n_refs < 0) return fail(ctx, MTH_ERR_STATE, "mth_tag_set_genome has not been called");
+    if (tid < 0 || tid >= ctx->tag_n_refs) return fail(ctx, MTH_ERR_INVALID, "mth_tag_genome_fetch: no such contig");
+    const uint64_t o0 = ctx->tag_h_goff[(size_t)tid], o1 = ctx->tag_h_goff[(size_t)tid + 1];
+    if ((uint64_t)beg > o1 - o0 || (uint64_t)n > o1 - o0 - (uint64_t)beg) return fail(ctx, MTH_ERR_INVALID, "mth_tag_genome_fetch: the slice leaves the bases the genome holds of this contig");
+    MTH_ENTER(ctx);
+    MTH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n) MTH_HIP(ctx, hipMemcpy(dst_host, ctx->tag_genome.as<uint8_t>() + o0 + (uint64_t)beg, (size_t)n, hipMemcpyDeviceToHost));
     return MTH_OK;
 }
 

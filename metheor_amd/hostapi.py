@@ -13,13 +13,23 @@ SYMBOLS = [
     "mth_host_read_tid", "mth_host_read_start", "mth_host_read_end", "mth_host_read_mapq",
     "mth_host_read_fwd", "mth_host_cpg_off", "mth_host_cpg_pos", "mth_host_cpg_rel", "mth_host_format_f32", "mth_host_write_synthetic_bam",
     "mth_host_write_synthetic_bam_multi", "mth_host_write_synthetic_bam_repeat", "mth_host_header_text", "mth_host_path", "mth_host_sam_format", "mth_host_fasta_open", "mth_host_fasta_close",
-    "mth_host_fasta_last_error", "mth_host_fasta_fetch",
+    "mth_host_fasta_last_error", "mth_host_fasta_fetch", "mth_host_fasta_compressed", "mth_host_fasta_map", "mth_host_fasta_layout",
 ]
 
 
 class _Bgzf(C.Structure):      # mth_host_bgzf_t
     _fields_ = [("file", C.c_void_p), ("file_bytes", C.c_uint64), ("coff", C.c_void_p), ("csize", C.c_void_p),
                 ("isize", C.c_void_p), ("n_blocks", C.c_uint64), ("header_bytes", C.c_uint64)]
+
+
+class _FastaMap(C.Structure):  # mth_host_fasta_map_t
+    _fields_ = [("file", C.c_void_p), ("file_bytes", C.c_uint64), ("stream_bytes", C.c_uint64), ("compressed", C.c_int),
+                ("coff", C.c_void_p), ("csize", C.c_void_p), ("isize", C.c_void_p), ("n_blocks", C.c_uint64)]
+
+
+class FastaRow(C.Structure):   # mth_host_fasta_row_t (the layout of metheor_hip.h's mth_fasta_row_t)
+    _fields_ = [("src_off", C.c_uint64), ("n_bases", C.c_int64), ("line_bases", C.c_int64), ("line_width", C.c_int64),
+                ("name", C.c_char_p)]
 
 
 class _Shard(C.Structure):     # mth_host_shard_t
@@ -89,6 +99,9 @@ def lib():
         L.mth_host_fasta_close.argtypes = [vp]; L.mth_host_fasta_close.restype = None
         L.mth_host_fasta_last_error.argtypes = [vp]; L.mth_host_fasta_last_error.restype = C.c_char_p
         L.mth_host_fasta_fetch.argtypes = [vp, C.c_char_p, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]
+        L.mth_host_fasta_compressed.argtypes = [vp]
+        L.mth_host_fasta_map.argtypes = [vp, vp]
+        L.mth_host_fasta_layout.argtypes = [vp, C.c_char_p, C.c_int64, vp]
         _LIB = L
     return _LIB
 
@@ -299,6 +312,36 @@ class Fasta:
         if rc != 0:
             raise HostError(rc, self.L.mth_host_fasta_last_error(self.h).decode())
         return C.string_at(p, n.value) if n.value else b""
+
+    @property
+    def compressed(self):
+        """the file is BGZF (read on the device: fetch refuses it)"""
+        return bool(self.L.mth_host_fasta_compressed(self.h))
+
+    def map(self):
+        """mth_host_fasta_map -> dict(file: uint8 view of the mapping, stream_bytes, compressed, coff / csize / isize: the BGZF block
+        table, None for a plain file); the views are valid until close()"""
+        m = _FastaMap()
+        rc = self.L.mth_host_fasta_map(self.h, C.byref(m))
+        if rc != 0:
+            raise HostError(rc, self.L.mth_host_fasta_last_error(self.h).decode())
+        n = int(m.n_blocks)
+
+        def view(ptr, ct, k):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(k,)) if k else np.zeros(0, ct)
+        out = dict(file=view(m.file, C.c_uint8, int(m.file_bytes)), stream_bytes=int(m.stream_bytes), compressed=bool(m.compressed),
+                   coff=None, csize=None, isize=None)
+        if m.compressed:
+            out.update(coff=view(m.coff, C.c_uint64, n), csize=view(m.csize, C.c_uint32, n), isize=view(m.isize, C.c_uint32, n))
+        return out
+
+    def layout(self, name, end_incl):
+        """mth_host_fasta_layout -> FastaRow: where fetch(name, end_incl) would read (the row mth_tag_set_genome_fasta takes)"""
+        r = FastaRow()
+        rc = self.L.mth_host_fasta_layout(self.h, name.encode(), int(end_incl), C.byref(r))
+        if rc != 0:
+            raise HostError(rc, self.L.mth_host_fasta_last_error(self.h).decode())
+        return r
 
     def close(self):
         if self.h:
