@@ -515,7 +515,7 @@ int mth_pdr_lpmd_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_
     if (params->want_lpmd) ctx->lpmd_reduced = false;
     // Pipelined batches (mth_pdr_lpmd.hip): device-resident batches that take the fused tile pass, from the second of a run of such
     // calls on (mth_reset does not break a run; any other entry point does).  Not while kernels are being timed one by one.
-    if (ctx->pipe_mode < 0) { const char *e = getenv("MTH_PIPELINE"); ctx->pipe_mode = (e && atoi(e) == 0) ? 0 : 1; }
+    if (ctx->pipe_mode < 0) ctx->pipe_mode = pipeline_knob() ? 1 : 0;
     // (not for a batch of more than 2^29 positions -- a contig group: its kernels fill the chip for a millisecond, the boundary the
     // pipeline hides is nothing beside that, and the second lane's scratch rows would be another 16 B a position)
     const bool eligible = ctx->pipe_mode == 1 && (b.mem == MTH_MEM_DEVICE || b.mem == MTH_MEM_PREPARED) && !pdr_exact && !ctx->timing &&

@@ -4,19 +4,12 @@
 #include <stdint.h>
 
 #include "../../include/metheor_hip.h"
+#include "mth_plan.h"
 
 namespace mth {
 
-// ---- tiling constants -------------------------------------------------------------------
-// A tile is TILE_W consecutive reference positions of one contig; one workgroup owns the sites
-// of one tile and keeps their accumulators in LDS.  The read index has one entry per IDX_Q bp.
-// (the tile width is a template parameter of the tile kernel: 1024 / 2048 / 4096)
-constexpr int IDX_QSHIFT = 5;   // 32-bp quanta (256 until round 2: up to 362 bp of useless candidates per tile / site)
-constexpr int IDX_Q = 1 << IDX_QSHIFT;
+// (the tiling constants -- IDX_Q, PDR_FLUSH_MARGIN, the tile kernels' capacities -- are mth_plan.h's: beside the rules tuned against them)
 constexpr int BLOCK = 256;
-
-// pdr.rs:162 -- a site is flushed once a passing read's first CpG lies more than 150 bp past it
-constexpr int PDR_FLUSH_MARGIN = 150;
 
 // device-side error bits (DevState::err)
 enum : uint32_t {

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "mth_common.h"
+#include "mth_knobs.h"
 
 namespace mth {
 
@@ -328,14 +329,11 @@ int build_fine_index(mth_ctx *ctx, const mth_batch_t &dev_batch, int32_t idx_bas
 inline const uint32_t *idx_ptr(const mth_ctx *ctx) { return ctx->cur_idx ? ctx->cur_idx : ctx->idx.as<uint32_t>(); }
 // extent of the fine index of a batch: origin and entries, for any tile width up to 65536
 inline void fine_index_extent(const mth_batch_t &b, int32_t &idx_base, uint32_t &nq) {
-    const int64_t region_len = (int64_t)b.region_end - b.region_beg;
-    const int32_t ext = ((b.max_span + 2 + IDX_Q - 1) / IDX_Q) * IDX_Q;
-    idx_base = b.region_beg - ext;
-    const int64_t padded = ((region_len + 65535) / 65536) * 65536;
-    nq = (uint32_t)((padded + ext) >> IDX_QSHIFT) + 2;
+    const IndexGeom g = index_geometry(batch_shape(b), 65536u);
+    idx_base = g.idx_base; nq = g.nq;
 }
 // MHL as one tile pass (mth_mhl_tile.hip): candidate-site arrays filled with finished rows and the sites left to the exact walk
-int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_mhl_params_t &p, uint64_t &bound);
+int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_mhl_params_t &p, const MhlKnobs &kn, uint64_t &bound);
 // FDRP + qFDRP at WGBS depth as one tile pass (mth_fdrp_wtile.hip): candidate-site arrays filled with finished rows and the sites left
 // to k_fdrp_walk (listed in redo_list / *redo_cnt)
 int launch_fdrp_wtile(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_fdrp_params_t &p, const uint16_t *pair_tab, uint32_t *redo_list, uint32_t *redo_cnt);

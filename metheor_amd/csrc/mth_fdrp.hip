@@ -43,8 +43,6 @@ constexpr int FD_WIN = 201;   // MAX_READ_LEN, fdrp.rs:10
 // With max_depth > 256 a site that holds more than 256 reads at once is flagged again (flags = 3) and redone by a third pass
 // whose rows live in HBM scratch, max_depth of them per wave (SLOTS = 0: capacity at run time); same pair-parallel finalize.
 // max_depth above FD_DEPTH_MAX is refused (MTH_ERR_CAPACITY, loud): the pair index arithmetic is 32-bit.
-constexpr int FD_SLOTS_DEEP = 256;
-constexpr uint32_t FD_DEPTH_MAX = 16384;
 // FD_NB (template parameter of the walk): calls of a stored read held in the slot's registers (8 or 16)
 
 struct FdrpArgs {
@@ -1394,26 +1392,14 @@ int mth_fdrp_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_fdrp
     if (rc) return rc;
     hipStream_t s = ctx->stream;
     uint64_t bound = 0;
-    // WGBS depth (about a dozen candidate reads per site -- reads starting in [c - max_span + 1, c + 1]), sparse calls, spans <= 200 bp:
-    // ONE tile pass finds the sites and computes them (k_fdrp_wtile, round 6); the general walk only redoes what it hands back.
-    // METHEOR_FDRP_WTILE=0 / 1 forces the choice (A/B, tests).
-    const bool dense = d.n_reads && ((double)d.n_cpgs / (double)d.n_reads) > 6.0;
-    const double cand = (double)d.n_reads * ((double)d.max_span + 2.0) / std::max<double>(1.0, (double)d.region_end - (double)d.region_beg);
-    // (round 6: a dense form of the tile pass -- 64-bit masks, sites up to 64 reads, term lists in HBM -- was built for the depths of config 4:
-    // parity-green, 4.2 ms against this file's k_fdrp_tile + k_fdrp_chain 3.4 ms: profiles/r06_fdrp_dense.md, tools/experiments/)
-    // How deep: a site holds up to 64 readers there, but readers beyond max_depth are the reservoir's (handed back), so the depth must
-    // stay 4 sigma below max_depth (CLI default 40: ~22 candidate reads a site).  Measured on a chr1-sized contig at density 0.0091,
-    // pass ms, this form against rounds 2-5's choice: 16 M reads (10 x) 0.45 / 0.615, 24 M 0.85 / 1.48, 32 M (20 x) 1.26 / 2.91 (the
-    // read x read form), 48 M (29 x) 3.06 / 3.45 (hand-backs 0.7), 64 M (39 x) 10.5 / 4.8.  Sparse calls only (<= 2 a read):
-    // config 2 -- 25.6 x, 3 calls a read -- 2.1 / 1.35.
-    const bool sparse_calls = d.n_reads && (double)d.n_cpgs / (double)d.n_reads <= 2.0;
-    bool wtile = sparse_calls && d.max_span <= 200 && cand <= 24.0 && cand + 4.0 * std::sqrt(cand) <= (double)params->max_depth &&
-                 !getenv("METHEOR_FDRP_WALK4") && !getenv("METHEOR_FDRP_TILE");
-    if (const char *e = getenv("METHEOR_FDRP_WTILE")) wtile = d.max_span <= 200 && atoi(e) != 0;
+    // which kernels take the batch: plan_fdrp (mth_plan.h)
+    const BatchShape shape = batch_shape(d);
+    const FdrpKnobs kn = fdrp_knobs_from_env();
+    const FdrpPlan pl = plan_fdrp(shape, *params, kn);
+    const bool wtile = pl.wtile, dense = pl.dense;
     if (wtile) {
         // the candidate-site arrays the tile pass fills itself (no discovery pass)
-        const uint64_t region_len = (uint64_t)((int64_t)d.region_end - d.region_beg);
-        bound = d.n_cpgs < region_len ? d.n_cpgs : region_len;
+        bound = pl.bound;
         if (!ctx->d_state2) MTH_HIP(ctx, hipMalloc((void **)&ctx->d_state2, sizeof(DevState)));
         MTH_HIP(ctx, hipMemsetAsync(ctx->d_state2, 0, sizeof(DevState), s));
         MTH_HIP(ctx, ctx->s_pos.reserve((bound + 1) * 4, s));
@@ -1445,14 +1431,13 @@ int mth_fdrp_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_fdrp
     if (d.max_span >= 203 && d.n_reads)
         hipLaunchKernelGGL(k_fdrp_guard, dim3((uint32_t)((d.n_reads + 255) / 256)), dim3(256), 0, s, d.read_start, d.read_end, d.read_mapq, d.cpg_off,
                            d.cpg_pos, (uint32_t)d.n_reads, (uint32_t)params->min_qual, &ctx->d_state->err);
-    const int32_t ext = ((d.max_span + 2 + IDX_Q - 1) / IDX_Q) * IDX_Q;
     FdrpArgs a;
     a.read_start = d.read_start; a.read_end = d.read_end; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
     a.idx = idx_ptr(ctx); a.sites_st = ctx->d_state2; a.site_pos = ctx->s_pos.as<int32_t>(); a.st = ctx->d_state;
     a.site_nc = ctx->s_nc.as<uint32_t>(); a.site_nd = ctx->s_nd.as<uint32_t>();
     a.fdrp = ctx->w_val.as<float>(); a.qfdrp = reinterpret_cast<float *>(ctx->w_aux.p); a.nreads = ctx->w_cov.as<uint32_t>();
     a.flags = ctx->w_flags.as<uint32_t>();
-    a.seed = params->seed; a.idx_base = d.region_beg - ext; a.max_span = d.max_span; a.tid = d.tid;
+    a.seed = params->seed; a.idx_base = d.region_beg - index_ext(d.max_span); a.max_span = d.max_span; a.tid = d.tid;
     a.grp_tab = group_table(ctx, batch->tid, &a.grp_n);
     if (batch->tid <= -2 && !a.grp_tab) return fail(ctx, MTH_ERR_INVALID, "batch.tid is not a defined contig group's handle");
     a.min_overlap = params->min_overlap; a.n_reads = d.n_reads; a.n_cpgs = d.n_cpgs; a.region_beg = d.region_beg; a.region_end = d.region_end;
@@ -1460,7 +1445,7 @@ int mth_fdrp_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_fdrp
     a.min_qual = params->min_qual;
     a.rows_scratch = nullptr; a.slots_cap = 0;
     a.redo_list = nullptr; a.redo_cnt = nullptr; a.no_compact = 0u;
-    a.wide_rows = getenv("METHEOR_FDRP_TILE_WIDE_ROWS") ? 1u : 0u;
+    a.wide_rows = kn.wide_rows ? 1u : 0u;
     a.terms = nullptr; a.cursor = nullptr; a.budget = 0; a.site_off = nullptr; a.site_nz = nullptr; a.site_disc = nullptr;
     if (!ctx->f_pairtab.p) {
         // the pairs of n stored reads in the reference's (i, j) loop order (fdrp.rs:129-141), n = 2..64, one after the other
@@ -1479,23 +1464,10 @@ int mth_fdrp_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_fdrp
     const uint32_t grid = (uint32_t)std::min<uint64_t>((bound + 3) / 4, 16384);   // 4 waves (sites) per block
     {
         // (each kernel of the pass under its own timer id: bench.py's kernels_ms decomposes -- VERDICT r04 item 2)
-        // dense CpGs (hotspots, RRBS): 16 call registers per stored read keep the per-call match out of
-        // the memory loop; sparse WGBS keeps 8 (half the compares per call)
-        // WGBS depth: when a site has about a dozen reads that can call it (reads starting in [c - max_span + 1, c + 1]), four
-        // sites share a wave (k_fdrp_walk4<16>) and the general walk only redoes what that kernel handed back.  Measured on a
-        // chr1-sized contig (profiles/r02_fdrp_walk4.md): ~10 such reads per site 0.887 -> 0.568 ms, 12 1.29 -> 0.94, 14.6 1.58 -> 1.39,
-        // 17 1.79 -> 1.83 (the switch is at 16), ~19.5 per site 1.95 -> 2.17
-        // (16 lanes) / 2.13 (32 lanes) -- deeper sites are bound by their pair rounds and keep the wave-per-site walk.
-        // METHEOR_FDRP_WALK4=0 / 16 / 32 (1 = 16) forces the choice (A/B, tests).
-        int walk4 = (!wtile && !dense && d.max_span <= 200 && cand <= 16.0) ? 16 : 0;                        // lanes per site
-        if (const char *e = getenv("METHEOR_FDRP_WALK4")) { const int k = atoi(e); walk4 = d.max_span <= 200 ? (k == 1 ? 16 : (k == 16 || k == 32 ? k : 0)) : 0; }
+        const int walk4 = pl.walk4;               // lanes per site
+        bool tile = pl.tile;                      // (may still lose to its term list below)
         a.only_flag = 0u; a.redo_mask = nullptr;
-        // The read x read form (k_fdrp_tile + k_fdrp_chain) for everything the four-sites-per-wave kernel does not take:
-        // METHEOR_FDRP_TILE=0 / 1 forces the choice (A/B, tests).
-        bool tile = d.max_span <= 200 && !walk4 && !wtile;
-        if (const char *e = getenv("METHEOR_FDRP_TILE")) { tile = d.max_span <= 200 && atoi(e) != 0 && !wtile; if (tile) walk4 = 0; }
         if (wtile) {
-            walk4 = 0;
             MTH_HIP(ctx, ctx->f_redo.reserve((bound + 2) * 4, s));
             unsigned long long *cur = ctx->f_state.as<unsigned long long>() + 2;
             MTH_HIP(ctx, hipMemsetAsync(cur, 0, 16, s));
@@ -1512,9 +1484,7 @@ int mth_fdrp_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_fdrp
                 fprintf(stderr, "[fdrp wtile] candidate rows %llu handed back %u\n", (unsigned long long)st.n_sites, redo);
             }
         }
-        const uint64_t dcap = std::min<uint64_t>(std::max<uint32_t>(params->max_depth, 1u), 64u);
-        // sum over sites of C(n, 2) <= (dcap - 1) / 2 x the sum of n <= (dcap - 1) / 2 x the batch's calls; + the 64-byte rounding
-        const uint64_t budget = (uint64_t)d.n_cpgs * (dcap - 1) / 2 + 64 * bound + 64;
+        const uint64_t budget = fdrp_term_budget(shape, *params, bound);
         if (tile && budget > ctx->f_terms.cap) {
             // a contig group can hold 2^32 calls: ~80 GB of term codes at -D 40.  The list is a bound, not a need -- when it would take
             // more than half of what the device has free, the batch keeps the walk kernels (same rows)
@@ -1559,10 +1529,7 @@ int mth_fdrp_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_fdrp
             a.redo_mask = ctx->f_redo.as<unsigned long long>();
             const uint32_t grid4 = (uint32_t)std::min<uint64_t>((bound + 255) / 256, 16384);   // 4 waves x 64 sites per block and step
             LaunchTimer lt(ctx, K_FDRPWALK4);
-            // 32-site windows where 32 sites reach well beyond +- 200 bp (at the batch's site density; METHEOR_FDRP_WIN=64 / 32 forces it)
-            const double sites_per_bp = d.n_reads ? (double)d.n_cpgs / (double)d.n_reads / (double)std::max(d.max_span, 1) : 0.0;   // (the site count itself is on the device)
-            int win = sites_per_bp * 402.0 <= 12.0 ? 32 : 64;
-            if (const char *e = getenv("METHEOR_FDRP_WIN")) win = atoi(e) == 32 ? 32 : 64;
+            const int win = pl.win;
             if (walk4 == 16 && win == 32) hipLaunchKernelGGL((k_fdrp_walk4<16, 32>), dim3(grid4), dim3(256), 0, s, a);
             else if (walk4 == 16) hipLaunchKernelGGL((k_fdrp_walk4<16, 64>), dim3(grid4), dim3(256), 0, s, a);
             else if (win == 32) hipLaunchKernelGGL((k_fdrp_walk4<32, 32>), dim3(grid4), dim3(256), 0, s, a);

@@ -71,15 +71,7 @@ struct FwArgs {
     unsigned long long *trace;    // -DMTH_FW_TRACE builds: cycles per phase of each tile's first stretch (lane 0)
 };
 
-#ifndef MTH_FW_U
-#define MTH_FW_U 2
-#endif
-constexpr int FW_U = MTH_FW_U;                          // 64-read chunks of a stretch
-constexpr int FW_WPT = FW_U > 2 ? 2 : 1;                // bitmap words per lane
-constexpr int FW_WMAX = FW_WPT * 2048 - 448;            // the tile + 200 on either side fit the bitmap (1600 / 3648 positions)
-constexpr int FW_RCAP = 64 * FW_U;                      // candidate reads of a stretch (more: the stretch is halved)
-constexpr int FW_V = FW_U > 2 ? 6 : 4;                  // 64-call chunks of a stretch
-constexpr int FW_CCAP = 64 * FW_V;                      // calls of a stretch's candidate reads (more: the stretch is halved)
+// (FW_U, FW_WMAX, FW_RCAP, FW_CCAP: mth_plan.h, beside the width rule)
 constexpr int FW_SC = 32;                               // core sites of a stretch (one per lane; a denser stretch is halved)
 constexpr int FW_LCAP = 64;                             // stored reads of a site here (more: handed back)
 constexpr int FW_NZCAP = 1024;                           // non-zero qFDRP terms of a stretch's sites (more: the site is handed back)
@@ -570,19 +562,8 @@ int launch_fdrp_wtile(mth_ctx *ctx, const mth_batch_t &d, const mth_fdrp_params_
     hipStream_t s = ctx->stream;
     const int64_t region_len = (int64_t)d.region_end - d.region_beg;
     if (d.n_reads == 0 || region_len <= 0) return MTH_OK;
-    // Tile width: the widest whose candidate reads (start in [P0 - max_span + 1, P1]) fill the stretch's two 64-read chunks without
-    // spilling over too often (mean + 2 sigma <= 128: an overfull tile is redone in halves), at most FW_WMAX.
-    int W;
-    {
-        const double rpb = (double)d.n_reads / (double)region_len;
-        const double want = (double)FW_RCAP - 2.0 * std::sqrt((double)FW_RCAP);     // ~105 of 128 reads
-        W = (int)(want / std::max(rpb, 1e-9)) - d.max_span;
-        // ... and their calls the stretch's call lanes (denser calls: a narrower tile rather than a tile redone in halves)
-        const double cpr = (double)d.n_cpgs / (double)d.n_reads, wantc = (double)FW_CCAP - 2.0 * std::sqrt((double)FW_CCAP);
-        W = std::min(W, (int)(wantc / std::max(rpb * cpr, 1e-9)) - d.max_span);
-        W = std::max(256, std::min(FW_WMAX, W)) & ~63;
-    }
-    if (const char *e = getenv("METHEOR_FDRP_WTILE_W")) W = std::min(FW_WMAX, std::max(64, atoi(e))) & ~63;   // tests / tuning
+    const FdrpWtileKnobs kn = fdrp_wtile_knobs_from_env();
+    const int W = plan_fdrp_wtile(batch_shape(d), kn);       // the tile width (mth_plan.h)
     int32_t idx_base = 0;
     uint32_t ntiles = 0;
     int rc = build_read_index(ctx, d, W, idx_base, ntiles);
@@ -604,7 +585,7 @@ int launch_fdrp_wtile(mth_ctx *ctx, const mth_batch_t &d, const mth_fdrp_params_
     a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span; a.min_overlap = p.min_overlap;
     a.n_reads = d.n_reads; a.n_cpgs = (uint32_t)d.n_cpgs; a.ntiles = ntiles; a.tile_w = (uint32_t)W;
     a.min_depth = (uint32_t)std::min<uint64_t>(p.min_depth, 0xffffffffull); a.max_depth = p.max_depth; a.min_qual = p.min_qual;
-    a.force_sub = getenv("METHEOR_FDRP_WTILE_SUB") ? 1 : 0; a.force_heavy = getenv("METHEOR_FDRP_WTILE_HEAVY") ? 1 : 0;
+    a.force_sub = kn.force_sub ? 1 : 0; a.force_heavy = kn.force_heavy ? 1 : 0;
     a.scratch = reinterpret_cast<FdRec *>(ctx->scratch.p); a.rows_per_tile = rows_per_tile;
     a.tile_cnt = ctx->tile_cnt.as<uint32_t>(); a.bucket = ctx->tile_bucket.as<unsigned long long>(); a.st = ctx->d_state; a.pair_tab = pair_tab;
     a.quot = ctx->f_quot.as<float>();

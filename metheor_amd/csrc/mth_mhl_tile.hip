@@ -58,14 +58,13 @@ struct MhlTileArgs {
 #ifndef MTH_MT_U
 #define MTH_MT_U 2
 #endif
-constexpr int MT_S = 256, MT_B = 256, MT_U = MTH_MT_U, MT_NC = 8, MT_LCAP = 16;
+constexpr int MT_B = 256, MT_U = MTH_MT_U, MT_NC = 8, MT_LCAP = 16;
 // slot h: tkey[h] = position; taux[h] bit 31 = "a read with > 16 CpGs calls it", low bits = largest (index - lo + 1) of a contributor
 // calling its own start - 1; thist[17 h ..]: words 0..7 hn, 8..15 hm (bin b in half (b - 1) & 1 of word (b - 1) >> 1); the 17th word
 // is padding: with 16 the slots' words fall on 4 of the 64 LDS banks (measured: contributions 0.17 -> 0.22 ms)
 constexpr int MT_HW = 17;
 constexpr int MT_Q = 1024;         // contributing reads a sub-range may queue (more: the sub-range is halved)
 constexpr uint32_t MT_EMPTY = 0xffffffffu;
-constexpr uint32_t MT_HEAVY = 8191;   // candidate reads a sub-range may have with 16-bit bins (a read adds up to 8 to one hm bin)
 
 // A contributing read of a `heavy` stretch: a slot per called position, a 32-bit count in the slot's first histogram word.  Out of
 // line: the stretch is rare and its registers would otherwise be live across the whole kernel (21 spilled VGPRs when it was inline).
@@ -675,7 +674,7 @@ __global__ __launch_bounds__(256) void k_mhl_walk_wave(const MhlWaveArgs a) {
 
 // The tile pass of one batch: candidate-site arrays (ctx->s_pos, w_val, w_cov, w_flags; count in d_state2->n_sites) filled with
 // the finished rows (flag 1) and the sites left to k_mhl_walk_big (flag 4); the read index is left for that walk.
-int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &d, const mth_mhl_params_t &p, uint64_t &bound) {
+int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &d, const mth_mhl_params_t &p, const MhlKnobs &kn, uint64_t &bound) {
     hipStream_t s = ctx->stream;
     const int64_t region_len = (int64_t)d.region_end - d.region_beg;
     bound = (uint64_t)std::min<int64_t>((int64_t)d.n_cpgs, std::max<int64_t>(region_len, 0));
@@ -687,48 +686,13 @@ int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &d, const mth_mhl_params_t &
     MTH_HIP(ctx, ctx->w_flags.reserve((bound + 1) * 4, s));
     MTH_HIP(ctx, ctx->w_aux.reserve((bound + 1) * 4, s));
     if (d.n_reads == 0 || region_len <= 0) return MTH_OK;
-    // Tile width: up to 0.65 x 256 slots' worth of sites per tile at the batch's call density (a denser stretch is redone in halves)
-    // and few enough candidate reads for the 16-bit bins.  A tile is a chain of ~6 dependent round trips and ~10 barriers whatever it
-    // holds, so the widest tile that fits wins: config-3 density 0.319 / 0.220 / 0.144 ms at 4096 / 8192 / 16384 bp, config 2 0.209 /
-    // 0.204 at 4096 / 8192 (16384 overflows the slots there: 1.27 ms)
-    // (round 6: the one-wave-per-tile form that pays for FDRP was built for MHL too -- parity-green and 30 % slower than this kernel, whose
-    // tile is eleven times larger: profiles/r06_mhl_wtile.md, tools/experiments/mth_mhl_wtile.hip)
-    int shift = 12, W = 0;
+    // row check or per-read marks, and the tile width: plan_mhl (mth_plan.h)
+    const MhlPlan pl = plan_mhl(batch_shape(d), p, kn);
+    const bool rowchk = pl.rowchk;
+    const int shift = pl.shift, W = 1 << shift;
     int32_t idx_base = 0;
     uint32_t ntiles = 0;
     MhlTileArgs a;
-    a.trace = nullptr;
-    // the flush rule per read (position bitmap in the tile kernel) or per finished row (k_mhl_rowcheck): rows are few where calls are
-    // sparse -- at <= 2 CpGs a read one read in twenty reaches min_cpgs = 4 -- and there the per-read marks (start, a dependent first-call
-    // load, bitmap atomics) were 29 % of the tile kernel for a test only the rows need (chr1-sized contig at config-3 density: 0.170 ->
-    // 0.130 ms + 0.009 for the row kernel); config 2 (2.94 CpGs a read, 100 rows a tile) keeps the marks
-    bool rowchk = (double)d.n_cpgs <= 1.8 * (double)d.n_reads;       // (density sweep, profiles/r06_mhl_rowcheck.md: even at 2.0)
-    if (const char *e = getenv("MTH_MHL_ROWCHK")) rowchk = atoi(e) != 0;                               // tests / tuning
-    {
-        const double cpr = (double)d.n_cpgs / (double)d.n_reads;
-        const double sites_per_bp = cpr / (double)std::max(d.max_span, 1);
-        const double reads_per_bp = (double)d.n_reads / (double)region_len;
-        while (shift < 14 && sites_per_bp * (double)(2 << shift) <= 0.65 * MT_S &&
-               reads_per_bp * (double)((2 << shift) + d.max_span + 2 * IDX_Q) <= 0.75 * MT_HEAVY)
-            ++shift;
-        // Without the marks a tile's cost is its contributors', and a slot is taken only by a site that a CONTRIBUTOR calls: 32 768-position
-        // tiles where those sites fit (config 3: MHL pass 2.21 -> 1.56 ms; 65 536 overflows the slots on a chr1-sized contig: 0.092 ->
-        // 0.227 ms) and the region still gives three rounds of tiles.  The share of such sites: a covering read has min_cpgs - 1 other
-        // CpGs with probability pc (Poisson at the batch's calls per read); overlapping readers are far from independent -- sqrt(depth)
-        // of them counted (measured at 10 x: 0.35 of the sites).  An underestimate costs time only (the stretch is redone in halves).
-        if (rowchk && shift == 14) {
-            double pc = 1.0, term = std::exp(-cpr);
-            for (uint32_t k = 0; k + 1 < p.min_cpgs && k < 64; ++k) { pc -= term; term *= cpr / (double)(k + 1); }
-            pc = std::min(1.0, std::max(pc, 0.0));
-            const double depth = reads_per_bp * (double)std::max(d.max_span, 1);
-            const double share = 1.0 - std::pow(1.0 - pc, std::max(1.0, std::sqrt(depth)));
-            if (sites_per_bp * share * 32768.0 <= 0.5 * MT_S && reads_per_bp * (double)(32768 + d.max_span + 2 * IDX_Q) <= 0.75 * MT_HEAVY &&
-                region_len >= 3ll * 1536 * 32768)
-                shift = 15;
-        }
-    }
-    if (const char *e = getenv("MTH_MHL_TILE_SHIFT")) shift = std::min(16, std::max(12, atoi(e)));   // tests / tuning
-    W = 1 << shift;
     int rc = build_read_index(ctx, d, W, idx_base, ntiles);
     if (rc) return rc;
     const uint32_t nbk = (ntiles + (1u << TILE_BUCKET_SHIFT) - 1) >> TILE_BUCKET_SHIFT;
@@ -740,7 +704,7 @@ int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &d, const mth_mhl_params_t &
     a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span;
     a.n_reads = d.n_reads; a.ntiles = ntiles; a.n_cpgs = (uint32_t)d.n_cpgs; a.min_depth = p.min_depth; a.min_cpgs = p.min_cpgs;
     a.min_qual = p.min_qual;
-    a.force_sub = getenv("MTH_MHL_FORCE_SUB") ? 1 : 0; a.force_hand_on = getenv("MTH_MHL_FORCE_HAND_ON") ? 1 : 0;
+    a.force_sub = kn.force_sub ? 1 : 0; a.force_hand_on = kn.force_hand_on ? 1 : 0;
     a.dbg = getenv("MTH_MHL_DBG") ? (uint8_t)atoi(getenv("MTH_MHL_DBG")) : 0;
     a.scratch = reinterpret_cast<MhlRec *>(ctx->scratch.p); a.tile_cnt = ctx->tile_cnt.as<uint32_t>();
     a.bucket = ctx->tile_bucket.as<unsigned long long>(); a.st = ctx->d_state;
@@ -779,7 +743,7 @@ int launch_mhl_tile(mth_ctx *ctx, const mth_batch_t &d, const mth_mhl_params_t &
         rc.hand_list = ctx->w_aux.as<uint32_t>(); rc.st = ctx->d_state; rc.idx_base = idx_base; rc.max_span = d.max_span; rc.n_reads = d.n_reads;
         hipLaunchKernelGGL(k_mhl_rowcheck, dim3(2048), dim3(256), 0, s, rc);
     }
-    if (!getenv("MTH_MHL_NO_WAVE_WALK")) {
+    if (!kn.no_wave_walk) {
         LaunchTimer lt(ctx, K_MHLWALK);
         MhlWaveArgs w;
         w.read_mapq = d.read_mapq; w.cpg_off = d.cpg_off; w.cpg_pos = d.cpg_pos; w.idx = idx_ptr(ctx);

@@ -47,7 +47,7 @@ static int fused_batch(mth_ctx *ctx, const mth_batch_t &pb, const mth_multi_para
     unsigned long long *qs = t.words();
     FusedQuartet fq;
     fq.force = force ? 1 : 0;
-    fq.force_heavy = getenv("MTH_MULTI_FORCE_HANDBACK") ? 1 : 0;       // tests: every tile handed back
+    fq.force_heavy = multi_force_handback_knob() ? 1 : 0;       // tests: every tile handed back
     fq.min_qual = mp.quartet.min_qual;
     fq.qs = qs; fq.row_cap = t.cap; fq.max_tiles = max_tiles;
     fq.tile_flag = t.tflag.as<uint32_t>();

@@ -55,7 +55,7 @@ struct PairArgs {
 // PT_U / PT_OCC: 2 reads per thread and round at 6 waves per SIMD (80 VGPRs; 26 KiB of LDS allow 6 workgroups per CU) measured best
 // (tools/ab_measure.sh pairs: 1 / 6 +5 %, 2 / 5 +2 %, 3 / 5 +17 %, 4 / 4 +21 %; profiles/r03_pairs_tile.md)
 constexpr int PT_OCC = 6;
-constexpr int PT_S = 2048, PT_B = 256, PT_U = 2, PT_CHUNK = 1024, PT_GRID = 8192;   // tile kernel: LDS slots, threads, reads per thread and round (the tile
+constexpr int PT_B = 256, PT_U = 2, PT_CHUNK = 1024, PT_GRID = 8192;   // tile kernel: LDS slots, threads, reads per thread and round (the tile
                                                    // width is a template parameter: 8192 / 16384 / 32768, chosen per batch)
 constexpr int PT_NC = 8;                                 // calls of a read parked in LDS for the pair loops
 
@@ -419,21 +419,8 @@ __global__ __launch_bounds__(PT_B, PT_OCC) void k_pairs_tile(const PTileArgs a) 
 }
 
 // ---- what the pairs table brings to the tile-row driver (mth_tile_rows.hip) ----------------------------------------
-// Tile width (see mth_quartet.hip): distinct pairs per tile ~ sites per tile x sites per pair window
-static int pairs_tile_shift(const mth_batch_t &d, const TileParams &p) {
-    const int64_t region_len = (int64_t)d.region_end - d.region_beg;
-    int tile_shift = 13;
-    if (d.n_reads && region_len > 0) {
-        const double sites_per_bp = (double)d.n_cpgs / (double)d.n_reads / (double)std::max(d.max_span, 1);
-        const double reads_per_bp = (double)d.n_reads / (double)region_len;
-        const double window = std::max(1.0, (double)std::min<int64_t>((int64_t)p.pairs.max_distance - std::max(p.pairs.min_distance, 0) + 1, d.max_span));
-        while (tile_shift < 16 && sites_per_bp * (double)(2 << tile_shift) * std::max(1.0, sites_per_bp * window) <= 0.3 * PT_S &&
-               reads_per_bp * (double)((2 << tile_shift) + d.max_span + 2 * IDX_Q) <= 30000.0)
-            ++tile_shift;
-    }
-    if (const char *e = getenv("MTH_PAIRS_TILE_SHIFT")) tile_shift = std::min(16, std::max(13, atoi(e)));   // tests / tuning
-    return tile_shift;
-}
+// the tile width: pairs_tile_shift of mth_plan.h
+static int pairs_tile_shift(const mth_batch_t &d, const TileParams &p) { return pairs_tile_shift(batch_shape(d), p.pairs, tile_shift_knob("MTH_PAIRS")); }
 
 static hipError_t pairs_grow_rows(mth_ctx *ctx, uint64_t cap, uint64_t used) {
     const hipError_t e = ctx->p_out_key.reserve(cap * 8, ctx->stream, true, used * 8);
@@ -452,7 +439,7 @@ static void pairs_launch_tiles(mth_ctx *ctx, const mth_batch_t &d, const TilePar
     a.idx = idx_ptr(ctx); a.cpg_rel = r8 ? (const void *)d.cpg_rel : (const void *)d.cpg_rel16;
     a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span;
     a.min_dist = params->min_distance; a.max_dist = params->max_distance; a.n_reads = d.n_reads; a.ntiles = ntiles; a.n_cpgs = (uint32_t)d.n_cpgs;
-    a.min_qual = params->min_qual; a.force_heavy = getenv("MTH_PAIRS_FORCE_GLOBAL") ? 1 : 0;
+    a.min_qual = params->min_qual; a.force_heavy = force_global_knob("MTH_PAIRS") ? 1 : 0;
     a.row_total = ps + 1; a.row_cap = row_cap; a.unfit = ps + 6; a.n_heavy = ps + 5;
     a.tile_flag = t.tflag.as<uint32_t>();
     a.tile_row0 = t.tile_row0.as<unsigned long long>() + tiles_before;
@@ -501,7 +488,7 @@ static int pairs_global_path(mth_ctx *ctx, const mth_batch_t &d, const TileParam
     // batch: start at bound / 2 slots and redo 4x larger if an insert ran out of probes (cannot happen at 2 x bound)
     unsigned long long n_slots = 1024;
     while (n_slots < bound / 2) n_slots <<= 1;
-    if (const char *e = getenv("MTH_PAIRS_SLOTS_MIN")) { const unsigned long long k = strtoull(e, nullptr, 10); if (k >= 16) { n_slots = 16; while (n_slots < k) n_slots <<= 1; } }   // tests: force the retry
+    if (const unsigned long long k = slots_min_knob("MTH_PAIRS")) n_slots = k;   // tests: force the retry
     for (;;) {
         MTH_HIP(ctx, ctx->p_keys.reserve(n_slots * 8, s));
         MTH_HIP(ctx, ctx->p_cnt.reserve(n_slots * 8, s));

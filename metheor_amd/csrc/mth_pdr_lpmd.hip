@@ -1575,15 +1575,11 @@ __global__ void k_pipe_seed(const DevState *__restrict__ st, DevState *__restric
 }
 
 // ---------------------------------------------------------------------------------------------
-constexpr int DENSE_TILE_SHIFT = 12;   // the dense kernel's 4096-bp tiles
-constexpr int TILE_MARGIN = 256;   // counter margins on either side of a tile for batches with max_span <= 256
-#ifndef MTH_TILE_B_DEFAULT
-#define MTH_TILE_B_DEFAULT 128     // threads per workgroup of the dense kernel on 8-bit relpos batches (launch_pdr_lpmd)
-#endif
+// (DENSE_TILE_SHIFT, TILE_MARGIN, MTH_TILE_B_DEFAULT: mth_plan.h)
 template <int W, int B, typename RelT>
 static void launch_tile(const TileArgs &a, uint32_t ntiles, hipStream_t s) {
     const uint32_t grid = ((ntiles + 7) / 8) * 8;   // whole rows of 8 XCDs (remap in the kernel)
-    static const bool no_margin = getenv("MTH_TILE_NO_MARGIN") != nullptr;   // A/B switch
+    const bool no_margin = tile_no_margin_knob();   // A/B switch
     // (two waves per workgroup: never the margins -- their 2 KB are the ninth workgroup of a CU, worth more than the clamp per slot they save)
     if (B == 256 && a.max_span <= TILE_MARGIN && !no_margin) hipLaunchKernelGGL((k_pdr_lpmd_tile<W, 256, 8, RelT, TILE_MARGIN>), dim3(grid), dim3(256), 0, s, a, ntiles);
     else hipLaunchKernelGGL((k_pdr_lpmd_tile<W, B, 8, RelT, 0>), dim3(grid), dim3(B), 0, s, a, ntiles);
@@ -1594,20 +1590,17 @@ static uint32_t runs_grid(uint32_t ntiles) {
     static const uint32_t slots = [] {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const char *e = getenv("MTH_RUNS_WGS_PER_CU");
-        const int per = e && atoi(e) > 0 ? atoi(e) : MTH_RUNS_OCC;
+        const int per = runs_wgs_per_cu_knob() ? runs_wgs_per_cu_knob() : MTH_RUNS_OCC;
         return (uint32_t)std::max(cus, 1) * (uint32_t)per;
     }();
     return std::max(1u, std::min(slots, ntiles));
 }
 static void launch_runs(const TileArgs &a, const RunArgs &ra, uint32_t ntiles, uint32_t G, hipStream_t s) {
-    static const bool no_margin = getenv("MTH_TILE_NO_MARGIN") != nullptr;   // A/B switch
+    const bool no_margin = tile_no_margin_knob();   // A/B switch
     if (a.max_span <= TILE_MARGIN && !no_margin) hipLaunchKernelGGL((k_pdr_lpmd_runs<(1 << DENSE_TILE_SHIFT), TILE_MARGIN>), dim3(G), dim3(256), 0, s, a, ra, ntiles);
     else hipLaunchKernelGGL((k_pdr_lpmd_runs<(1 << DENSE_TILE_SHIFT), 0>), dim3(G), dim3(256), 0, s, a, ra, ntiles);
 }
 
-// the linear read index alone (for kernels that find a tile's candidate reads without running the PDR/LPMD pass):
-// idx lives in ctx->idx; same origin and quantum as launch_pdr_lpmd builds
 // first kernel of a PDR + LPMD batch whose index exists already (prepared batches): what k_build_index does beside the index -- the row
 // base, the bucket sums, safe_hi and the batch's own findings (unsorted) into the lane's block
 __global__ __launch_bounds__(256) void k_batch_begin(DevState *__restrict__ lane_st, DevState *__restrict__ cst, const DevState *__restrict__ prep_st,
@@ -1621,39 +1614,42 @@ __global__ __launch_bounds__(256) void k_batch_begin(DevState *__restrict__ lane
 }
 __global__ void k_batch_err(DevState *__restrict__ st, const DevState *__restrict__ prep_st) { if (prep_st->err) atomicOr(&st->err, prep_st->err); }
 
-int build_fine_index(mth_ctx *ctx, const mth_batch_t &b, int32_t idx_base, uint32_t nq, uint32_t *idx, DevState *st) {
-    hipStream_t s = ctx->stream;
+// The fine index of a batch (k_build_index<1>: one entry per IDX_Q positions from idx_base on) on stream s; beside it the kernel leaves
+// the batch's findings (unsorted, the word of position -1) and safe_hi in *st, and for a PDR + LPMD batch the row base (cst) and the
+// cleared bucket sums.  cpg_off: the kernel's own view of the call offsets (nullptr: none, as the index-only build passes it)
+static void launch_fine_index(mth_ctx *ctx, hipStream_t s, const mth_batch_t &b, int32_t idx_base, uint32_t nq, uint32_t *idx, DevState *st,
+                              DevState *cst, unsigned long long *bucket_sums, uint32_t n_bucket_words, const uint32_t *cpg_off) {
     LaunchTimer lt(ctx, K_INDEX);
     const uint32_t nb = (b.n_reads / 4 + 1 + BLOCK * IDX_GROUPS - 1) / (BLOCK * IDX_GROUPS);
     hipLaunchKernelGGL(k_build_index<1>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, idx_base, 0, (int)IDX_QSHIFT, nq,
-                       (int)((reinterpret_cast<uintptr_t>(b.read_start) & 15u) == 0), idx, (uint32_t *)nullptr, st,
-                       (DevState *)nullptr, (unsigned long long *)nullptr, 0u, b.cpg_off, b.n_cpgs, b.cpg_off, b.n_cpgs ? b.cpg_pos : nullptr);
+                       (int)batch_shape(b).start_al16, idx, (uint32_t *)nullptr, st, cst, bucket_sums, n_bucket_words, cpg_off, b.n_cpgs,
+                       b.cpg_off, b.n_cpgs ? b.cpg_pos : nullptr);
+}
+
+int build_fine_index(mth_ctx *ctx, const mth_batch_t &b, int32_t idx_base, uint32_t nq, uint32_t *idx, DevState *st) {
+    launch_fine_index(ctx, ctx->stream, b, idx_base, nq, idx, st, nullptr, nullptr, 0u, b.cpg_off);
     MTH_HIP(ctx, hipGetLastError());
     return MTH_OK;
 }
 
+// the linear read index alone (for kernels that find a tile's candidate reads without running the PDR/LPMD pass):
+// idx lives in ctx->idx; same origin and quantum as launch_pdr_lpmd builds
 int build_read_index(mth_ctx *ctx, const mth_batch_t &b, int tile_w, int32_t &idx_base, uint32_t &ntiles) {
     hipStream_t s = ctx->stream;
-    const int64_t region_len = (int64_t)b.region_end - b.region_beg;
-    ntiles = (uint32_t)((region_len + tile_w - 1) / tile_w);
-    const int32_t ext = ((b.max_span + 2 + IDX_Q - 1) / IDX_Q) * IDX_Q;
-    idx_base = b.region_beg - ext;
-    const uint32_t nq = (uint32_t)(((int64_t)ntiles * tile_w + ext) >> IDX_QSHIFT) + 2;
+    const IndexGeom g = index_geometry(batch_shape(b), (uint32_t)tile_w);
+    idx_base = g.idx_base; ntiles = g.ntiles;
     ctx->cur_idx = nullptr;
     if (Prepared *pr = ctx->cur_prep) {
         // a prepared batch: its index was built once (same origin and quantum; it covers every tile width up to 65536)
-        if (pr->idx_base == idx_base && nq <= pr->nq) {
+        if (pr->idx_base == g.idx_base && g.nq <= pr->nq) {
             ctx->cur_idx = pr->idx.as<uint32_t>();
             hipLaunchKernelGGL(k_batch_err, dim3(1), dim3(1), 0, s, ctx->d_state, (const DevState *)pr->st);      // an unsorted batch is this measure's error too
             return MTH_OK;
         }
     }
-    MTH_HIP(ctx, ctx->idx.reserve((size_t)(nq + 1) * 4, s));
-    LaunchTimer lt(ctx, K_INDEX);
-    const uint32_t nb = (b.n_reads / 4 + 1 + BLOCK * IDX_GROUPS - 1) / (BLOCK * IDX_GROUPS);
-    hipLaunchKernelGGL(k_build_index<1>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, idx_base, 0, (int)IDX_QSHIFT, nq,
-                       (int)((reinterpret_cast<uintptr_t>(b.read_start) & 15u) == 0), ctx->idx.as<uint32_t>(), (uint32_t *)nullptr, ctx->d_state,
-                       ctx->d_state, (unsigned long long *)nullptr, 0u, (const uint32_t *)nullptr, b.n_cpgs, b.cpg_off, b.n_cpgs ? b.cpg_pos : nullptr);   // cur_base is rewritten by the next PDR batch's own index build
+    MTH_HIP(ctx, ctx->idx.reserve((size_t)(g.nq + 1) * 4, s));
+    // (cur_base is rewritten by the next PDR batch's own index build)
+    launch_fine_index(ctx, s, b, g.idx_base, g.nq, ctx->idx.as<uint32_t>(), ctx->d_state, ctx->d_state, nullptr, 0u, nullptr);
     return MTH_OK;
 }
 
@@ -1716,94 +1712,22 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
     float *o_pdr = sink ? sink->pdr : ctx->out_pdr.as<float>();
     uint32_t *o_nc = sink ? sink->nc : ctx->out_nc.as<uint32_t>();
     uint32_t *o_nd = sink ? sink->nd : ctx->out_nd.as<uint32_t>();
-    const int64_t region_len = (int64_t)b.region_end - b.region_beg;
-    // Two forms of the tile kernel.  Dense batches: one LDS counter per position, 4096-bp tiles (8192-bp tiles, 4 workgroups per CU:
-    // config 3 0.1655 -> 0.1956 ms, config 2 0.0858 -> 0.1069; profiles/r03_stream_kernel.md).  Sparse batches (WGBS depth: few calls
-    // per read and few reads per 4096 bp, so that a tile's fixed chain of round trips is what the kernel waits for): hashed sites,
-    // 16384- to 65536-bp tiles (mth_pdr_wide.hip).  MTH_PDR_WIDE=0 / 14 / 15 / 16 overrides the choice (tests, A/B).
-    int wide_shift = 0;
-    if (b.n_reads && region_len > 0) {
-        const double sites_per_bp = (double)b.n_cpgs / (double)b.n_reads / (double)std::max(b.max_span, 1);
-        const double reads_per_bp = (double)b.n_reads / (double)region_len;
-        // (1024 slots: up to ~0.6 of them for the sites a tile can expect; a denser stretch is redone in halves)
-        // A hashed insert (compare-and-swap + adds) costs more than the dense form's one LDS add: the wide form only pays while few
-        // calls are inserted.  Expected insertions per read = E[n; n >= min_cpgs] = lambda P(N >= min_cpgs - 1) for Poisson calls per
-        // read: 0.22 under the CLI defaults at config-3 density (0.117 against 0.170 ms), 1.37 for FDRP's site discovery (min_cpgs 1:
-        // 0.202 against 0.153 ms -- that pass keeps the dense form).
-        double ins_per_read = 0.0;
-        if (p.want_pdr) {
-            const double lam = (double)b.n_cpgs / (double)b.n_reads;
-            const int kmin = (int)std::min<uint32_t>(std::max<uint32_t>(p.pdr_min_cpgs, 1u), 64u) - 1;     // P(N >= kmin)
-            double term = std::exp(-lam), cdf = 0.0;
-            for (int k = 0; k < kmin; ++k) { cdf += term; term *= lam / (double)(k + 1); }
-            ins_per_read = lam * std::max(0.0, 1.0 - cdf);
-        }
-        // Depth: measured on a chr1-sized contig at density 0.0091 -- 16 M reads (10x) dense 0.170 / wide 0.113 ms, 24 M 0.201 / 0.160,
-        // 32 M 0.238 / 0.196, 48 M (29x) 0.295 / 0.277, each with a gather of 0.027 / 0.008 on top; 65536-bp tiles only lead at 10x.
-        if (sites_per_bp <= 0.012 && reads_per_bp * 4096.0 <= 900.0 && ins_per_read <= 0.6)
-        {
-            wide_shift = sites_per_bp * 65536.0 <= 0.6 * 1024 && reads_per_bp * 65536.0 <= 4500.0 ? 16 : sites_per_bp * 32768.0 <= 0.6 * 1024 ? 15 : 14;
-            // ... and enough tiles to fill the chip twice over (7 workgroups on each of 256 CUs): a short contig takes narrower tiles
-            // (config 3's 24 contigs: 2.33 -> 2.20 ms; the same rule made the quartet / pairs kernels slower -- 2.36 -> 2.62, 2.72 -> 2.95 ms --
-            // whose persistent workgroups gain more from the wider tile than they lose to a half-filled last round)
-            while (wide_shift > 14 && (region_len >> wide_shift) < 2 * 7 * 256) --wide_shift;
-        }
-    }
-    if (const char *e = getenv("MTH_PDR_WIDE")) { const int k = atoi(e); wide_shift = k >= 14 && k <= 16 ? k : 0; }
-    if (fq && fq->force && wide_shift == 0) wide_shift = 14;       // MTH_MULTI_FUSED on a dense batch
-    const int tile_w = wide_shift ? 1 << wide_shift : 4096;
-    // Wide form: the tile need not be as wide as its slice.  A chr1-sized contig is 2.12 rounds of 65536-position tiles over the chip's
-    // 1 792 resident workgroups (7 on each of 256 CUs) and ends on a nearly empty third round; tiles of region / (3 x 1 792) positions
-    // make three full rounds of smaller tiles.  Only where the last round would be less than half full, and never below
-    // half the slice (the chain of round trips per tile is what the wide form exists to pay less often).  MTH_PDR_WIDE_W forces a width.
-    uint32_t tile_w_rt = 0;
-    if (wide_shift) {
-        const double slots = 7.0 * 256.0, rounds = (double)region_len / (double)tile_w / slots;
-        const double frac = rounds - std::floor(rounds);
-        if (rounds > 1.0 && rounds < 8.0 && frac > 0.02 && frac < 0.5) {
-            const uint64_t w = (uint64_t)std::ceil((double)region_len / (std::ceil(rounds) * slots));
-            const uint32_t wr = (uint32_t)((w + 63) & ~63ull);
-            if (wr >= (uint32_t)tile_w / 2 && wr < (uint32_t)tile_w) tile_w_rt = wr;
-        }
-        if (const char *e = getenv("MTH_PDR_WIDE_W")) { const int k = atoi(e); tile_w_rt = (k >= 1024 && k < tile_w) ? (uint32_t)k & ~63u : 0u; }
-    }
-    const uint32_t tile_step = tile_w_rt ? tile_w_rt : (uint32_t)tile_w;
-    const uint32_t ntiles = (uint32_t)((region_len + tile_step - 1) / tile_step);
-    if (ntiles == 0) return MTH_OK;
-    // index origin: a whole number of quanta below the region so that halo reads are indexed
-    const int32_t ext = ((b.max_span + 2 + IDX_Q - 1) / IDX_Q) * IDX_Q;
-    const int32_t idx_base = b.region_beg - ext;
-    const uint32_t nq = (uint32_t)(((int64_t)ntiles * tile_step + ext) >> IDX_QSHIFT) + 2;
-
-    // The dense tile kernel's own index: one entry per tile in each of two families (k_build_index<2>).  Site discovery for the walk
-    // measures (sink) leaves the fine index behind for them; the wide form looks up arbitrary stretch bounds.  MTH_COARSE_INDEX=0: A/B.
-    const char *coarse_env = getenv("MTH_COARSE_INDEX");     // (read per call: the tests run both indices in one process)
-    const bool coarse_off = coarse_env && atoi(coarse_env) == 0;
-    // a prepared batch brings its fine index: no index kernel in this call (k_batch_begin does what else that kernel did)
+    // which form, how wide, which index: plan_pdr_lpmd (mth_plan.h)
     Prepared *prep = ctx->cur_prep;
-    if (prep && !(prep->idx_base == idx_base && nq <= prep->nq)) prep = nullptr;
-    const bool coarse = !sink && wide_shift == 0 && !coarse_off && !prep;
-    const uint32_t coarse_stride = (ntiles + 2u + 3u) & ~3u;
+    const PdrPlan pl = plan_pdr_lpmd(batch_shape(b), p, pdr_knobs_from_env(), sink != nullptr, fq && fq->force, L != nullptr,
+                                     prep ? prep->idx_base : 0, prep ? prep->nq : 0u);
+    const int wide_shift = pl.wide_shift, tile_w = pl.tile_w;
+    const uint32_t ntiles = pl.ntiles, nq = pl.nq, nbk = pl.nbk, n_bucket_words = pl.n_bucket_words, coarse_stride = pl.coarse_stride;
+    const int32_t idx_base = pl.idx_base;
+    const bool coarse = pl.coarse, runs = pl.runs;
+    if (ntiles == 0) return MTH_OK;
+    // a prepared batch brings its fine index: no index kernel in this call (k_batch_begin does what else that kernel did)
+    if (!pl.prepared_fits) prep = nullptr;
     if (!prep) MTH_HIP(ctx, b_idx.reserve(coarse ? (size_t)coarse_stride * 2 * 4 : (size_t)(nq + 1) * 4, s));
     const uint32_t *fine_idx = prep ? prep->idx.as<uint32_t>() : nullptr;
     ctx->cur_idx = fine_idx;                      // (the walks that follow a discovery pass read the index this call used)
-    // the run form of the dense kernel (k_pdr_lpmd_runs; persistent workgroups, no index, no atomics): opt-in with MTH_TILE_RUNS=1 --
-    // parity-green on every PDR / LPMD case, measured SLOWER than the one-tile-per-workgroup form on config 2 (0.127 against 0.084 ms;
-    // profiles/r05_persistent.md).  8-bit relative positions, call offsets that fit a buffer descriptor's 32-bit byte offset.
-    const char *runs_env = getenv("MTH_TILE_RUNS");          // (read per call: the tests switch it per case)
-    const bool runs = wide_shift == 0 && b.cpg_rel != nullptr && b.n_cpgs < (1u << 30) && runs_env && atoi(runs_env) == 1;
     const uint32_t G = runs ? runs_grid(ntiles) : 0u;
-    // threads per workgroup of the one-tile-per-workgroup form: 128 (two waves, two chunks of reads per trip, nine workgroups on a CU;
-    // profiles/tile_two_waves.md) for pipelined batches with 8-bit relative positions, 256 for 16-bit ones (built for 256 only) and for
-    // a batch outside a pipelined run -- a job's first batch, MTH_PIPELINE=0, site discovery through a sink: alone on the chip the
-    // four-wave kernel is the faster one (75.8 against 82.2 us on config 2); the two-wave form wins where the index build, the gather
-    // and the other lane's tile kernel run beside it.  MTH_TILE_B=128 / 256 forces either for 8-bit batches (read per call: the tests
-    // run both in one process).
-    int tile_b = L ? MTH_TILE_B_DEFAULT : 256;
-    if (const char *e = getenv("MTH_TILE_B")) { const int k = atoi(e); if (k == 128 || k == 256) tile_b = k; }
     MTH_HIP(ctx, b_tile_cnt.reserve((size_t)ntiles * 4 * (runs ? 4 : 1), s));
-    const uint32_t nbk = (ntiles + (1u << TILE_BUCKET_SHIFT) - 1) >> TILE_BUCKET_SHIFT;
-    const uint32_t n_bucket_words = nbk * 5u;      // rows, 4 LPMD sums per bucket
     // run form: [G + 1] first tiles, [G] rows (32-bit words), then [G][4] LPMD sums
     const size_t run_words = ((size_t)G + 2u) / 2u + ((size_t)G + 1u) / 2u;
     MTH_HIP(ctx, b_bucket.reserve(((size_t)n_bucket_words + run_words + (size_t)G * 4u) * sizeof(unsigned long long), s));
@@ -1814,18 +1738,17 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
         else hipLaunchKernelGGL(k_batch_begin, dim3(1), dim3(256), 0, s, lane_st, L ? (DevState *)nullptr : cst, (const DevState *)prep->st,
                                 b_bucket.as<unsigned long long>(), n_bucket_words);
     } else if (!runs || sink) {      // (the run form needs no index; site discovery leaves the fine one behind for the walks)
-        LaunchTimer lt(ctx, K_INDEX);
-        const uint32_t nb = (b.n_reads / 4 + 1 + BLOCK * IDX_GROUPS - 1) / (BLOCK * IDX_GROUPS);
-        const int al16 = (int)((reinterpret_cast<uintptr_t>(b.read_start) & 15u) == 0);
-        if (coarse)
+        if (coarse) {
+            LaunchTimer lt(ctx, K_INDEX);
+            const uint32_t nb = (b.n_reads / 4 + 1 + BLOCK * IDX_GROUPS - 1) / (BLOCK * IDX_GROUPS);
+            const int al16 = (int)batch_shape(b).start_al16;
             hipLaunchKernelGGL(k_build_index<2>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, b.region_beg - b.max_span + 1, b.region_beg + 1,
                                DENSE_TILE_SHIFT, ntiles + 1u, al16, b_idx.as<uint32_t>(), b_idx.as<uint32_t>() + coarse_stride, lane_st,
                                L ? (DevState *)nullptr : cst, b_bucket.as<unsigned long long>(), n_bucket_words, b.cpg_off, b.n_cpgs, b.cpg_off,
                                b.n_cpgs ? b.cpg_pos : nullptr);
-        else
-            hipLaunchKernelGGL(k_build_index<1>, dim3(nb), dim3(BLOCK), 0, s, b.read_start, b.n_reads, idx_base, 0, (int)IDX_QSHIFT, nq, al16,
-                               b_idx.as<uint32_t>(), (uint32_t *)nullptr, lane_st, L ? (DevState *)nullptr : cst,
-                               b_bucket.as<unsigned long long>(), n_bucket_words, b.cpg_off, b.n_cpgs, b.cpg_off, b.n_cpgs ? b.cpg_pos : nullptr);
+        } else
+            launch_fine_index(ctx, s, b, idx_base, nq, b_idx.as<uint32_t>(), lane_st, L ? (DevState *)nullptr : cst,
+                              b_bucket.as<unsigned long long>(), n_bucket_words, b.cpg_off);
     } else if (b.n_reads && b.n_cpgs) {      // the run form: no index kernel, so the look for the word of position -1 is a launch of its own
         hipLaunchKernelGGL(k_minus_one_check, dim3(std::min<uint32_t>((b.n_reads + 255) / 256, 64u)), dim3(256), 0, s, b.read_start, b.cpg_off, b.cpg_pos,
                            b.n_reads, b.n_cpgs, lane_st);
@@ -1843,7 +1766,7 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
     a.min_dist = p.lpmd_min_distance; a.max_dist = p.lpmd_max_distance;
     a.pdr_min_qual = p.pdr_min_qual; a.lpmd_min_qual = p.lpmd_min_qual;
     a.want_pdr = p.want_pdr; a.want_lpmd = p.want_lpmd;
-    a.tile_w_rt = tile_w_rt;
+    a.tile_w_rt = pl.tile_w_rt;
     RunArgs ra;
     ra.run_tile0 = reinterpret_cast<uint32_t *>(b_bucket.as<unsigned long long>() + n_bucket_words);
     ra.run_rows = ra.run_tile0 + (((size_t)G + 2u) / 2u) * 2u;
@@ -1855,7 +1778,7 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
     if (!d_rtrace) (void)hipMalloc((void **)&d_rtrace, 8 * 8 * 4 * 4096);
     ra.trace = G <= 4096 ? d_rtrace : nullptr;
 #endif
-    ra.hint_stride = (uint32_t)std::max(1.0, std::ceil((double)b.n_reads / (double)ntiles * (1.0 + (double)b.max_span / (double)tile_w) * 1.3 / 63.0));
+    ra.hint_stride = pl.hint_stride;
 #ifdef MTH_TILE_TRACE
     static unsigned long long *d_ttrace = nullptr;
     if (!d_ttrace) (void)hipMalloc((void **)&d_ttrace, 8 * 8 * 262144);
@@ -1867,7 +1790,7 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
         if (wide_shift && fq && ntiles <= fq->max_tiles) { launch_tile_fused(a, *fq, ntiles, wide_shift, r8, s); fq->taken = true; fq->ntiles = ntiles; }
         else if (wide_shift) launch_tile_wide(a, ntiles, wide_shift, r8, s);
         else if (runs) launch_runs(a, ra, ntiles, G, s);
-        else if (r8 && tile_b == 128) launch_tile<(1 << DENSE_TILE_SHIFT), 128, uint8_t>(a, ntiles, s);
+        else if (r8 && pl.tile_b == 128) launch_tile<(1 << DENSE_TILE_SHIFT), 128, uint8_t>(a, ntiles, s);
         else if (r8) launch_tile<(1 << DENSE_TILE_SHIFT), 256, uint8_t>(a, ntiles, s); else launch_tile<(1 << DENSE_TILE_SHIFT), 256, uint16_t>(a, ntiles, s);
     }
     {
@@ -1879,25 +1802,21 @@ int launch_pdr_lpmd(mth_ctx *ctx, const mth_batch_t &b, const mth_pdr_lpmd_param
             reset_first = ctx->reset_pending ? 1 : 0;
             ctx->reset_pending = false;
         }
-        static const bool gather1 = getenv("MTH_GATHER") && atoi(getenv("MTH_GATHER")) == 1;       // A/B: the per-tile form
+        // the three gathers differ in what they walk (tiles, runs); where the rows and the job's counters go is the same twelve arguments
+        auto gather = [&](auto kernel, dim3 grid, dim3 block, uint32_t rows_per_unit, auto... walked) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, s, b_scratch.as<SiteRec>(), b_tile_cnt.as<uint32_t>(), walked...,
+                               p.want_pdr ? 0 : 1, (int)p.want_lpmd, cst, L ? (const DevState *)L->st : (const DevState *)cst,
+                               L ? ctx->lane[li ^ 1].st : (DevState *)nullptr, L ? L->st : (DevState *)nullptr, reset_first,
+                               bcnt, rows_per_unit, o_pos, o_pdr, o_nc, o_nd);
+        };
         if (runs)
-            hipLaunchKernelGGL(k_gather_runs, dim3(p.want_pdr ? G : 1u), dim3(256), 0, s, b_scratch.as<SiteRec>(),
-                               b_tile_cnt.as<uint32_t>(), ra.run_tile0, ra.run_rows, ra.run_lpmd, G,
-                               p.want_pdr ? 0 : 1, (int)p.want_lpmd, cst, L ? (const DevState *)L->st : (const DevState *)cst,
-                               L ? ctx->lane[li ^ 1].st : (DevState *)nullptr, L ? L->st : (DevState *)nullptr, reset_first,
-                               bcnt, (uint32_t)tile_w / 4u, o_pos, o_pdr, o_nc, o_nd);
-        else if (gather1)
-            hipLaunchKernelGGL(k_gather, dim3(p.want_pdr ? (ntiles + GATHER_WAVES - 1) / GATHER_WAVES : 1u), dim3(p.want_pdr ? 64 * GATHER_WAVES : 64), 0, s, b_scratch.as<SiteRec>(),
-                               b_tile_cnt.as<uint32_t>(), b_bucket.as<unsigned long long>(), nbk, ntiles,
-                               p.want_pdr ? 0 : 1, (int)p.want_lpmd, cst, L ? (const DevState *)L->st : (const DevState *)cst,
-                               L ? ctx->lane[li ^ 1].st : (DevState *)nullptr, L ? L->st : (DevState *)nullptr, reset_first,
-                               bcnt, (uint32_t)tile_w, o_pos, o_pdr, o_nc, o_nd);
+            gather(k_gather_runs, dim3(p.want_pdr ? G : 1u), dim3(256), (uint32_t)tile_w / 4u, ra.run_tile0, ra.run_rows, ra.run_lpmd, G);
+        else if (gather_per_tile_knob())      // A/B: the per-tile form
+            gather(k_gather, dim3(p.want_pdr ? (ntiles + GATHER_WAVES - 1) / GATHER_WAVES : 1u), dim3(p.want_pdr ? 64 * GATHER_WAVES : 64),
+                   (uint32_t)tile_w, b_bucket.as<unsigned long long>(), nbk, ntiles);
         else
-            hipLaunchKernelGGL(k_gather2, dim3(p.want_pdr ? (ntiles + GATHER2_TILES - 1) / GATHER2_TILES : 1u), dim3(256), 0, s, b_scratch.as<SiteRec>(),
-                               b_tile_cnt.as<uint32_t>(), b_bucket.as<unsigned long long>(), nbk, ntiles,
-                               p.want_pdr ? 0 : 1, (int)p.want_lpmd, cst, L ? (const DevState *)L->st : (const DevState *)cst,
-                               L ? ctx->lane[li ^ 1].st : (DevState *)nullptr, L ? L->st : (DevState *)nullptr, reset_first,
-                               bcnt, (uint32_t)tile_w, o_pos, o_pdr, o_nc, o_nd);
+            gather(k_gather2, dim3(p.want_pdr ? (ntiles + GATHER2_TILES - 1) / GATHER2_TILES : 1u), dim3(256), (uint32_t)tile_w,
+                   b_bucket.as<unsigned long long>(), nbk, ntiles);
         if (L) { MTH_HIP(ctx, hipEventRecord(L->done, s)); ctx->pipe_tail = li; }
     }
 #ifdef MTH_RUNS_TRACE

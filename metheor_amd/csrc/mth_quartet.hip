@@ -34,7 +34,7 @@ namespace mth {
 constexpr int QT_NC = 8;   // calls of a read held in registers
 constexpr int QT_QCAP = 2048;   // candidate reads per fill of the contributor queue
 constexpr int QT_OCC = 6;  // waves per SIMD (LDS: 23 KiB per workgroup = 6 per CU)
-constexpr int QT_S = 512, QT_B = 256, QT_U = 2, QT_CHUNK = 512, QT_GRID = 8192;   // (the tile width is a template parameter: 8192 / 16384 / 32768, chosen per batch)
+constexpr int QT_B = 256, QT_U = 2, QT_CHUNK = 512, QT_GRID = 8192;   // (the tile width is a template parameter: 8192 / 16384 / 32768, chosen per batch)
 
 __device__ __forceinline__ unsigned long long qhash(unsigned long long x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
@@ -391,27 +391,8 @@ __global__ __launch_bounds__(QT_B, QT_OCC) void k_quartet_tile(const QTileArgs a
 }
 
 // ---- what ME / PM brings to the tile-row driver (mth_tile_rows.hip) -----------------------------------------------
-// Tile width: wide tiles pay the per-tile costs (index look-up, LDS clear, barriers, halo reads) less often, but the
-// table holds QT_S quartets and a 16-bit bin 65535 candidate reads.  About one quartet starts per CpG site; sites per
-// bp ~ calls per read / read length (max_span stands in for the length).  Tiles that overflow anyway take the global path.
-static int quartet_tile_shift(const mth_batch_t &d, const TileParams &) {
-    const int64_t region_len = (int64_t)d.region_end - d.region_beg;
-    int tile_shift = 13;
-    if (d.n_reads && region_len > 0) {
-        const double sites_per_bp = (double)d.n_cpgs / (double)d.n_reads / (double)std::max(d.max_span, 1);
-        const double reads_per_bp = (double)d.n_reads / (double)region_len;
-        // a site starts a quartet only if three more sites follow within a read's span: Poisson tail P(>= 3 | sites_per_bp x span).
-        // (Without it config 2 stayed at 8192 bp and config-3 density at 16384: 0.119 against 0.100 ms at 16384 and 0.159 against
-        // 0.112 ms at 32768 -- a tile's fixed chain of round trips and barriers is what these kernels wait for.)
-        const double lam = sites_per_bp * (double)std::max(d.max_span, 1);
-        const double p3 = std::max(0.05, 1.0 - std::exp(-lam) * (1.0 + lam + 0.5 * lam * lam));
-        while (tile_shift < 16 && sites_per_bp * p3 * (double)(2 << tile_shift) <= 0.4 * QT_S &&
-               reads_per_bp * (double)((2 << tile_shift) + d.max_span + 2 * IDX_Q) <= 30000.0)
-            ++tile_shift;
-    }
-    if (const char *e = getenv("MTH_QUARTET_TILE_SHIFT")) tile_shift = std::min(16, std::max(13, atoi(e)));   // tests / tuning
-    return tile_shift;
-}
+// the tile width: quartet_tile_shift of mth_plan.h
+static int quartet_tile_shift(const mth_batch_t &d, const TileParams &) { return quartet_tile_shift(batch_shape(d), tile_shift_knob("MTH_QUARTET")); }
 
 static hipError_t quartet_grow_rows(mth_ctx *ctx, uint64_t cap, uint64_t used) {
     hipStream_t s = ctx->stream;
@@ -433,7 +414,7 @@ static void quartet_launch_tiles(mth_ctx *ctx, const mth_batch_t &d, const TileP
     a.idx = idx_ptr(ctx);
     a.region_beg = d.region_beg; a.region_end = d.region_end; a.idx_base = idx_base; a.max_span = d.max_span;
     a.n_reads = d.n_reads; a.ntiles = ntiles; a.n_cpgs = (uint32_t)d.n_cpgs; a.min_qual = p.quartet.min_qual;
-    a.force_heavy = getenv("MTH_QUARTET_FORCE_GLOBAL") ? 1 : 0;
+    a.force_heavy = force_global_knob("MTH_QUARTET") ? 1 : 0;
     a.row_total = qs + 1; a.row_cap = row_cap; a.unfit = qs + 6; a.n_heavy = qs + 5;
     a.tile_flag = t.tflag.as<uint32_t>();
     a.tile_row0 = t.tile_row0.as<unsigned long long>() + tiles_before;
@@ -467,7 +448,7 @@ static int quartet_global_path(mth_ctx *ctx, const mth_batch_t &d, const TilePar
     unsigned long long n_slots = 1024;
     while (n_slots < bound / 2) n_slots <<= 1;
     unsigned long long wide_cap = std::max<unsigned long long>(ctx->q_wpat.cap / 4, 65536), wide_n = 0;
-    if (const char *e = getenv("MTH_QUARTET_SLOTS_MIN")) { const unsigned long long k = strtoull(e, nullptr, 10); if (k >= 16) { n_slots = 16; while (n_slots < k) n_slots <<= 1; } }   // tests: force the retry
+    if (const unsigned long long k = slots_min_knob("MTH_QUARTET")) n_slots = k;   // tests: force the retry
     for (;;) {
         MTH_HIP(ctx, ctx->q_keys.reserve(n_slots * 8, s));
         MTH_HIP(ctx, ctx->q_hist.reserve(n_slots * 64, s));

@@ -615,7 +615,7 @@ int launch_pdr_exact(mth_ctx *ctx, const mth_batch_t &d, const mth_pdr_lpmd_para
     MTH_HIP(ctx, ctx->w_cov.reserve(bound * 4, s));
     MTH_HIP(ctx, ctx->w_aux.reserve(bound * 4, s));
     MTH_HIP(ctx, ctx->w_flags.reserve(bound * 4, s));
-    const int32_t ext = ((d.max_span + 2 + IDX_Q - 1) / IDX_Q) * IDX_Q;
+    const int32_t ext = index_ext(d.max_span);
     PdrWalkArgs a;
     a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos; a.idx = idx_ptr(ctx);
     a.sites_st = ctx->d_state2; a.site_pos = ctx->s_pos.as<int32_t>();
@@ -661,11 +661,12 @@ int mth_mhl_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_mhl_p
     // Default: one tile pass computes every site whose covering reads form a single segment and leaves the others to
     // k_mhl_walk_big (mth_mhl_tile.hip).  MTH_MHL_WALK=1: round 2's form -- PDR-style site discovery, then the per-site walk
     // out of LDS (k_mhl_walk_lds) -- kept for A/B and as the tests' second implementation.
-    const bool walk_form = getenv("MTH_MHL_WALK") != nullptr;
+    const MhlKnobs kn = mhl_knobs_from_env();
+    const bool walk_form = kn.walk;
     if (walk_form) {
         // (the site list is NOT filtered by min_depth here: the walk skips such sites itself and keeps its staging dense)
         if ((rc = discover_sites(ctx, d, params->min_cpgs, params->min_qual, bound))) return rc;
-    } else if ((rc = launch_mhl_tile(ctx, d, *params, bound))) return rc;
+    } else if ((rc = launch_mhl_tile(ctx, d, *params, kn, bound))) return rc;
     if (bound == 0) { ctx->m_batches.push_back(BatchMeta{batch->tid}); bound = 1; }
     else ctx->m_batches.push_back(BatchMeta{batch->tid});
     // per-candidate-site work arrays
@@ -690,7 +691,7 @@ int mth_mhl_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_mhl_p
     MTH_HIP(ctx, ctx->m_batch_rows.reserve((nb + 1) * 4, s, true, nb * 4));
 
     // the walk uses the index the discovery pass just built (same batch, same idx_base arithmetic)
-    const int32_t ext = ((d.max_span + 2 + IDX_Q - 1) / IDX_Q) * IDX_Q;
+    const int32_t ext = index_ext(d.max_span);
     WalkArgs a;
     a.read_start = d.read_start; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
     a.idx = idx_ptr(ctx); a.sites_st = ctx->d_state2; a.site_pos = ctx->s_pos.as<int32_t>();

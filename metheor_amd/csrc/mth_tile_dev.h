@@ -27,8 +27,6 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
     return v;
 }
 
-constexpr int TILE_BUCKET_SHIFT = 8;   // 256 tiles per bucket
-
 // arguments of the PDR + LPMD tile kernels (mth_pdr_lpmd.hip: dense counters, 4096-bp tiles; mth_pdr_wide.hip: hashed sites, wide tiles)
 struct TileArgs {
     const int32_t  *read_start;
@@ -49,7 +47,7 @@ struct TileArgs {
     uint32_t min_cpgs;
     int32_t  min_dist, max_dist;
     uint8_t  pdr_min_qual, lpmd_min_qual, want_pdr, want_lpmd;
-    uint32_t tile_w_rt;    // wide form only: positions per tile when it is not the slice width 1 << SHIFT (0: it is) -- see launch_pdr_lpmd
+    uint32_t tile_w_rt;    // wide form only: positions per tile when it is not the slice width 1 << SHIFT (0: it is) -- see plan_pdr_lpmd
 #ifdef MTH_TILE_TRACE
     unsigned long long *trace;     // experiment build: 8 ticks per tile (tools/tile_trace.py)
 #endif

@@ -27,11 +27,7 @@ __global__ void k_tile_rows_snap(const unsigned long long *__restrict__ w, unsig
 }
 
 // a measure's knob MTH_<MEASURE>_<suffix>
-static const char *knob(const TileRowTable &t, const char *suffix) {
-    char name[48];
-    snprintf(name, sizeof name, "%s_%s", t.env, suffix);
-    return getenv(name);
-}
+static const char *knob(const TileRowTable &t, const char *suffix) { return tile_rows_knob(t.env, suffix); }
 
 int tile_rows_open(mth_ctx *ctx, TileRowTable &t, uint64_t ntiles) {
     hipStream_t s = ctx->stream;

@@ -19,7 +19,7 @@ f32 = np.float32
 @pytest.fixture(autouse=True, params=["auto", "tile", "runs", "wide14", "wide15", "wide16"])
 def kernel_form(request, monkeypatch):
     """every case runs with the engine's own choice of kernel form (MTH_PDR_WIDE unset: the density chooser of
-    launch_pdr_lpmd, the path production takes), through the dense tile kernel (forced: MTH_PDR_WIDE=0), through the
+    plan_pdr_lpmd in mth_plan.h, the path production takes), through the dense tile kernel (forced: MTH_PDR_WIDE=0), through the
     persistent run form of the dense kernel (round 5: k_pdr_lpmd_runs + k_gather_runs, MTH_TILE_RUNS=1) and through the
     hashed-site form for sparse batches (mth_pdr_wide.hip) with 16384-, 32768- and 65536-bp tiles forced"""
     monkeypatch.delenv("MTH_PDR_WIDE", raising=False)
@@ -394,7 +394,7 @@ def test_long_reads_lpmd_only(eng):
 
 
 def test_density_chooser_takes_the_wide_form_on_sparse_batches(eng, kernel_form):
-    """the per-batch choice between the dense tile kernel and the hashed-site form (launch_pdr_lpmd) is what production
+    """the per-batch choice between the dense tile kernel and the hashed-site form (plan_pdr_lpmd, mth_plan.h) is what production
     runs; with MTH_PDR_WIDE unset a WGBS-density batch must take k_pdr_lpmd_wide and a config-2-density batch the dense kernel
     (seen through the engine's per-kernel timers), both equal to the oracle"""
     if kernel_form != "auto":

@@ -1,6 +1,6 @@
 """The hashed-site tile pass (tile_pass in mth_pdr_wide.hip: k_pdr_lpmd_wide and the fused k_multi_tile) at a NARROWED tile width.
 
-launch_pdr_lpmd narrows the tile below its scratch slice (TileArgs::tile_w_rt) where the last round of workgroups would be less than
+plan_pdr_lpmd (mth_plan.h) narrows the tile below its scratch slice (TileArgs::tile_w_rt) where the last round of workgroups would be less than
 half full -- contigs beyond ~29 Mbp, which no other test reaches -- or where MTH_PDR_WIDE_W says so.  Then tile origins are
 region_beg + t * width with the width only a multiple of 64, the slice stays 2^shift wide, a stretch redone in halves ends on a piece
 that is no power of two, the quartet side owns [T0, T1) of the narrowed tile, and the fine index has less slack behind region_end.
@@ -267,7 +267,7 @@ def test_forced_width_site_discovery(eng, monkeypatch, shift, w, consumer):
 # ---- d. the width the host chooses by itself ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("length", [32_000_000, 40_000_000, 45_000_000])
 def test_chooser_narrows_long_contigs(eng, length):
-    """nothing forced: contigs of 32 and 40 Mbp take 8960- and 11200-position tiles by launch_pdr_lpmd's own rule (1.09 and 1.36 rounds
+    """nothing forced: contigs of 32 and 40 Mbp take 8960- and 11200-position tiles by plan_pdr_lpmd's own rule (1.09 and 1.36 rounds
     of 16384-position tiles over 1792 workgroups), one of 45 Mbp (1.53 rounds) keeps 16384.  The fused pass's tile count says which
     width ran; the plain PDR + LPMD call on the same batch must run k_pdr_lpmd_wide alone."""
     assert "MTH_PDR_WIDE" not in os.environ and "MTH_PDR_WIDE_W" not in os.environ

@@ -1,5 +1,5 @@
 """The inputs of tests/test_gpu_wide_width.py on the CPU (tests/wide_width_util.py): the restated width rule gives the widths worked
-out by hand from launch_pdr_lpmd's rule, and the generated batches hold every feature the GPU cases rely on -- calls, read starts and
+out by hand from the rule of plan_pdr_lpmd (mth_plan.h), and the generated batches hold every feature the GPU cases rely on -- calls, read starts and
 quartets on both sides of every narrowed tile boundary, a tile with more distinct sites and quartets than the LDS tables hold, a tile
 with more candidate reads than the queues hold, reads with no call and with more than 8, a batch that ends inside its last reads'
 8-slot windows, and long contigs that stay in the chooser's sparse branch -- so that a later edit cannot quietly make them trivial."""

@@ -1,5 +1,6 @@
 """Inputs for the hashed-site tile pass at a narrowed tile width (TileArgs::tile_w_rt, mth_pdr_wide.hip) and a plain restatement of
-the host rule that picks the width (launch_pdr_lpmd, "Wide form: the tile need not be as wide as its slice").  numpy only; nothing
+the host rule that picks the width (plan_pdr_lpmd in mth_plan.h, "Wide form: the tile need not be as wide as its slice";
+tests/test_launch_plan.py compares the two).  numpy only; nothing
 here computes a measure.  tests/test_wide_width_inputs.py shows on the CPU that the inputs hold what they claim,
 tests/test_gpu_wide_width.py runs them."""
 import math
@@ -17,7 +18,7 @@ SLOTS = 7 * 256             # resident workgroups of the wide form
 
 
 def narrowed_width(region_len, shift):
-    """the tile width launch_pdr_lpmd chooses by itself for a region of region_len positions under 2^shift-position slices; 0 where
+    """the tile width plan_pdr_lpmd (mth_plan.h) chooses by itself for a region of region_len positions under 2^shift-position slices; 0 where
     the tile stays as wide as its slice"""
     tile_w = 1 << shift
     rounds = float(region_len) / float(tile_w) / float(SLOTS)
@@ -181,7 +182,7 @@ def long_sparse_contig(length, width, seed=1):
 
 
 def chooser_figures(c, min_cpgs=4):
-    """the two quantities launch_pdr_lpmd's density chooser weighs: calls per read per position of the span, and the expected
+    """the two quantities the density chooser of plan_pdr_lpmd (mth_plan.h) weighs: calls per read per position of the span, and the expected
     insertions per read E[n; n >= min_cpgs] for Poisson calls"""
     n_reads = len(c["read_start"])
     lam = float(c["cpg_off"][-1]) / n_reads
