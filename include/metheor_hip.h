@@ -370,6 +370,14 @@ int  mth_decode_set_xm_min_mapq(mth_ctx_t *ctx, uint32_t min_mapq);
  * The 4 bytes after each payload (the gzip trailer's CRC32) must lie inside the file bytes given: they are verified. */
 int  mth_bgzf_inflate(mth_ctx_t *ctx, const void *file, uint64_t n_bytes, const uint64_t *coff, const uint32_t *csize,
                       const uint32_t *isize, uint64_t n_blocks, void *dst_host, uint64_t *n_out);
+/* The mirror image, the compression step alone: src[0, n_bytes) (mem says where it lives) cut at cut_off (HOST memory, n_blocks + 1
+ * ascending offsets from 0 to n_bytes, at most 0xff00 bytes apart) becomes n_blocks BGZF blocks, each deflated on its own by
+ * k_deflate (RFC 1951 dynamic Huffman, or fixed or stored where that is smaller: a payload is never above its input + 5 bytes)
+ * and framed with the BC subfield, CRC32 and ISIZE.  The output is a function of the bytes and the cuts alone.  *out_bytes =
+ * the blocks back to back, *out_n bytes, block b at (*out_block_off)[b] (n_blocks + 1 entries; may be NULL): host memory owned
+ * by the context, valid until its next deflate or tag call.  n_blocks == 0 returns nothing; the EOF block is the caller's. */
+int  mth_bgzf_deflate(mth_ctx_t *ctx, const void *src, uint64_t n_bytes, int mem, const uint64_t *cut_off, uint64_t n_blocks,
+                      const uint8_t **out_bytes, uint64_t *out_n, const uint64_t **out_block_off);
 /* The whole step on the device: BGZF inflate (one wave per block, RFC 1951 stored / fixed / dynamic blocks, checked
  * against ISIZE), record boundaries (one thread per block; htslib-family writers never let a record straddle a BGZF
  * block, which is verified -- MTH_ERR_UNALIGNED otherwise, nothing is appended then), record + XM decode as above.
@@ -543,6 +551,21 @@ typedef struct {
 int  mth_tag_set_genome(mth_ctx_t *ctx, int32_t n_refs, const int64_t *ref_len, const uint8_t *const *seq, const int64_t *seq_len);
 int  mth_tag_records(mth_ctx_t *ctx, const void *raw, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
                      int is_paired_end, mth_tag_out_t *out);
+/* `tag --output-format bam`: mth_tag_records' arguments and errors (MTH_ERR_FORMAT where the reference panics; nothing is
+ * returned then), but what comes back is the window's TAGGED records as BGZF blocks, made on the device: every input record with
+ * XM:Z:<string> appended as its last optional field (its bytes, 'X' 'M' 'Z', the string, NUL; block_size raised by the string's
+ * length + 4 -- a zero-length string still gets the field), cut into blocks by htslib's rule (at most 0xff00 bytes per block, a
+ * record that does not fit starts a new block, a record longer than a block starts one and fills consecutive blocks, the window's
+ * last block is closed short) and deflated as mth_bgzf_deflate does.  The strings stay on the device; only the records' sizes come
+ * back for the cuts.  bytes / block_off: host memory owned by the context, valid until its next deflate or tag call; block b is
+ * bytes[block_off[b] .. block_off[b + 1]).  stream_bytes = size of the tagged record stream.  No EOF block is added. */
+typedef struct {
+    uint64_t        n_records, n_blocks, stream_bytes, n_bytes;
+    const uint8_t  *bytes;
+    const uint64_t *block_off;  /* n_blocks + 1 */
+} mth_tag_bam_out_t;
+int  mth_tag_records_bam(mth_ctx_t *ctx, const void *raw, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
+                         int is_paired_end, mth_tag_bam_out_t *out);
 /* mth_tag_set_genome with the FASTA read on the device: the same genome (bytes, offsets, header lengths) straight from the
  * file's text, plain or bgzip-compressed -- what faidx_fetch_seq(name, 0, LN) returns for every contig, with no host pass over
  * the bases.

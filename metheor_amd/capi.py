@@ -16,7 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -114,6 +114,14 @@ class mth_tag_out_t(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("xm_off", C.c_void_p), ("xm_len", C.c_void_p), ("xm", C.c_void_p)]
 
 
+class mth_tag_bam_out_t(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_blocks", C.c_uint64), ("stream_bytes", C.c_uint64), ("n_bytes", C.c_uint64),
+                ("bytes", C.c_void_p), ("block_off", C.c_void_p)]
+
+
+BGZF_MAX_BLOCK = 0xff00
+
+
 def library_path():
     # METHEOR_HIP_LIB: another build of the same library (A/B timing of kernel variants on one box)
     return os.environ.get("METHEOR_HIP_LIB") or os.path.join(_HERE, "libmetheor_hip.so")
@@ -177,6 +185,7 @@ def lib():
         L.mth_decode_set_cpg_filter.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mth_decode_set_xm_min_mapq.argtypes = [vp, C.c_uint32]
         L.mth_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
+        L.mth_bgzf_deflate.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp)]
         L.mth_bgzf_decode.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(mth_decoded_t)]
         L.mth_bgzf_decode_straddle.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint, C.POINTER(mth_decoded_t),
                                                C.POINTER(mth_straddle_info_t)]
@@ -189,6 +198,7 @@ def lib():
         L.mth_tag_set_genome_fasta.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, vp, vp]
         L.mth_tag_genome_fetch.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp]
         L.mth_tag_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_tag_out_t)]
+        L.mth_tag_records_bam.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_tag_bam_out_t)]
         L.mth_decode_set_genome.argtypes = [vp, C.c_int, C.c_int]
         L.mth_decoded_fetch.argtypes = [vp] * 9
         L.mth_decoded_contigs.argtypes = [vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -526,6 +536,18 @@ class Engine:
         assert n.value == len(out)
         return out
 
+    def bgzf_deflate(self, data, cuts=None):
+        """data (bytes / uint8 array, host) as BGZF blocks made on the device (k_deflate), back to back, without the EOF block;
+        cuts: ascending offsets from 0 to len(data), at most 0xff00 apart (default: every 0xff00 bytes).  -> bytes"""
+        src = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+        if cuts is None:
+            cuts = list(range(0, src.size, BGZF_MAX_BLOCK)) + [src.size] if src.size else [0]
+        cut = np.ascontiguousarray(cuts, np.uint64)
+        out, n, boff = C.c_void_p(), C.c_uint64(0), C.c_void_p()
+        self._check(self.L.mth_bgzf_deflate(self.h, src.ctypes.data if src.size else None, src.size, MTH_MEM_HOST, cut.ctypes.data,
+                                            len(cut) - 1, C.byref(out), C.byref(n), C.byref(boff)))
+        return C.string_at(out.value, n.value) if n.value else b""
+
     def bgzf_decode(self, file_bytes, coff, csize, isize, first_byte, append=False):
         """file_bytes: the BAM file (bytes / uint8 array, host); coff/csize/isize: per-BGZF-block payload offset, payload
         size, inflated size.  Inflate + record walk + decode on the device; returns (n_reads, n_cpgs)."""
@@ -631,6 +653,17 @@ class Engine:
         xo = np.ctypeslib.as_array(C.cast(t.xm_off, C.POINTER(C.c_uint64)), shape=(n + 1,))
         xl = np.ctypeslib.as_array(C.cast(t.xm_len, C.POINTER(C.c_uint32)), shape=(n,))
         return [C.string_at(t.xm + int(xo[i]), int(xl[i])) for i in range(n)]
+
+    def tag_records_bam(self, raw, rec_off, is_paired_end=False):
+        """tag_records' arguments; -> (the window's tagged records as BGZF blocks (bytes, no EOF block), size of the tagged record
+        stream, number of blocks): every record with XM:Z appended as its last field, assembled and deflated on the device"""
+        rb = np.frombuffer(raw, np.uint8)
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        t = mth_tag_bam_out_t()
+        n = len(off) - 1
+        self._check(self.L.mth_tag_records_bam(self.h, rb.ctypes.data if len(rb) else None, len(rb), off.ctypes.data, max(n, 0), 0,
+                                               int(bool(is_paired_end)), C.byref(t)))
+        return (C.string_at(t.bytes, t.n_bytes) if t.n_bytes else b""), int(t.stream_bytes), int(t.n_blocks)
 
     def decode_set_genome(self, enabled, is_paired_end=False):
         """derive the calls of the following decode_records / bgzf_decode calls from the genome of tag_set_genome instead of

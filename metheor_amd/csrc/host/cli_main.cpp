@@ -6,6 +6,7 @@
 // 101 with the panic message on stderr.  There is no CPU fallback: a measure whose device kernel is
 // not built yet fails loudly.
 #include <unistd.h>
+#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
@@ -119,7 +120,9 @@ const std::vector<Cmd> &commands() {
           O_CPG, O_REGION, O_BAI, O_GENOME}},
         {"tag", "Add bismark XM tag to BAM file",
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
-          {"genome", 'g', "GENOME", "", nullptr, true, 's'}}},
+          {"genome", 'g', "GENOME", "", nullptr, true, 's'},
+          // not in the reference (its writer is bam::Format::Sam, tag.rs:406): the tagged records as a BGZF-compressed BAM made on the device
+          {"output-format", 'O', "OUTPUT_FORMAT", "(MI355X extension) Format of the output alignment file: sam or bam", "sam", false, 's'}}},
     };
     return c;
 }
@@ -139,12 +142,17 @@ std::string usage_line(const Cmd &c) {
 
 void print_cmd_help(FILE *f, const Cmd &c) {
     fprintf(f, "%s\n\n%s\n\nOptions:\n", c.about, usage_line(c).c_str());
+    const Opt *ext = nullptr;
     for (const Opt &o : c.opts) {
+        // `tag --help` on stdout is the reference's text to the byte (tests/test_genome_cli_args.py pins it): tag's one extension is
+        // listed on stderr instead, after the help
+        if (!strcmp(c.name, "tag") && !strcmp(o.long_name, "output-format")) { ext = &o; continue; }
         std::string left = o.short_name ? std::string("  -") + o.short_name + ", --" + o.long_name + " <" + o.value_name + ">"
                                         : std::string("      --") + o.long_name + " <" + o.value_name + ">";      // (a long-only option)
         fprintf(f, "%-34s %s%s%s%s\n", left.c_str(), o.help, o.def ? " [default: " : "", o.def ? o.def : "", o.def ? "]" : "");
     }
     fprintf(f, "  -h, --help                       Print help\n");
+    if (ext) { fflush(f); fprintf(stderr, "\nExtension:\n  -O, --output-format <OUTPUT_FORMAT> %s [default: %s]\n", ext->help, ext->def); }
 }
 
 [[noreturn]] void usage_error(const Cmd *c, const std::string &msg) {
@@ -1544,8 +1552,53 @@ int tag_window(void *user, const uint8_t *buf, const uint64_t *rec_off, uint64_t
     return 0;
 }
 
+// --output-format bam: the window's tagged records come back as finished BGZF blocks (mth_tag_records_bam: record stream,
+// block cuts by htslib's rule and DEFLATE on the device) and go to the file as they are
+int tag_window_bam(void *user, const uint8_t *buf, const uint64_t *rec_off, uint64_t n_rec) {
+    TagState *st = static_cast<TagState *>(user);
+    if (n_rec == 0) return 0;
+    if (st->paired < 0) {                          // is_paired_end: the file's first record
+        const uint64_t o = rec_off[0];
+        st->paired = (rec_off[1] - o >= 36) ? ((buf[o + 4 + 14] | (buf[o + 4 + 15] << 8)) & 1) : 0;
+    }
+    mth_tag_bam_out_t t{};
+    const int rc = mth_tag_records_bam(st->ctx, buf, rec_off[n_rec], rec_off, n_rec, MTH_MEM_HOST, st->paired, &t);
+    if (rc != MTH_OK) {
+        st->fail = std::string("metheor (MI355X path): ") + mth_strerror(rc) + (mth_last_error(st->ctx)[0] ? std::string(" -- ") + mth_last_error(st->ctx) : std::string());
+        return 1;
+    }
+    if (t.n_bytes && fwrite(t.bytes, 1, (size_t)t.n_bytes, st->out) != (size_t)t.n_bytes) { st->fail = "Error writing to output file."; return 1; }
+    return 0;
+}
+
+// n bytes as BGZF blocks of at most 0xff00 bytes each, compressed on the host (the BAM header: a few blocks at most)
+bool bgzf_write_host(FILE *out, const uint8_t *p, size_t n) {
+    std::vector<uint8_t> blk(18 + compressBound(0xff00) + 8);
+    for (size_t i = 0; i < n;) {
+        const size_t k = std::min<size_t>(n - i, 0xff00);
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        zs.next_in = const_cast<uint8_t *>(p + i); zs.avail_in = (uInt)k;
+        zs.next_out = blk.data() + 18; zs.avail_out = (uInt)(blk.size() - 26);
+        const int zr = deflate(&zs, Z_FINISH);
+        const size_t clen = blk.size() - 26 - zs.avail_out;
+        deflateEnd(&zs);
+        if (zr != Z_STREAM_END || 18 + clen + 8 > 65536) return false;
+        const uint8_t hdr[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
+        memcpy(blk.data(), hdr, 16);
+        const uint32_t bsize = (uint32_t)(clen + 25), crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), p + i, (uInt)k), isize = (uint32_t)k;
+        blk[16] = (uint8_t)bsize; blk[17] = (uint8_t)(bsize >> 8);
+        for (int b = 0; b < 4; ++b) { blk[18 + clen + b] = (uint8_t)(crc >> (8 * b)); blk[22 + clen + b] = (uint8_t)(isize >> (8 * b)); }
+        if (fwrite(blk.data(), 1, 26 + clen, out) != 26 + clen) return false;
+        i += k;
+    }
+    return true;
+}
+
 int run_tag(const Args &a) {
     const std::string input = a.s.at("input"), output = a.s.at("output"), genome = a.s.at("genome");
+    const bool as_bam = a.has("output-format") && a.s.at("output-format") == "bam";
     CtxFuture cf;
     cf.start();
     mth_host_t *h = nullptr;
@@ -1567,7 +1620,27 @@ int run_tag(const Args &a) {
         const char *t = mth_host_header_text(h, &n);
         std::string text(t, strnlen(t, (size_t)n));
         while (!text.empty() && text.back() == '\n') text.pop_back();
-        if (!text.empty()) { text += '\n'; fwrite(text.data(), 1, text.size(), out); }
+        if (!text.empty()) text += '\n';
+        if (!as_bam) {
+            if (!text.empty()) fwrite(text.data(), 1, text.size(), out);
+        } else {
+            // the BAM header in BGZF blocks of its own: magic, l_text + the same text, n_ref + the names and lengths
+            std::vector<uint8_t> hb;
+            auto put32 = [&](uint32_t x) { for (int i = 0; i < 4; ++i) hb.push_back((uint8_t)(x >> (8 * i))); };
+            hb.insert(hb.end(), {'B', 'A', 'M', 1});
+            put32((uint32_t)text.size());
+            hb.insert(hb.end(), text.begin(), text.end());
+            const int n_ref = mth_host_n_refs(h);
+            put32((uint32_t)n_ref);
+            for (int t2 = 0; t2 < n_ref; ++t2) {
+                const char *name = mth_host_ref_name(h, t2);
+                const size_t ln = strlen(name) + 1;
+                put32((uint32_t)ln);
+                hb.insert(hb.end(), name, name + ln);
+                put32((uint32_t)mth_host_ref_len(h, t2));
+            }
+            if (!bgzf_write_host(out, hb.data(), hb.size())) { cf.wait(); fflush(out); die("Error writing to output file."); }
+        }
     }
     mth_fasta_t *fa = genome_open(genome, [&] { cf.wait(); fflush(out); });
     printf("Parsing reference genome...\n");
@@ -1583,10 +1656,28 @@ int run_tag(const Args &a) {
     fflush(stdout);
     TagState st;
     st.ctx = ctx; st.h = h; st.out = out;
-    {
+    if (!as_bam) {
         Phase ph("records -> XM -> SAM");
         const int rc = mth_host_decode_stream(h, tag_window, &st);
         if (rc != 0) { fflush(out); die(!st.fail.empty() ? st.fail : std::string("Error reading BAM record. ") + mth_host_last_error(h)); }
+    } else {
+        const bool timing = getenv("METHEOR_TIMING") != nullptr;
+        if (timing) { mth_timing_reset(ctx); mth_timing_enable(ctx, 1); }
+        {
+            Phase ph("records -> XM -> BAM");
+            const int rc = mth_host_decode_stream(h, tag_window_bam, &st);
+            if (rc != 0) { fflush(out); die(!st.fail.empty() ? st.fail : std::string("Error reading BAM record. ") + mth_host_last_error(h)); }
+        }
+        if (timing) {
+            for (const char *k : {"k_tag_assemble", "k_crc32", "k_deflate", "k_bgzf_compact", "bgzf_d2h"}) {
+                double ms = 0;
+                uint64_t n = 0;
+                if (mth_timing_get(ctx, k, &ms, &n) == MTH_OK && n) fprintf(stderr, "[metheor timing]     tag/%-14s %.3f ms in %llu launches\n", k, ms * (double)n, (unsigned long long)n);
+            }
+            mth_timing_enable(ctx, 0);
+        }
+        static const uint8_t eof_block[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (fwrite(eof_block, 1, sizeof eof_block, out) != sizeof eof_block) die("Error writing to output file.");
     }
     if (fclose(out) != 0) die("Error writing to output file.");
     mth_host_fasta_close(fa);
@@ -1621,6 +1712,8 @@ int main(int argc, char **argv) {
         return -1;
     };
     if (sub == "tag") {
+        if (a.has("output-format") && a.s.at("output-format") != "sam" && a.s.at("output-format") != "bam")
+            usage_error(cmd, "invalid value '" + a.s.at("output-format") + "' for '--output-format <OUTPUT_FORMAT>'\n  [possible values: sam, bam]");
         if (const char *dev = getenv("METHEOR_DEVICE")) g_shard.device = atoi(dev);
         return run_tag(a);
     }

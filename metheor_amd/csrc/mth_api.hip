@@ -14,7 +14,7 @@ static const char *kKernelNames[K_NUM] = {"k_build_index", "k_pdr_lpmd_tile", "k
                                           "k_mhl_walk", "k_mhl_walk_big", "k_mhl_emit", "k_pdr_walk",
                                           "k_fdrp_walk", "k_fdrp_emit", "k_pairs", "k_pairs_tile", "k_decode", "k_inflate", "k_crc32", "k_mhl_tile", "k_pdr_lpmd_wide",
                                           "k_fdrp_tile", "k_fdrp_chain", "k_fdrp_walk4", "k_fdrp_wtile", "k_mhl_rowcheck", "k_decode_genome",
-                                          "k_straddle_guess", "k_straddle_walk", "k_straddle_repair", "k_fasta_pack"};
+                                          "k_straddle_guess", "k_straddle_walk", "k_straddle_repair", "k_fasta_pack", "k_deflate", "k_tag_assemble", "k_bgzf_compact", "bgzf_d2h"};
 
 __global__ void k_lpmd_add2(DevState *st, long long n_read, long long n_valid) { st->lpmd[2] += n_read; st->lpmd[3] += n_valid; }
 
@@ -341,7 +341,7 @@ void mth_ctx_destroy(mth_ctx_t *ctx) {
                       &ctx->st_rel, &ctx->idx, &ctx->tile_cnt, &ctx->tile_bucket, &ctx->scratch, &ctx->dec_raw, &ctx->dec_recoff, &ctx->dec_tid, &ctx->dec_start, &ctx->dec_end,
                       &ctx->dec_mapq, &ctx->dec_fwd, &ctx->dec_n, &ctx->dec_off, &ctx->dec_pos, &ctx->dec_rel, &ctx->dec_blk, &ctx->dec_off32, &ctx->dec_runs, &ctx->dec_xm, &ctx->dec_filter,
                       &ctx->inf_file, &ctx->inf_file2, &ctx->inf_tab, &ctx->inf_raw, &ctx->inf_cnt, &ctx->inf_base, &ctx->inf_recoff, &ctx->crc_mat, &ctx->inf_links, &ctx->inf_carry,
-                      &ctx->tag_genome, &ctx->tag_goff, &ctx->fa_genome, &ctx->fa_tab, &ctx->tag_ncol, &ctx->tag_coloff, &ctx->tag_xmlen, &ctx->tag_cols, &ctx->tag_xm,
+                      &ctx->tag_genome, &ctx->tag_goff, &ctx->fa_genome, &ctx->fa_tab, &ctx->tag_ncol, &ctx->tag_coloff, &ctx->tag_xmlen, &ctx->tag_cols, &ctx->tag_xm, &ctx->tag_sz, &ctx->tag_ooff, &ctx->tag_stream, &ctx->def_src, &ctx->def_tab, &ctx->def_tok, &ctx->def_slot, &ctx->def_boff, &ctx->def_out,
                       &ctx->batch_cnt, &ctx->out_pos, &ctx->out_pdr, &ctx->out_nc, &ctx->out_nd, &ctx->q_keys,
                       &ctx->q_hist, &ctx->q_blk, &ctx->q_batch_rows, &ctx->q_wpos, &ctx->q_wpat, &ctx->q_wk0, &ctx->q_wk1, &ctx->q_pos, &ctx->q_cnt, &ctx->q_me, &ctx->q_pm, &ctx->q_depth,
                       &ctx->s_pos, &ctx->s_pdr, &ctx->s_nc, &ctx->s_nd, &ctx->s_batch_cnt, &ctx->w_val, &ctx->w_cov, &ctx->w_aux, &ctx->w_flags,

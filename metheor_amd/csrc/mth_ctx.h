@@ -185,6 +185,14 @@ struct mth_ctx {
     std::vector<uint64_t> tag_h_off;
     std::vector<uint32_t> tag_h_len;
     std::vector<uint8_t> tag_h_xm;
+    // `tag -O bam` (mth_tag.hip: the tagged record stream; mth_deflate.hip: its BGZF blocks): per-record tagged sizes and output
+    // offsets, the stream, and the deflate step's block table, token scratch, per-block slots and the compacted blocks
+    mth::DevBuf tag_sz, tag_ooff, tag_stream;
+    std::vector<uint32_t> tag_h_sz;
+    std::vector<uint64_t> tag_h_cut;
+    mth::DevBuf def_src, def_tab, def_tok, def_slot, def_boff, def_out;
+    std::vector<uint8_t> def_h_out;
+    std::vector<uint64_t> def_h_boff;
     // contig groups (include/metheor_hip.h, "contig groups"): handle -2 - k is groups[k]
     struct ContigGroup { std::vector<int32_t> tids; std::vector<int64_t> voff; mth::DevBuf d_tab; };   // d_tab: n voff (int32) then n tids
     std::vector<ContigGroup> groups;
@@ -302,6 +310,11 @@ int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint6
 int genome_commit(mth_ctx *ctx, int32_t n_refs, const std::vector<uint64_t> &off, const int64_t *ref_len);
 // mth_tag.hip: the XM strings of n device-resident records into ctx->tag_xm (offsets tag_coloff, lengths tag_xmlen); *total = bytes
 int tag_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint32_t n, int is_paired_end, unsigned long long *total);
+// mth_inflate.hip: CRC-32 of device-resident blocks (k_crc32) into d_out
+int crc32_blocks(mth_ctx *ctx, const uint8_t *raw, const uint64_t *d_uoff, const uint32_t *d_isize, uint32_t n_blocks, uint32_t *d_out);
+// mth_deflate.hip: n_blocks BGZF blocks of the device-resident bytes d_src cut at h_cut (n_blocks + 1 ascending offsets, blocks of
+// at most 0xff00 bytes) into ctx->def_h_out, block b at ctx->def_h_boff[b]; synchronises
+int deflate_core(mth_ctx *ctx, const uint8_t *d_src, const uint64_t *h_cut, uint64_t n_blocks);
 struct DecArgs;
 // mth_decode_genome.hip: the two passes of the decode with the calls derived from the genome (k_decode_genome); `a` as decode_core
 // fills it for k_decode<false>.  count: ncpg / tid / start / end / mapq / fwd; fill: cpg_pos / cpg_rel at a.cpg_off

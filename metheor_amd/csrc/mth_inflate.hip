@@ -397,6 +397,7 @@ struct CrcArgs {
     const uint32_t *mat;            // [17][32]: operator for 2^k zero bytes, k = 0..16
     uint32_t n_blocks;
     uint32_t *err;
+    uint32_t *out;                  // non-null: the CRCs are stored here and nothing is compared (the deflate side, mth_deflate.hip)
 };
 __device__ __forceinline__ uint32_t gf2_apply(const uint32_t *__restrict__ m, uint32_t v) {
     uint32_t s = 0;
@@ -459,6 +460,7 @@ __global__ __launch_bounds__(64) void k_crc32(const CrcArgs a) {
         uint32_t init = 0xffffffffu;                              // shift_L(0xffffffff): binary decomposition of L
         for (int k = 0; k < 17; ++k) if ((L >> k) & 1u) init = gf2_apply(smat + k * 32, init);
         const uint32_t crc = ~(c ^ init);
+        if (a.out) { a.out[blk] = crc; return; }
         uint32_t want;
         __builtin_memcpy(&want, a.file + a.coff[blk] + a.csize[blk], 4);
         if (crc != want) atomicOr(a.err, (uint32_t)ERRB_CRC);
@@ -690,6 +692,30 @@ static void crc_zero_operators(uint32_t (*mat)[32]) {
 // no gain at 4, slower at 8 -- profiles/r02_e2e.md.)
 namespace mth {
 
+// the zero-byte operators of k_crc32 into the context, once
+static int crc_operators(mth_ctx *ctx) {
+    if (ctx->crc_mat.p) return MTH_OK;
+    hipStream_t s = ctx->stream;
+    uint32_t mat[17][32];
+    crc_zero_operators(mat);
+    MTH_HIP(ctx, ctx->crc_mat.reserve(sizeof mat, s));
+    MTH_HIP(ctx, hipMemcpyAsync(ctx->crc_mat.p, mat, sizeof mat, hipMemcpyHostToDevice, s));
+    MTH_HIP(ctx, hipStreamSynchronize(s));            // mat is a local
+    return MTH_OK;
+}
+
+// CRC-32 of n_blocks device-resident blocks (block b: isize[b] <= 65536 bytes at raw + uoff[b]) into out[b]: k_crc32 without a
+// trailer to compare with
+int crc32_blocks(mth_ctx *ctx, const uint8_t *raw, const uint64_t *d_uoff, const uint32_t *d_isize, uint32_t n_blocks, uint32_t *d_out) {
+    { const int rc = crc_operators(ctx); if (rc) return rc; }
+    CrcArgs ca{};
+    ca.raw = raw; ca.uoff = d_uoff; ca.isize = d_isize; ca.mat = ctx->crc_mat.as<uint32_t>(); ca.n_blocks = n_blocks;
+    ca.err = &ctx->d_state->err; ca.out = d_out;
+    LaunchTimer lt(ctx, K_CRC);
+    hipLaunchKernelGGL(k_crc32, dim3(n_blocks), dim3(64), 0, ctx->stream, ca);
+    return MTH_OK;
+}
+
 int stage_take(mth_ctx *ctx, const void *file, uint64_t n_bytes, bool &staged) {
     hipStream_t s = ctx->stream;
     // the helper thread of the previous call (copying THIS call's bytes, if they were announced) has to be done first
@@ -770,13 +796,7 @@ int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, const uint6
         MTH_HIP(ctx, hipMemsetAsync(static_cast<uint8_t *>(ctx->inf_file.p) + n_bytes, 0, INF_FILE_PAD, s));
     }
     // (before the inflate is launched: allocating it afterwards synchronised with the inflate and delayed the first CRC launch by ~7 ms)
-    if (!ctx->crc_mat.p) {
-        uint32_t mat[17][32];
-        crc_zero_operators(mat);
-        MTH_HIP(ctx, ctx->crc_mat.reserve(sizeof mat, s));
-        MTH_HIP(ctx, hipMemcpyAsync(ctx->crc_mat.p, mat, sizeof mat, hipMemcpyHostToDevice, s));
-        MTH_HIP(ctx, hipStreamSynchronize(s));            // mat is a local
-    }
+    { const int rc = crc_operators(ctx); if (rc) return rc; }
     { const int rc = stage_start_next(ctx); if (rc) return rc; }
     uint8_t *tab = static_cast<uint8_t *>(ctx->inf_tab.p);
     uint64_t *d_coff = reinterpret_cast<uint64_t *>(tab);
