@@ -566,6 +566,48 @@ typedef struct {
 } mth_tag_bam_out_t;
 int  mth_tag_records_bam(mth_ctx_t *ctx, const void *raw, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
                          int is_paired_end, mth_tag_bam_out_t *out);
+/* ---- the BAM index (.bai, SAM spec 5.2) of a record stream, built on the device (mth_bai.hip) -------------------------------
+ * What is indexed, for every record with refID >= 0 in file order: beg = pos, end = pos + max(1, reference length of the CIGAR:
+ * M D N = X), bin = reg2bin(beg, end), and the virtual offsets (file offset of the BGZF block << 16 | offset inside it) of its first
+ * byte and of the byte after its last -- a record that ends exactly at a block's end keeps that block, as bgzf_tell does; a record
+ * longer than a block begins in its first block.  Chunks: a run of consecutive records of one (refID, bin) is one chunk, across
+ * calls too.  Linear index: per 16-kbp window the smallest first-byte offset of the records that touch it; a window nothing touches
+ * takes the entry before it, leading ones are 0.  Per reference with records the four words of samtools' metadata pseudo-bin 37450.
+ *   mth_bai_begin        starts an index (any earlier one is dropped): ref_len[t] = the header's LN (the linear table is sized from
+ *                        it), file_off = file offset of the next block mth_tag_records_bam will make.  From here to mth_bai_finish
+ *                        every successful mth_tag_records_bam call also indexes its window from the buffers it has on the device and
+ *                        advances the offset by the window's compressed bytes.
+ *   mth_bai_add_records  the same step with everything given: records as mth_decode_records takes them (mem says where raw / rec_off
+ *                        live), n_blocks + 1 ascending cut offsets into the stream and every block's file offset, both in HOST memory
+ *                        (cut_off[0] = 0, the records must end at or before cut_off[n_blocks]).  n_rec = 0 with an empty block
+ *                        (cut_off = {0, 0}): that block follows the stream -- the EOF block; the record that ended where the blocks
+ *                        so far end is given its offset as its end, which is what bgzf_tell reports there.
+ *   mth_bai_finish       the tables (host memory owned by the context, valid until the next mth_bai_* call) and the end of indexing.
+ * Refused, with the record's ordinal (counted from 0 over all calls) in mth_last_error; the lowest one is reported, by the call
+ * that met it, by every later mth_bai_add_records and by mth_bai_finish, which then returns no tables -- a new mth_bai_begin
+ * starts afresh: MTH_ERR_UNSORTED for a stream that is not coordinate-sorted (refID descending, pos descending inside a
+ * reference, a placed record after one with refID < 0; equal positions are fine); MTH_ERR_RANGE for a record that ends beyond
+ * 2^29 (the format's limit: a .csi would be needed), lies at pos < 0 or ends beyond its reference's length, or names refID >=
+ * n_refs; MTH_ERR_FORMAT for a malformed record.  mth_tag_records_bam itself does not fail on these: the BAM stays complete. */
+typedef struct {
+    int32_t         n_refs;
+    uint64_t        n_records;     /* records seen, with and without a reference */
+    uint64_t        n_chunks;
+    const uint64_t *chunk_beg, *chunk_end;   /* sorted by (refID, bin), file order inside a bin */
+    uint64_t        n_bins;        /* bins that hold chunks, over all references, ascending (refID, bin) */
+    const int32_t  *bin_ref;
+    const uint32_t *bin_id, *bin_n_chunks;
+    const uint32_t *ref_n_bins;    /* n_refs */
+    const uint32_t *ref_n_intv;    /* n_refs: highest window touched + 1 */
+    const uint64_t *lin_off;       /* n_refs + 1: reference t's entries are lin[lin_off[t] .. lin_off[t] + ref_n_intv[t]) */
+    const uint64_t *lin;
+    const uint64_t *meta;          /* 4 per reference with records: first offset, last end, records with flag 0x4 clear / set */
+    uint64_t        n_no_coor;     /* records with refID < 0 */
+} mth_bai_out_t;
+int  mth_bai_begin(mth_ctx_t *ctx, int32_t n_refs, const int64_t *ref_len, uint64_t file_off);
+int  mth_bai_add_records(mth_ctx_t *ctx, const void *raw, const uint64_t *rec_off, uint64_t n_rec, int mem, const uint64_t *cut_off,
+                         const uint64_t *block_coff, uint64_t n_blocks);
+int  mth_bai_finish(mth_ctx_t *ctx, mth_bai_out_t *out);
 /* mth_tag_set_genome with the FASTA read on the device: the same genome (bytes, offsets, header lengths) straight from the
  * file's text, plain or bgzip-compressed -- what faidx_fetch_seq(name, 0, LN) returns for every contig, with no host pass over
  * the bases.

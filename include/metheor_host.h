@@ -190,6 +190,24 @@ int  mth_host_plan_region(mth_host_t *h, const char *bai_path, int32_t tid, int3
  * that starts behind the index's end offset (MTH_STRADDLE_DROP_TAIL). */
 int  mth_host_plan_region_at_record(mth_host_t *h, const char *bai_path, int32_t tid, int32_t beg, int32_t end, int64_t halo_bp,
                                     mth_host_shard_t *out);
+/* The writer beside that reader: the tables mth_bai_finish (metheor_hip.h) returns, framed as a .bai file -- "BAI\1", n_ref; per
+ * reference its bins in ascending bin number, each with its chunks in file order, then samtools' metadata pseudo-bin 37450 (two
+ * "chunks": the four words of meta) where the reference has records; n_intv and the linear entries; n_no_coor at the end.  The
+ * arrays are mth_bai_out_t's, field by field.  Written to a temporary name in the same directory and renamed, so `path` is either
+ * the whole index or not touched.  MTH_HOST_ERR_INVALID for tables that do not add up, MTH_HOST_ERR_OPEN when the file cannot be
+ * written (err, optional, gets the text). */
+typedef struct {
+    int32_t         n_refs;
+    uint64_t        n_chunks;
+    const uint64_t *chunk_beg, *chunk_end;
+    uint64_t        n_bins;
+    const int32_t  *bin_ref;
+    const uint32_t *bin_id, *bin_n_chunks;
+    const uint32_t *ref_n_bins, *ref_n_intv;
+    const uint64_t *lin_off, *lin, *meta;
+    uint64_t        n_no_coor;
+} mth_host_bai_tables_t;
+int  mth_host_bai_write(const char *path, const mth_host_bai_tables_t *t, char *err, int err_len);
 int64_t mth_host_n_reads(const mth_host_t *h);
 int64_t mth_host_n_cpgs(const mth_host_t *h);
 const int32_t  *mth_host_read_tid(const mth_host_t *h);

@@ -16,7 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -119,6 +119,13 @@ class mth_tag_bam_out_t(C.Structure):
                 ("bytes", C.c_void_p), ("block_off", C.c_void_p)]
 
 
+class mth_bai_out_t(C.Structure):
+    _fields_ = [("n_refs", C.c_int32), ("n_records", C.c_uint64), ("n_chunks", C.c_uint64), ("chunk_beg", C.c_void_p), ("chunk_end", C.c_void_p),
+                ("n_bins", C.c_uint64), ("bin_ref", C.c_void_p), ("bin_id", C.c_void_p), ("bin_n_chunks", C.c_void_p),
+                ("ref_n_bins", C.c_void_p), ("ref_n_intv", C.c_void_p), ("lin_off", C.c_void_p), ("lin", C.c_void_p),
+                ("meta", C.c_void_p), ("n_no_coor", C.c_uint64)]
+
+
 BGZF_MAX_BLOCK = 0xff00
 
 
@@ -199,6 +206,9 @@ def lib():
         L.mth_tag_genome_fetch.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp]
         L.mth_tag_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_tag_out_t)]
         L.mth_tag_records_bam.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_tag_bam_out_t)]
+        L.mth_bai_begin.argtypes = [vp, C.c_int32, vp, C.c_uint64]
+        L.mth_bai_add_records.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint64]
+        L.mth_bai_finish.argtypes = [vp, C.POINTER(mth_bai_out_t)]
         L.mth_decode_set_genome.argtypes = [vp, C.c_int, C.c_int]
         L.mth_decoded_fetch.argtypes = [vp] * 9
         L.mth_decoded_contigs.argtypes = [vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -664,6 +674,39 @@ class Engine:
         self._check(self.L.mth_tag_records_bam(self.h, rb.ctypes.data if len(rb) else None, len(rb), off.ctypes.data, max(n, 0), 0,
                                                int(bool(is_paired_end)), C.byref(t)))
         return (C.string_at(t.bytes, t.n_bytes) if t.n_bytes else b""), int(t.stream_bytes), int(t.n_blocks)
+
+    def bai_begin(self, ref_len, file_off=0):
+        """mth_bai_begin: start a .bai index over references of these lengths; file_off: where the next block tag_records_bam makes
+        will lie in the file (every tag_records_bam call up to bai_finish indexes its window)"""
+        ln = np.ascontiguousarray(ref_len, np.int64)
+        self._check(self.L.mth_bai_begin(self.h, len(ln), ln.ctypes.data if len(ln) else None, int(file_off)))
+
+    def bai_add_records(self, raw, rec_off, cuts, block_coff):
+        """mth_bai_add_records: records (bytes + uint64[n_rec + 1] offsets, host) cut into blocks at the stream offsets `cuts`
+        (n_blocks + 1), block b at file offset block_coff[b]"""
+        rb = np.frombuffer(raw, np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else np.ascontiguousarray(raw, np.uint8)
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        cut = np.ascontiguousarray(cuts, np.uint64); coff = np.ascontiguousarray(block_coff, np.uint64)
+        assert len(cut) == len(coff) + 1
+        n = max(len(off) - 1, 0)
+        self._check(self.L.mth_bai_add_records(self.h, rb.ctypes.data if rb.size else None, off.ctypes.data if n else None, n, MTH_MEM_HOST,
+                                               cut.ctypes.data, coff.ctypes.data if len(coff) else None, len(coff)))
+
+    def bai_finish(self):
+        """mth_bai_finish -> dict: n_refs, n_records, n_no_coor and the tables as numpy arrays (copies) -- chunk_beg / chunk_end
+        (sorted by (refID, bin)), bin_ref / bin_id / bin_n_chunks, ref_n_bins, ref_n_intv, lin_off, lin, meta (n_refs x 4)"""
+        t = mth_bai_out_t()
+        self._check(self.L.mth_bai_finish(self.h, C.byref(t)))
+        def arr(p, ct, dt, k):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(k,)).astype(dt, copy=True) if k and p else np.zeros(0, dt)
+        nr, nc, nb = int(t.n_refs), int(t.n_chunks), int(t.n_bins)
+        lin_off = arr(t.lin_off, C.c_uint64, np.uint64, nr + 1)
+        return dict(n_refs=nr, n_records=int(t.n_records), n_no_coor=int(t.n_no_coor),
+                    chunk_beg=arr(t.chunk_beg, C.c_uint64, np.uint64, nc), chunk_end=arr(t.chunk_end, C.c_uint64, np.uint64, nc),
+                    bin_ref=arr(t.bin_ref, C.c_int32, np.int32, nb), bin_id=arr(t.bin_id, C.c_uint32, np.uint32, nb),
+                    bin_n_chunks=arr(t.bin_n_chunks, C.c_uint32, np.uint32, nb), ref_n_bins=arr(t.ref_n_bins, C.c_uint32, np.uint32, nr),
+                    ref_n_intv=arr(t.ref_n_intv, C.c_uint32, np.uint32, nr), lin_off=lin_off if nr else np.zeros(1, np.uint64),
+                    lin=arr(t.lin, C.c_uint64, np.uint64, int(lin_off[-1]) if nr else 0), meta=arr(t.meta, C.c_uint64, np.uint64, nr * 4).reshape(nr, 4))
 
     def decode_set_genome(self, enabled, is_paired_end=False):
         """derive the calls of the following decode_records / bgzf_decode calls from the genome of tag_set_genome instead of

@@ -3,7 +3,10 @@
 // opens them; here `metheor <measure> --region chr:beg-end` asks the index which BGZF blocks can hold records that
 // overlap the region (plus the halo the measures need on its left) and only those blocks go to the GPU.
 // The answer has the shape of a shard plan (mth_host_shard_t): blocks to load + the owned (tid, pos) interval.
+#include <unistd.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -81,3 +84,52 @@ bool BaiIndex::query(int32_t tid, int64_t beg, int64_t end, uint64_t &lo, uint64
 }
 
 }  // namespace mthh
+
+// ---- the writer: mth_bai_finish's tables as a .bai file --------------------------------------------------------------------
+extern "C" int mth_host_bai_write(const char *path, const mth_host_bai_tables_t *t, char *err, int err_len) {
+    auto say = [&](int rc, const std::string &m) { if (err && err_len > 0) snprintf(err, (size_t)err_len, "%s", m.c_str()); return rc; };
+    if (!path || !t || t->n_refs < 0) return say(MTH_HOST_ERR_INVALID, "mth_host_bai_write: bad argument");
+    if ((t->n_chunks && (!t->chunk_beg || !t->chunk_end)) || (t->n_bins && (!t->bin_ref || !t->bin_id || !t->bin_n_chunks)) ||
+        (t->n_refs && (!t->ref_n_bins || !t->ref_n_intv || !t->lin_off || !t->meta)))
+        return say(MTH_HOST_ERR_INVALID, "mth_host_bai_write: a table is missing");
+    std::vector<uint8_t> out;
+    auto put = [&](const void *p, size_t n) { const uint8_t *b = static_cast<const uint8_t *>(p); out.insert(out.end(), b, b + n); };
+    auto put32 = [&](uint32_t v) { put(&v, 4); };
+    auto put64 = [&](uint64_t v) { put(&v, 8); };
+    put("BAI\1", 4);
+    put32((uint32_t)t->n_refs);
+    uint64_t bin = 0, chunk = 0;
+    for (int32_t r = 0; r < t->n_refs; ++r) {
+        const uint64_t *meta = t->meta + 4 * (size_t)r;
+        const bool has = meta[2] + meta[3] > 0;
+        const uint32_t nb = t->ref_n_bins[r];
+        if ((nb > 0) != has || bin + nb > t->n_bins) return say(MTH_HOST_ERR_INVALID, "mth_host_bai_write: the bin counts do not add up");
+        put32(nb + (has ? 1u : 0u));
+        for (uint32_t k = 0; k < nb; ++k, ++bin) {
+            const uint32_t nc = t->bin_n_chunks[bin];
+            if (t->bin_ref[bin] != r || t->bin_id[bin] >= 37450u || (k && t->bin_id[bin] <= t->bin_id[bin - 1]) || nc == 0 || nc > 0x7fffffffu || chunk + nc > t->n_chunks)
+                return say(MTH_HOST_ERR_INVALID, "mth_host_bai_write: the bins are not in ascending (reference, bin) order or their chunk counts do not add up");
+            put32(t->bin_id[bin]);
+            put32(nc);
+            for (uint32_t c = 0; c < nc; ++c, ++chunk) { put64(t->chunk_beg[chunk]); put64(t->chunk_end[chunk]); }
+        }
+        if (has) { put32(37450u); put32(2u); put(meta, 32); }
+        const uint32_t ni = t->ref_n_intv[r];
+        if (ni > 0x7fffffffu || (ni && !t->lin) || t->lin_off[r] + ni > t->lin_off[(size_t)r + 1]) return say(MTH_HOST_ERR_INVALID, "mth_host_bai_write: a linear index longer than its table");
+        put32(ni);
+        if (ni) put(t->lin + t->lin_off[r], (size_t)ni * 8);
+    }
+    if (bin != t->n_bins || chunk != t->n_chunks) return say(MTH_HOST_ERR_INVALID, "mth_host_bai_write: bins or chunks left over");
+    put64(t->n_no_coor);
+    // in one piece: a temporary name beside the target, then rename
+    const std::string tmp = std::string(path) + ".tmp." + std::to_string((long long)getpid());
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return say(MTH_HOST_ERR_OPEN, "Error opening BAM index to write: " + tmp + ": " + strerror(errno));
+    const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+    if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path) != 0) {
+        const std::string why = strerror(errno);
+        remove(tmp.c_str());
+        return say(MTH_HOST_ERR_OPEN, "Error writing BAM index " + std::string(path) + ": " + why);
+    }
+    return MTH_HOST_OK;
+}

@@ -38,7 +38,7 @@ struct Opt {
     const char *help;
     const char *def;          // nullptr: no default
     bool required;
-    char kind;                // 's' string, 'B' u8, 'U' u32, 'Z' usize, 'I' i32
+    char kind;                // 's' string, 'B' u8, 'U' u32, 'Z' usize, 'I' i32, 'F' a flag: takes no value
 };
 struct Cmd {
     const char *name;
@@ -122,7 +122,9 @@ const std::vector<Cmd> &commands() {
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
           {"genome", 'g', "GENOME", "", nullptr, true, 's'},
           // not in the reference (its writer is bam::Format::Sam, tag.rs:406): the tagged records as a BGZF-compressed BAM made on the device
-          {"output-format", 'O', "OUTPUT_FORMAT", "(MI355X extension) Format of the output alignment file: sam or bam", "sam", false, 's'}}},
+          {"output-format", 'O', "OUTPUT_FORMAT", "(MI355X extension) Format of the output alignment file: sam or bam", "sam", false, 's'},
+          // not in the reference either: the .bai of that BAM, built on the device beside the records (mth_bai.hip), as <OUTPUT>.bai
+          {"write-index", 0, "", "(MI355X extension) with -O bam, also write the BAM index <OUTPUT>.bai, built on the device", nullptr, false, 'F'}}},
     };
     return c;
 }
@@ -142,17 +144,19 @@ std::string usage_line(const Cmd &c) {
 
 void print_cmd_help(FILE *f, const Cmd &c) {
     fprintf(f, "%s\n\n%s\n\nOptions:\n", c.about, usage_line(c).c_str());
-    const Opt *ext = nullptr;
+    const Opt *ext = nullptr, *ext_flag = nullptr;
     for (const Opt &o : c.opts) {
-        // `tag --help` on stdout is the reference's text to the byte (tests/test_genome_cli_args.py pins it): tag's one extension is
+        // `tag --help` on stdout is the reference's text to the byte (tests/test_genome_cli_args.py pins it): tag's extensions are
         // listed on stderr instead, after the help
         if (!strcmp(c.name, "tag") && !strcmp(o.long_name, "output-format")) { ext = &o; continue; }
+        if (!strcmp(c.name, "tag") && !strcmp(o.long_name, "write-index")) { ext_flag = &o; continue; }
         std::string left = o.short_name ? std::string("  -") + o.short_name + ", --" + o.long_name + " <" + o.value_name + ">"
                                         : std::string("      --") + o.long_name + " <" + o.value_name + ">";      // (a long-only option)
         fprintf(f, "%-34s %s%s%s%s\n", left.c_str(), o.help, o.def ? " [default: " : "", o.def ? o.def : "", o.def ? "]" : "");
     }
     fprintf(f, "  -h, --help                       Print help\n");
     if (ext) { fflush(f); fprintf(stderr, "\nExtension:\n  -O, --output-format <OUTPUT_FORMAT> %s [default: %s]\n", ext->help, ext->def); }
+    if (ext_flag) fprintf(stderr, "      --%-30s %s\n", ext_flag->long_name, ext_flag->help);
 }
 
 [[noreturn]] void usage_error(const Cmd *c, const std::string &msg) {
@@ -218,6 +222,11 @@ Args parse_args(const Cmd &c, int argc, char **argv, int first) {
             if (o && tok.size() > 2) { val = tok.substr(tok[2] == '=' ? 3 : 2); have_val = true; }
         }
         if (!o) usage_error(&c, "unexpected argument '" + tok + "' found");
+        if (o->kind == 'F') {
+            if (have_val) usage_error(&c, "unexpected value '" + val + "' for '--" + o->long_name + "' found; no more were expected");
+            a.s[o->long_name] = "true";
+            continue;
+        }
         if (!have_val) {
             if (i + 1 >= argc) usage_error(&c, std::string("a value is required for '--") + o->long_name + " <" + o->value_name + ">' but none was supplied");
             val = argv[++i];
@@ -1599,6 +1608,8 @@ bool bgzf_write_host(FILE *out, const uint8_t *p, size_t n) {
 int run_tag(const Args &a) {
     const std::string input = a.s.at("input"), output = a.s.at("output"), genome = a.s.at("genome");
     const bool as_bam = a.has("output-format") && a.s.at("output-format") == "bam";
+    const bool write_index = as_bam && a.has("write-index");
+    const std::string index_path = output + ".bai";             // the first name mth_host_plan_region looks for
     CtxFuture cf;
     cf.start();
     mth_host_t *h = nullptr;
@@ -1615,6 +1626,9 @@ int run_tag(const Args &a) {
     if (!out) { cf.wait(); die("Error opening alignment file to write: " + output + ": " + strerror(errno)); }
     static char obuf[1 << 20];
     setvbuf(out, obuf, _IOFBF, sizeof obuf);
+    // an index left over from another file of this name must not outlive it, whatever becomes of this run
+    if (write_index && remove(index_path.c_str()) != 0 && errno != ENOENT) { cf.wait(); die("Error removing the old BAM index: " + index_path + ": " + strerror(errno)); }
+    long header_bytes = 0;
     {   // the header text as it is, newline-terminated (Header::from_template strips and re-adds the final newline)
         uint64_t n = 0;
         const char *t = mth_host_header_text(h, &n);
@@ -1640,6 +1654,7 @@ int run_tag(const Args &a) {
                 put32((uint32_t)mth_host_ref_len(h, t2));
             }
             if (!bgzf_write_host(out, hb.data(), hb.size())) { cf.wait(); fflush(out); die("Error writing to output file."); }
+            header_bytes = ftell(out);                          // where the first block of records will lie
         }
     }
     mth_fasta_t *fa = genome_open(genome, [&] { cf.wait(); fflush(out); });
@@ -1663,23 +1678,52 @@ int run_tag(const Args &a) {
     } else {
         const bool timing = getenv("METHEOR_TIMING") != nullptr;
         if (timing) { mth_timing_reset(ctx); mth_timing_enable(ctx, 1); }
+        if (write_index) {
+            if (header_bytes < 0) { fflush(out); die("Error writing to output file."); }
+            const int n_ref = mth_host_n_refs(h);
+            std::vector<int64_t> ln((size_t)std::max(n_ref, 0));
+            for (int t2 = 0; t2 < n_ref; ++t2) ln[(size_t)t2] = mth_host_ref_len(h, t2);
+            if (mth_bai_begin(ctx, n_ref, ln.data(), (uint64_t)header_bytes) != MTH_OK) { fflush(out); die(std::string("metheor (MI355X path): ") + mth_last_error(ctx)); }
+        }
         {
             Phase ph("records -> XM -> BAM");
             const int rc = mth_host_decode_stream(h, tag_window_bam, &st);
             if (rc != 0) { fflush(out); die(!st.fail.empty() ? st.fail : std::string("Error reading BAM record. ") + mth_host_last_error(h)); }
         }
-        if (timing) {
-            for (const char *k : {"k_tag_assemble", "k_crc32", "k_deflate", "k_bgzf_compact", "bgzf_d2h"}) {
+        auto print_timing = [&] {
+            if (!timing) return;
+            for (const char *k : {"k_tag_assemble", "k_crc32", "k_deflate", "k_bgzf_compact", "bgzf_d2h", "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill"}) {
                 double ms = 0;
                 uint64_t n = 0;
                 if (mth_timing_get(ctx, k, &ms, &n) == MTH_OK && n) fprintf(stderr, "[metheor timing]     tag/%-14s %.3f ms in %llu launches\n", k, ms * (double)n, (unsigned long long)n);
             }
             mth_timing_enable(ctx, 0);
-        }
+        };
+        if (!write_index) print_timing();
         static const uint8_t eof_block[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (fwrite(eof_block, 1, sizeof eof_block, out) != sizeof eof_block) die("Error writing to output file.");
+        const long eof_off = write_index ? ftell(out) : 0;
+        if (eof_off < 0 || fwrite(eof_block, 1, sizeof eof_block, out) != sizeof eof_block) die("Error writing to output file.");
+        if (fclose(out) != 0) die("Error writing to output file.");
+        out = nullptr;
+        if (write_index) {
+            // the BAM is complete; the index follows in one piece, or not at all.  The EOF block is an empty block behind the last
+            // record: the library gives that record the block's offset as its end, as bgzf_tell reports it there
+            Phase ph("index -> .bai");
+            const uint64_t cut[2] = {0, 0}, coff[1] = {(uint64_t)eof_off};
+            mth_bai_out_t ix{};
+            int rc = mth_bai_add_records(ctx, nullptr, nullptr, 0, MTH_MEM_HOST, cut, coff, 1);
+            if (rc == MTH_OK) rc = mth_bai_finish(ctx, &ix);
+            print_timing();
+            if (rc != MTH_OK) die("metheor: " + output + " is complete, but no index is written: " + mth_last_error(ctx));
+            mth_host_bai_tables_t tb{};
+            tb.n_refs = ix.n_refs; tb.n_chunks = ix.n_chunks; tb.chunk_beg = ix.chunk_beg; tb.chunk_end = ix.chunk_end; tb.n_bins = ix.n_bins;
+            tb.bin_ref = ix.bin_ref; tb.bin_id = ix.bin_id; tb.bin_n_chunks = ix.bin_n_chunks; tb.ref_n_bins = ix.ref_n_bins; tb.ref_n_intv = ix.ref_n_intv;
+            tb.lin_off = ix.lin_off; tb.lin = ix.lin; tb.meta = ix.meta; tb.n_no_coor = ix.n_no_coor;
+            if (mth_host_bai_write(index_path.c_str(), &tb, err, sizeof err) != MTH_HOST_OK) die(err);
+            if (timing) fprintf(stderr, "[metheor timing]     tag/index: %llu chunks in %llu bins\n", (unsigned long long)ix.n_chunks, (unsigned long long)ix.n_bins);
+        }
     }
-    if (fclose(out) != 0) die("Error writing to output file.");
+    if (out && fclose(out) != 0) die("Error writing to output file.");
     mth_host_fasta_close(fa);
     return finish(ctx, h);
 }
@@ -1714,6 +1758,8 @@ int main(int argc, char **argv) {
     if (sub == "tag") {
         if (a.has("output-format") && a.s.at("output-format") != "sam" && a.s.at("output-format") != "bam")
             usage_error(cmd, "invalid value '" + a.s.at("output-format") + "' for '--output-format <OUTPUT_FORMAT>'\n  [possible values: sam, bam]");
+        if (a.has("write-index") && !(a.has("output-format") && a.s.at("output-format") == "bam"))
+            usage_error(cmd, "the argument '--write-index' cannot be used without '--output-format bam'");
         if (const char *dev = getenv("METHEOR_DEVICE")) g_shard.device = atoi(dev);
         return run_tag(a);
     }

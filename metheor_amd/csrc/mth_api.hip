@@ -14,7 +14,8 @@ static const char *kKernelNames[K_NUM] = {"k_build_index", "k_pdr_lpmd_tile", "k
                                           "k_mhl_walk", "k_mhl_walk_big", "k_mhl_emit", "k_pdr_walk",
                                           "k_fdrp_walk", "k_fdrp_emit", "k_pairs", "k_pairs_tile", "k_decode", "k_inflate", "k_crc32", "k_mhl_tile", "k_pdr_lpmd_wide",
                                           "k_fdrp_tile", "k_fdrp_chain", "k_fdrp_walk4", "k_fdrp_wtile", "k_mhl_rowcheck", "k_decode_genome",
-                                          "k_straddle_guess", "k_straddle_walk", "k_straddle_repair", "k_fasta_pack", "k_deflate", "k_tag_assemble", "k_bgzf_compact", "bgzf_d2h"};
+                                          "k_straddle_guess", "k_straddle_walk", "k_straddle_repair", "k_fasta_pack", "k_deflate", "k_tag_assemble", "k_bgzf_compact", "bgzf_d2h",
+                                          "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill"};
 
 __global__ void k_lpmd_add2(DevState *st, long long n_read, long long n_valid) { st->lpmd[2] += n_read; st->lpmd[3] += n_valid; }
 
@@ -352,6 +353,7 @@ void mth_ctx_destroy(mth_ctx_t *ctx) {
     for (TileRowTable *t : {&ctx->quartets, &ctx->pairs})
         for (DevBuf *b : {&t->state, &t->snap, &t->tflag, &t->tile_row0, &t->tile_rows}) b->release();
     for (auto &g : ctx->groups) g.d_tab.release();
+    bai_release(ctx);
     for (auto &t : ctx->timed) { (void)hipEventDestroy(t.beg); (void)hipEventDestroy(t.end); }
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->d_state) (void)hipFree(ctx->d_state);

@@ -105,6 +105,25 @@ struct Prepared {
     uint32_t nq = 0;
     DevState *st = nullptr;
 };
+
+// the .bai index under construction (mth_bai.hip): device tables, the run rows appended window by window, and the host copies
+// mth_bai_finish hands out
+struct BaiBuild {
+    bool on = false;                       // between mth_bai_begin and mth_bai_finish: mth_tag_records_bam indexes its windows
+    int err = 0;                           // the first error a window raised (kept until the next mth_bai_begin)
+    std::string err_msg;
+    int32_t n_refs = 0;
+    uint64_t file_off = 0;                 // file offset of the next block mth_tag_records_bam makes
+    uint64_t n_records = 0, n_rows = 0, row_cap = 0;
+    int par = 0;                           // generation of the device state's "record before" words the next window reads
+    DevBuf state, lin, tab, meta, n_intv;  // tab: n_refs + 1 linear-table offsets, then n_refs reference lengths
+    DevBuf key, vb, ve, flag, rank, cut;   // per record of the window in flight; cut: an explicit call's cuts + block offsets
+    DevBuf r_key, r_vb, r_ve;              // run rows, file order
+    DevBuf skey, idx, perm, tmp, cb, ce, bin_key, bin_start, bin_cnt, ref_nbin;     // mth_bai_finish
+    std::vector<uint64_t> h_lin_off, h_cb, h_ce, h_bin_key, h_lin, h_meta;
+    std::vector<uint32_t> h_bin_cnt, h_bin_id, h_ref_nbin, h_n_intv;
+    std::vector<int32_t> h_bin_ref;
+};
 }  // namespace mth
 
 struct mth_ctx {
@@ -193,6 +212,7 @@ struct mth_ctx {
     mth::DevBuf def_src, def_tab, def_tok, def_slot, def_boff, def_out;
     std::vector<uint8_t> def_h_out;
     std::vector<uint64_t> def_h_boff;
+    mth::BaiBuild bai;
     // contig groups (include/metheor_hip.h, "contig groups"): handle -2 - k is groups[k]
     struct ContigGroup { std::vector<int32_t> tids; std::vector<int64_t> voff; mth::DevBuf d_tab; };   // d_tab: n voff (int32) then n tids
     std::vector<ContigGroup> groups;
@@ -315,6 +335,12 @@ int crc32_blocks(mth_ctx *ctx, const uint8_t *raw, const uint64_t *d_uoff, const
 // mth_deflate.hip: n_blocks BGZF blocks of the device-resident bytes d_src cut at h_cut (n_blocks + 1 ascending offsets, blocks of
 // at most 0xff00 bytes) into ctx->def_h_out, block b at ctx->def_h_boff[b]; synchronises
 int deflate_core(mth_ctx *ctx, const uint8_t *d_src, const uint64_t *h_cut, uint64_t n_blocks);
+// mth_bai.hip: one window of the index under construction -- n records of the device-resident stream d_raw at d_off, cut at the
+// device-resident stream offsets d_cut (n_blocks + 1), block b at file offset coff_base + d_coff[b]; synchronises.  bai_release:
+// the index's device buffers (mth_ctx_destroy)
+int bai_window(mth_ctx *ctx, const uint8_t *d_raw, const unsigned long long *d_off, uint32_t n, const unsigned long long *d_cut,
+               const unsigned long long *d_coff, unsigned long long coff_base, uint32_t n_blocks);
+void bai_release(mth_ctx *ctx);
 struct DecArgs;
 // mth_decode_genome.hip: the two passes of the decode with the calls derived from the genome (k_decode_genome); `a` as decode_core
 // fills it for k_decode<false>.  count: ncpg / tid / start / end / mapq / fwd; fill: cpg_pos / cpg_rel at a.cpg_off

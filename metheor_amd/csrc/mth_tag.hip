@@ -253,6 +253,15 @@ int mth_tag_records_bam(mth_ctx_t *ctx, const void *raw, uint64_t n_bytes, const
     bgzf_record_cuts(ctx->tag_h_sz.data(), n, ctx->tag_h_cut);
     const uint64_t nb = ctx->tag_h_cut.size() - 1;
     if ((rc = deflate_core(ctx, ctx->tag_stream.as<uint8_t>(), ctx->tag_h_cut.data(), nb))) return rc;
+    if (ctx->bai.on) {
+        // mth_bai_begin: the window goes into the index from what is on the device -- the stream, its record offsets, the cuts at
+        // the head of the deflate table and the blocks' offsets.  What the index refuses (unsorted input, a record a .bai cannot
+        // address) does not fail the window: mth_bai_finish reports it
+        rc = bai_window(ctx, ctx->tag_stream.as<uint8_t>(), ctx->tag_ooff.as<unsigned long long>(), n, ctx->def_tab.as<unsigned long long>(),
+                        ctx->def_boff.as<unsigned long long>(), ctx->bai.file_off, (uint32_t)nb);
+        if (rc == MTH_ERR_HIP) return rc;
+        ctx->bai.file_off += ctx->def_h_out.size();
+    }
     out->n_records = n_rec; out->n_blocks = nb; out->stream_bytes = total;
     out->bytes = ctx->def_h_out.data(); out->n_bytes = ctx->def_h_out.size(); out->block_off = ctx->def_h_boff.data();
     return MTH_OK;

@@ -9,7 +9,7 @@ _LIB = None
 
 SYMBOLS = [
     "mth_host_open", "mth_host_close", "mth_host_last_error", "mth_host_notes", "mth_host_n_refs", "mth_host_ref_name",
-    "mth_host_ref_len", "mth_host_ref_tid", "mth_host_first_flag", "mth_host_set_xm_min_mapq", "mth_host_decode", "mth_host_decode_stream", "mth_host_bgzf_blocks", "mth_host_plan_shard", "mth_host_plan_straddle_run", "mth_host_plan_shard_straddle", "mth_host_plan_region", "mth_host_plan_region_at_record", "mth_host_cpg_set_keys", "mth_host_n_reads", "mth_host_n_cpgs",
+    "mth_host_ref_len", "mth_host_ref_tid", "mth_host_first_flag", "mth_host_set_xm_min_mapq", "mth_host_decode", "mth_host_decode_stream", "mth_host_bgzf_blocks", "mth_host_plan_shard", "mth_host_plan_straddle_run", "mth_host_plan_shard_straddle", "mth_host_plan_region", "mth_host_plan_region_at_record", "mth_host_bai_write", "mth_host_cpg_set_keys", "mth_host_n_reads", "mth_host_n_cpgs",
     "mth_host_read_tid", "mth_host_read_start", "mth_host_read_end", "mth_host_read_mapq",
     "mth_host_read_fwd", "mth_host_cpg_off", "mth_host_cpg_pos", "mth_host_cpg_rel", "mth_host_format_f32", "mth_host_write_synthetic_bam",
     "mth_host_write_synthetic_bam_multi", "mth_host_write_synthetic_bam_repeat", "mth_host_header_text", "mth_host_path", "mth_host_sam_format", "mth_host_fasta_open", "mth_host_fasta_close",
@@ -35,6 +35,13 @@ class FastaRow(C.Structure):   # mth_host_fasta_row_t (the layout of metheor_hip
 class _Shard(C.Structure):     # mth_host_shard_t
     _fields_ = [("block_beg", C.c_uint64), ("block_end", C.c_uint64), ("first_byte", C.c_uint64),
                 ("tid_beg", C.c_int32), ("pos_beg", C.c_int32), ("tid_end", C.c_int32), ("pos_end", C.c_int32)]
+
+
+class _BaiTables(C.Structure):  # mth_host_bai_tables_t
+    _fields_ = [("n_refs", C.c_int32), ("n_chunks", C.c_uint64), ("chunk_beg", C.c_void_p), ("chunk_end", C.c_void_p),
+                ("n_bins", C.c_uint64), ("bin_ref", C.c_void_p), ("bin_id", C.c_void_p), ("bin_n_chunks", C.c_void_p),
+                ("ref_n_bins", C.c_void_p), ("ref_n_intv", C.c_void_p), ("lin_off", C.c_void_p), ("lin", C.c_void_p),
+                ("meta", C.c_void_p), ("n_no_coor", C.c_uint64)]
 
 
 class _StraddleRun(C.Structure):     # mth_host_straddle_run_t
@@ -87,6 +94,7 @@ def lib():
         L.mth_host_plan_shard_straddle.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_int64, vp]
         L.mth_host_plan_region.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp]
         L.mth_host_plan_region_at_record.argtypes = L.mth_host_plan_region.argtypes
+        L.mth_host_bai_write.argtypes = [C.c_char_p, C.POINTER(_BaiTables), C.c_char_p, C.c_int]
         L.mth_host_format_f32.argtypes = [C.c_float, C.c_char_p]
         L.mth_host_write_synthetic_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int32] + [vp] * 6 + [C.c_uint64, C.c_int]
         L.mth_host_write_synthetic_bam_multi.argtypes = [C.c_char_p, C.c_int32, vp, vp, C.c_int64, C.c_int32] + [vp] * 7 + [C.c_uint64, C.c_int]
@@ -104,6 +112,21 @@ def lib():
         L.mth_host_fasta_layout.argtypes = [vp, C.c_char_p, C.c_int64, vp]
         _LIB = L
     return _LIB
+
+
+def bai_write(path, tables):
+    """mth_host_bai_write: the tables of capi.Engine.bai_finish (a dict of numpy arrays and counts) framed as the .bai file `path`"""
+    want = dict(chunk_beg=np.uint64, chunk_end=np.uint64, bin_ref=np.int32, bin_id=np.uint32, bin_n_chunks=np.uint32, ref_n_bins=np.uint32,
+                ref_n_intv=np.uint32, lin_off=np.uint64, lin=np.uint64, meta=np.uint64)
+    keep = {k: np.ascontiguousarray(tables[k], dt).ravel() for k, dt in want.items()}
+    t = _BaiTables()
+    t.n_refs, t.n_chunks, t.n_bins, t.n_no_coor = int(tables["n_refs"]), len(keep["chunk_beg"]), len(keep["bin_id"]), int(tables["n_no_coor"])
+    for k, a in keep.items():
+        setattr(t, k, a.ctypes.data if a.size else None)
+    err = C.create_string_buffer(1024)
+    rc = lib().mth_host_bai_write(os.fsencode(path), C.byref(t), err, len(err))
+    if rc != 0:
+        raise HostError(rc, err.value.decode(errors="replace"))
 
 
 def format_f32(v):
