@@ -142,6 +142,9 @@ const char *mth_last_error(const mth_ctx_t *ctx);
  * rust-htslib's reference_positions_full(), whose aligned-pairs iterator is believed to panic on Cigar::Pad (the crate is not part
  * of the reference tree and cannot be checked here); this engine treats P as "no query base, no reference base". */
 #define MTH_NOTE_CIGAR_PAD 1u
+/* MTH_NOTE_MODTAG_SKIPPED: under mth_decode_set_modtags, a record contributed no call because its MM / ML cannot be placed on
+ * SEQ: no SEQ, a hard clip in the CIGAR, or an MN field that differs from l_seq. */
+#define MTH_NOTE_MODTAG_SKIPPED 2u
 uint32_t mth_notes(const mth_ctx_t *ctx);
 /* forget all accumulated results (a new input file) */
 int  mth_reset(mth_ctx_t *ctx);
@@ -651,6 +654,35 @@ int  mth_tag_genome_fetch(mth_ctx_t *ctx, int32_t tid, int64_t beg, int64_t n, v
  * (mth_decode_genome.hip); METHEOR_GENOME_STAGED=1 in the environment selects the second form, k_tag_xm into HBM and k_decode
  * reading the strings from there. */
 int  mth_decode_set_genome(mth_ctx_t *ctx, int enabled, int is_paired_end);
+/* Take the calls from the SAM base-modification tags MM:Z / ML:B:C (with MN:i) instead of the records' XM:Z: applies to the
+ * following mth_decode_records / mth_bgzf_decode / mth_bgzf_decode_straddle calls.  threshold (an ML value, 0..=255; above:
+ * MTH_ERR_INVALID): a listed base with ML >= threshold is methylated.  Enabling it while mth_decode_set_genome is on, or the
+ * reverse, is MTH_ERR_STATE.
+ * The rule, an equivalence: a record decodes as the same record with (1) its flag replaced by flag & 0x10 -- the position rule
+ * of readutil.rs:332 then depends on the strand alone: a forward record's call lies at the aligned position of its query
+ * offset, a reverse record's one below, so both strands of a CpG land on the top-strand C, and read_fwd = !(flag & 0x10) --,
+ * (2) its XM:Z fields removed and (3) XM:Z:X appended, where X has l_seq characters, all '.' except:
+ *   - the chosen group is the first group of MM:Z (grammar: (base strand codes mode? (',' digits)* ';')*, base one of ACGTUN,
+ *     strand + or -, codes [a-z]+ or [0-9]+, mode . or ?, digits 1 to 9 of them) with base C, strand + and the letter m among
+ *     its codes; a group of k letter codes (a numeric code: k = 1) and n numbers owns n * k entries of ML, interleaved in code
+ *     order per position, the groups' entries in the groups' order;
+ *   - the fundamental bases are the Cs of the ORIGINAL read 5'->3' (SEQ for a forward record; the reverse complement of SEQ for
+ *     a reverse one, so query offset q = l_seq - 1 - j and an original C is a stored G); the first number d0 selects fundamental
+ *     base d0, each next number d the base d + 1 further on; the i-th listed base has probability ML[base of the group + i * k
+ *     + index of m], 255 when the record has no ML field;
+ *   - only a fundamental base in read CpG context (the original read's next base is G) gets a character: 'Z' listed with
+ *     probability >= threshold, 'z' listed below it or unlisted under mode '.' / no mode, '.' unlisted under mode '?'.
+ * Records that contribute nothing (all dots, MTH_NOTE_MODTAG_SKIPPED): l_seq = 0, an H operation in the CIGAR, an integer MN
+ * field that differs from l_seq -- checked before MM / ML are looked at.  A record without an MM field of type Z has all dots
+ * (its ML is not looked at); a record is never "without XM" in this mode and XM:Z fields are ignored.  The first MM:Z, the
+ * first ML and the first MN count; the spellings Mm / Ml count as absent.
+ * MTH_ERR_FORMAT ("modtags: ..."), whatever the record's mapq: aux fields that cannot be walked; with an MM:Z field, an ML field
+ * that is not B:C, MM outside the grammar, an ML count that differs from the sum of n * k over all groups, a list of the chosen
+ * group that selects a fundamental base the read does not have.  MTH_ERR_CAPACITY: l_seq > 65535 (cpg_rel is 16 bits).
+ * The kernels are k_mm_xm, which writes X into HBM, and k_decode reading it from there (mth_decode_mm.hip: the staged form,
+ * the default, measured the faster one); METHEOR_MM_STAGED=0 in the environment selects the direct form, k_decode_mm, which
+ * takes the calls in the decode's own two passes without any string.  There is no host form. */
+int  mth_decode_set_modtags(mth_ctx_t *ctx, int enabled, uint32_t threshold);
 
 /* ---- measurement hooks (bench.py's roofline leg) -------------------------------------- */
 /* when enabled, every kernel launch is bracketed by hipEvents on the launch stream */

@@ -16,7 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome", "mth_decode_set_modtags",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -210,6 +210,7 @@ def lib():
         L.mth_bai_add_records.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint64]
         L.mth_bai_finish.argtypes = [vp, C.POINTER(mth_bai_out_t)]
         L.mth_decode_set_genome.argtypes = [vp, C.c_int, C.c_int]
+        L.mth_decode_set_modtags.argtypes = [vp, C.c_int, C.c_uint32]
         L.mth_decoded_fetch.argtypes = [vp] * 9
         L.mth_decoded_contigs.argtypes = [vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.mth_decoded_sort.argtypes = [vp]
@@ -368,7 +369,8 @@ class Engine:
         return PreparedBatch(self, batch)
 
     def notes(self):
-        """non-fatal findings of the device decode so far (bit 0: a CIGAR P operation was decoded)"""
+        """non-fatal findings of the device decode so far (bit 0: a CIGAR P operation was decoded; bit 1: under
+        decode_set_modtags a record without SEQ, with a hard clip or with MN != l_seq contributed no call)"""
         return int(self.L.mth_notes(self.h))
 
     def sync(self):
@@ -712,6 +714,11 @@ class Engine:
         """derive the calls of the following decode_records / bgzf_decode calls from the genome of tag_set_genome instead of
         the records' XM:Z -- what `metheor tag` followed by the decode computes (mth_decode_set_genome)"""
         self._check(self.L.mth_decode_set_genome(self.h, int(bool(enabled)), int(bool(is_paired_end))))
+
+    def decode_set_modtags(self, enabled, threshold=128):
+        """take the calls of the following decode_records / bgzf_decode calls from the records' MM:Z / ML:B:C base-modification
+        tags instead of XM:Z; a listed C with ML >= threshold (0..255) is methylated (mth_decode_set_modtags)"""
+        self._check(self.L.mth_decode_set_modtags(self.h, int(bool(enabled)), int(threshold)))
 
     def decoded_fetch(self):
         d = self._decoded

@@ -54,6 +54,9 @@ const Opt O_GPUS = {"gpus", 'G', "GPUS", "(MI355X extension) Number of GPUs to s
 const Opt O_REGION = {"region", 'r', "REGION", "(MI355X extension) Only this region: chr or chr:beg-end (1-based, inclusive); needs the BAM index", nullptr, false, 's'};
 // not in the reference: the two commands `tag`, then the measure, as one
 const Opt O_GENOME = {"genome", 'g', "GENOME", "(MI355X extension) Reference FASTA: derive the methylation calls from it instead of XM:Z tags, as `metheor tag` would; XM:Z tags in the input are ignored", nullptr, false, 's'};
+// not in the reference: 5mC calls as current instruments write them, the SAM base-modification tags
+const Opt O_MMTAGS = {"mm-tags", 0, "", "(MI355X extension) Take the methylation calls from the MM:Z / ML:B:C base-modification tags (5mC, C+m, in read CpG context) instead of XM:Z tags; XM:Z tags in the input are ignored", nullptr, false, 'F'};
+const Opt O_MMTHR = {"mm-threshold", 0, "MM_THRESHOLD", "(MI355X extension) With the MM / ML tags as the source of calls: a listed C whose ML probability is at least this (0..=255) is methylated", "128", false, 'B'};
 const Opt O_BAI = {"bai", 'b', "BAI", "(MI355X extension) BAM index for --region [default: <input>.bai]", nullptr, false, 's'};
 
 // lib.rs:24-231
@@ -63,41 +66,41 @@ const std::vector<Cmd> &commands() {
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of PDR calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG stretches to consider", "10", false, 'U'},
           {"min-cpgs", 'p', "MIN_CPGS", "Minimum number of consecutive CpGs in a CpG stretch to consider", "4", false, 'Z'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"pm", "Compute epipolymorphism",
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of PM calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG quartets to consider", "10", false, 'U'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"me", "Compute methylation entropy",
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of PDR calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG quartets to consider", "10", false, 'U'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"fdrp", "Compute fraction of discordant read pairs (FDRP)",
          {{"input", 'i', "INPUT", "Path to input BAM file", nullptr, true, 's'},
           {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of FDRP calculation", nullptr, true, 's'},
           {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum number of reads mapped to a CpG in order to be considered", "10", false, 'Z'},
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
-          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
+          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"qfdrp", "Compute quantitative fraction of discordant read pairs (qFDRP)",
          {{"input", 'i', "INPUT", "Path to input BAM file", nullptr, true, 's'},
           {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of FDRP calculation", nullptr, true, 's'},
           {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum number of reads mapped to a CpG in order to be considered", "10", false, 'Z'},
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
-          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
+          {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"mhl", "Compute methylation haplotype load (MHL)",
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of MHL calculation", nullptr, true, 's'},
           {"min-depth", 'd', "MIN_DEPTH", "Minimum depth of CpG stretches to consider", "10", false, 'U'},
           {"min-cpgs", 'p', "MIN_CPGS", "Minimum number of consecutive CpGs in a CpG stretch to consider", "4", false, 'Z'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"lpmd", "Compute local pairwise methylation discordance (LPMD)",
          {{"input", 'i', "INPUT", "Path to input BAM file", nullptr, true, 's'},
           {"output", 'o', "OUTPUT", "Path to output table file summarizing the result of LPMD calculation", nullptr, true, 's'},
           {"pairs", 'p', "PAIRS", "(Optional) Concordance information for all CpG pairs", nullptr, false, 's'},
           {"min-distance", 'm', "MIN_DISTANCE", "Minimum distance between CpG pairs to consider", "2", false, 'I'},
           {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         // not in the reference: any subset of the seven measures from ONE decode of the input (the parameters are shared by every
         // measure that has them, under the single commands' names and defaults; --lpmd-pairs is lpmd's --pairs, whose -p is min-cpgs here)
         {"all", "(MI355X extension) Compute any of the seven measures from one decode of the input",
@@ -117,7 +120,7 @@ const std::vector<Cmd> &commands() {
           {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
           {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'},
-          O_CPG, O_REGION, O_BAI, O_GENOME}},
+          O_CPG, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"tag", "Add bismark XM tag to BAM file",
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
           {"genome", 'g', "GENOME", "", nullptr, true, 's'},
@@ -152,6 +155,7 @@ void print_cmd_help(FILE *f, const Cmd &c) {
         if (!strcmp(c.name, "tag") && !strcmp(o.long_name, "write-index")) { ext_flag = &o; continue; }
         std::string left = o.short_name ? std::string("  -") + o.short_name + ", --" + o.long_name + " <" + o.value_name + ">"
                                         : std::string("      --") + o.long_name + " <" + o.value_name + ">";      // (a long-only option)
+        if (o.kind == 'F') left = std::string("      --") + o.long_name;                                             // (a flag)
         fprintf(f, "%-34s %s%s%s%s\n", left.c_str(), o.help, o.def ? " [default: " : "", o.def ? o.def : "", o.def ? "]" : "");
     }
     fprintf(f, "  -h, --help                       Print help\n");
@@ -352,6 +356,12 @@ int finish(mth_ctx_t *ctx, mth_host_t *h) {
             fprintf(stderr, "metheor: note: the input holds CIGAR 'P' (padding) operations; they were taken as covering no query base and no "
                             "reference base\n");
     }
+    {   // --mm-tags: records whose MM / ML cannot be placed on SEQ gave no call
+        static std::atomic<bool> said{false};
+        if (ctx && (mth_notes(ctx) & MTH_NOTE_MODTAG_SKIPPED) && !said.exchange(true))
+            fprintf(stderr, "metheor: note: --mm-tags: the input holds records without SEQ, with hard clips or with an MN field that differs from "
+                            "the length of SEQ; they contributed no methylation call\n");
+    }
     if (g_shard.world > 1) return 0;      // a shard's thread: main() writes the files and leaves
     if (getenv("METHEOR_TEARDOWN")) {
         Phase ph("teardown");
@@ -506,6 +516,12 @@ void genome_read_once(mth_host_t *h, F on_fail) {
     genome_fetch(fa, h, g_genome, on_fail);
     mth_host_fasta_close(fa);
 }
+// --mm-tags: set by main(), put on every context (each --gpus shard's too) by load_on_device
+bool g_modtags = false;
+uint32_t g_mm_threshold = 128;
+const char *const kNoHostModtags =
+    "--mm-tags needs the device record decode: the full host decoder (METHEOR_HOST_DECODE=1, or input it has to take: records without a "
+    "contig or an aligned base, contigs not grouped) has no MM / ML form";
 const char *const kNoHostGenome =
     "--genome needs the device record decode: the full host decoder (METHEOR_HOST_DECODE=1, or input it has to take: records without a "
     "contig or an aligned base, contigs not grouped) has no genome form -- run `metheor tag` first and give the measure its output";
@@ -513,6 +529,7 @@ const char *const kNoHostGenome =
 // a failed decode call as the reference's panic
 [[noreturn]] void die_decode_format(mth_ctx_t *ctx, const char *what) {
     const std::string m = mth_last_error(ctx);
+    if (m.rfind("modtags:", 0) == 0) die(std::string("metheor (MI355X path): ") + mth_strerror(MTH_ERR_FORMAT) + " -- " + m);  // --mm-tags: MM / ML break the rule
     if (m.rfind("tag:", 0) == 0) die(std::string("metheor (MI355X path): ") + mth_strerror(MTH_ERR_FORMAT) + " -- " + m);      // --genome: determine_xm_tag_string panics
     if (m.find("XM") != std::string::npos) die("Error reading XM tag in BAM record. Make sure the reads are aligned using Bismark!");   // readutil.rs:46
     die(std::string("Error reading BAM record. ") + what);
@@ -789,6 +806,7 @@ bool load_on_device(Input &in, const char *cpg_set, CtxFuture &cf) {
         genome_upload(in.ctx, in.h, g_genome, [] {});
         check(in.ctx, mth_decode_set_genome(in.ctx, 1, first_flag >= 0 && (first_flag & 1)));
     }
+    if (g_modtags) check(in.ctx, mth_decode_set_modtags(in.ctx, 1, g_mm_threshold));
     if (cpg_set) check(in.ctx, mth_decode_set_cpg_filter(in.ctx, keys, n_keys, 1));
     check(in.ctx, mth_decode_set_xm_min_mapq(in.ctx, (uint32_t)g_shard.xm_min_mapq));
     const bool on_device = !getenv("METHEOR_HOST_INFLATE") && load_bgzf_on_device(in);
@@ -924,6 +942,7 @@ Input load(const std::string &path, const char *cpg_set, bool host_only = false,
     const bool try_device = !getenv("METHEOR_HOST_DECODE") && !host_only;
     if (!try_device && g_shard.planned()) die("--gpus N / --region need the device load path (METHEOR_HOST_DECODE is set)");
     if (!try_device && !g_genome.path.empty()) die(kNoHostGenome);
+    if (!try_device && g_modtags) die(kNoHostModtags);
     CtxFuture cf;
     if (try_device) cf.start();
     if (mth_host_open(path.c_str(), &in.h, err, sizeof err) != 0) { cf.wait(); die(err); }    // bamutil.rs:7-9
@@ -931,6 +950,7 @@ Input load(const std::string &path, const char *cpg_set, bool host_only = false,
         if (load_on_device(in, cpg_set, cf)) return in;
         if (g_shard.planned()) die("--gpus N / --region need the device load path (coordinate-sorted input, contigs grouped, records inside BGZF blocks)");
         if (!g_genome.path.empty()) die(kNoHostGenome);
+        if (g_modtags) die(kNoHostModtags);
         in.contigs.clear();
     }
     {
@@ -1772,6 +1792,9 @@ int main(int argc, char **argv) {
         if (a.has("lpmd-pairs") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
     }
     if (a.has("genome")) g_genome.path = a.s.at("genome");
+    if (a.has("mm-threshold") && !a.has("mm-tags")) usage_error(cmd, "the argument '--mm-threshold <MM_THRESHOLD>' cannot be used without '--mm-tags'");
+    if (a.has("mm-tags") && a.has("genome")) usage_error(cmd, "the argument '--mm-tags' cannot be used with '--genome <GENOME>'");
+    if (a.has("mm-tags")) { g_modtags = true; g_mm_threshold = (uint32_t)a.n.at("mm-threshold"); }
     // (`all` has no --gpus: one device)
     const int64_t gpus = a.n.count("gpus") ? a.n.at("gpus") : 1;
     int64_t halo = 65536;

@@ -15,7 +15,7 @@ static const char *kKernelNames[K_NUM] = {"k_build_index", "k_pdr_lpmd_tile", "k
                                           "k_fdrp_walk", "k_fdrp_emit", "k_pairs", "k_pairs_tile", "k_decode", "k_inflate", "k_crc32", "k_mhl_tile", "k_pdr_lpmd_wide",
                                           "k_fdrp_tile", "k_fdrp_chain", "k_fdrp_walk4", "k_fdrp_wtile", "k_mhl_rowcheck", "k_decode_genome",
                                           "k_straddle_guess", "k_straddle_walk", "k_straddle_repair", "k_fasta_pack", "k_deflate", "k_tag_assemble", "k_bgzf_compact", "bgzf_d2h",
-                                          "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill"};
+                                          "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill", "k_decode_mm", "k_mm_xm"};
 
 __global__ void k_lpmd_add2(DevState *st, long long n_read, long long n_valid) { st->lpmd[2] += n_read; st->lpmd[3] += n_valid; }
 
@@ -162,6 +162,8 @@ int sync_and_check(mth_ctx *ctx) {
     if (e & ERRB_FORMAT) return fail(ctx, MTH_ERR_FORMAT, "corrupt BGZF block or malformed BAM record (DEFLATE / ISIZE / block_size / field lengths inconsistent)");
     if (e & ERRB_TAGPANIC) return fail(ctx, MTH_ERR_FORMAT, "tag: a record the reference cannot tag either (unplaced or outside its contig / the FASTA, a base without a complement, or a C whose context ends in a deletion): determine_xm_tag_string panics there");
     if (e & ERRB_FDRPPANIC) return fail(ctx, MTH_ERR_FORMAT, "fdrp / qfdrp: a reverse-strand read calls a CpG at its start - 1 and another one 202 bp further while spanning at most 403 bp: the reference's window index is -1 there and it panics (fdrp.rs:70-72, index out of bounds)");
+    if (e & ERRB_MODTAG) return fail(ctx, MTH_ERR_FORMAT, "modtags: a record's MM / ML fields break the rule of mth_decode_set_modtags (aux fields that cannot be walked, ML not of type B:C, MM outside its grammar, ML with another count than the groups own, or a list that selects a C the read does not have)");
+    if (e & ERRB_MODLONG) return fail(ctx, MTH_ERR_CAPACITY, "modtags: a read of more than 65535 bases (a call's offset in its read is 16 bits wide)");
     if (e & ERRB_NOXM) return fail(ctx, MTH_ERR_FORMAT, "a record has no XM:Z tag (the reference panics: Error reading XM tag)");
     if (e & ERRB_UNALIGNED) return fail(ctx, MTH_ERR_UNALIGNED, "a BAM record straddles two BGZF blocks: the per-block device walk does not apply (use the host walk)");
     return MTH_OK;

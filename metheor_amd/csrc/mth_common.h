@@ -22,6 +22,8 @@ enum : uint32_t {
     ERRB_CRC = 1u << 8,        // device inflate: CRC32 of an inflated BGZF block does not match its trailer
     ERRB_TAGPANIC = 1u << 9,   // tag: a record on which the reference's determine_xm_tag_string panics (tag.rs:24, 155-170, 297)
     ERRB_FDRPPANIC = 1u << 10, // FDRP / qFDRP: a read on which the reference's window index leaves 0..=402 (fdrp.rs:70-72) -- it panics
+    ERRB_MODTAG = 1u << 11,    // mth_decode_set_modtags: MM:Z / ML of a record break the rule (grammar, ML type or count, a list past the read's last C)
+    ERRB_MODLONG = 1u << 12,   // mth_decode_set_modtags: a read of more than 65535 bases (cpg_rel is 16 bits)
     ERRB_UNALIGNED = 1u << 7,  // device record walk: a record straddles two BGZF blocks (take the host walk)
 };
 
@@ -43,6 +45,6 @@ struct SiteRec {  // per-tile scratch row
     uint32_t n_conc, n_disc, pad;
 };
 
-enum KernelId { K_INDEX = 0, K_TILE, K_GATHER, K_QBOUND, K_QTILE, K_QINSERT, K_QEMIT, K_MHLWALK, K_MHLWALKBIG, K_MHLEMIT, K_PDRWALK, K_FDRPWALK, K_FDRPEMIT, K_PAIRS, K_PAIRSTILE, K_DECODE, K_INFLATE, K_CRC, K_MHLTILE, K_WIDE, K_FDRPTILE, K_FDRPCHAIN, K_FDRPWALK4, K_FDRPWTILE, K_MHLROWCHK, K_DECODE_GENOME, K_STR_GUESS, K_STR_WALK, K_STR_REPAIR, K_FASTA_PACK, K_DEFLATE, K_TAG_ASSEMBLE, K_BGZF_COMPACT, K_BGZF_D2H, K_BAI_KEYS, K_BAI_ROWS, K_BAI_SORT, K_BAI_FILL, K_NUM };
+enum KernelId { K_INDEX = 0, K_TILE, K_GATHER, K_QBOUND, K_QTILE, K_QINSERT, K_QEMIT, K_MHLWALK, K_MHLWALKBIG, K_MHLEMIT, K_PDRWALK, K_FDRPWALK, K_FDRPEMIT, K_PAIRS, K_PAIRSTILE, K_DECODE, K_INFLATE, K_CRC, K_MHLTILE, K_WIDE, K_FDRPTILE, K_FDRPCHAIN, K_FDRPWALK4, K_FDRPWTILE, K_MHLROWCHK, K_DECODE_GENOME, K_STR_GUESS, K_STR_WALK, K_STR_REPAIR, K_FASTA_PACK, K_DEFLATE, K_TAG_ASSEMBLE, K_BGZF_COMPACT, K_BGZF_D2H, K_BAI_KEYS, K_BAI_ROWS, K_BAI_SORT, K_BAI_FILL, K_DECODE_MM, K_MM_XM, K_NUM };
 
 }  // namespace mth

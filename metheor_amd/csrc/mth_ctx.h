@@ -200,6 +200,9 @@ struct mth_ctx {
     mth::DevBuf fa_genome, fa_tab;
     // mth_decode_set_genome: the decode derives its calls from tag_genome (mth_decode_genome.hip) instead of XM:Z
     bool dec_genome = false, dec_genome_paired = false;
+    // mth_decode_set_modtags: the decode takes its calls from MM:Z / ML:B:C (mth_decode_mm.hip)
+    bool dec_modtags = false;
+    uint32_t dec_mm_threshold = 128;
     unsigned long long tag_cols_total = 0;   // column scratch of the decode call in progress (count pass -> fill pass)
     std::vector<uint64_t> tag_h_off;
     std::vector<uint32_t> tag_h_len;
@@ -346,6 +349,10 @@ struct DecArgs;
 // fills it for k_decode<false>.  count: ncpg / tid / start / end / mapq / fwd; fill: cpg_pos / cpg_rel at a.cpg_off
 int decode_genome_count(mth_ctx *ctx, const DecArgs &a);
 int decode_genome_fill(mth_ctx *ctx, const DecArgs &a);
+// mth_decode_mm.hip: a pass of the decode with the calls taken from MM:Z / ML:B:C (k_decode_mm), and the staged form's first half:
+// X(record, T) of every record into ctx->tag_xm (offsets tag_coloff, lengths tag_xmlen), named in a.xm_base / xm_off / xm_lens
+int decode_mm_pass(mth_ctx *ctx, const DecArgs &a, bool fill);
+int decode_mm_stage(mth_ctx *ctx, DecArgs &a);
 // implemented in mth_sites.hip: PDR with exact flush / re-open semantics (spans > 150 bp)
 int launch_pdr_exact(mth_ctx *ctx, const mth_batch_t &dev_batch, const mth_pdr_lpmd_params_t &p);
 // site discovery (tile pipeline into the private sink): positions called by >= 1 read with

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void k_decode(const DecArgs a) {
         }
         if (!bad && !have_xm) { xm = p; xm_len = 0; have_xm = true; }   // (tolerated, or reported above) no calls; start / end from the CIGAR
         if (!bad && have_xm) {
-            const bool forward = flag == 0u || flag == 99u || flag == 147u;   // readutil.rs:332
+            const bool forward = a.strand_fwd ? !(flag & 16u) : (flag == 0u || flag == 99u || flag == 147u);   // readutil.rs:332; the strand alone under mth_decode_set_modtags
             fwd = forward ? 1 : 0;
             int64_t r = pos;
             uint32_t q = 0;
@@ -407,8 +407,17 @@ int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint6
     // passes; METHEOR_GENOME_STAGED=1: k_tag_xm writes every record's XM string to HBM and k_decode reads it from there
     const bool genome = ctx->dec_genome, staged = genome && getenv("METHEOR_GENOME_STAGED") && atoi(getenv("METHEOR_GENOME_STAGED")) != 0;
     if (genome && ctx->tag_n_refs < 0) return fail(ctx, MTH_ERR_STATE, "mth_decode_set_genome is on but mth_tag_set_genome has not been called");
+    // mth_decode_set_modtags: the calls come from MM:Z / ML:B:C.  Default (METHEOR_MM_STAGED unset or 1): k_mm_xm writes every
+    // record's X string to HBM and k_decode reads it from there -- the tags are parsed once, and measured the faster of the two
+    // (profiles/modtags.md); METHEOR_MM_STAGED=0: k_decode_mm takes the calls in the decode's own two passes, no string exists
+    const bool modtags = ctx->dec_modtags, mm_staged = modtags && !(getenv("METHEOR_MM_STAGED") && atoi(getenv("METHEOR_MM_STAGED")) == 0);
+    a.strand_fwd = modtags ? 1u : 0u; a.mm_threshold = ctx->dec_mm_threshold;
     unsigned long long total = 0;
     if (n_rec) {
+        if (mm_staged) {
+            const int rc = decode_mm_stage(ctx, a);
+            if (rc) return rc;
+        }
         if (staged) {
             unsigned long long xm_bytes = 0;
             const int rc = tag_core(ctx, d_raw, d_off, a.n_rec, ctx->dec_genome_paired ? 1 : 0, &xm_bytes);
@@ -417,6 +426,9 @@ int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint6
         }
         if (genome && !staged) {
             const int rc = decode_genome_count(ctx, a);
+            if (rc) return rc;
+        } else if (modtags && !mm_staged) {
+            const int rc = decode_mm_pass(ctx, a, false);
             if (rc) return rc;
         } else {
             LaunchTimer lt(ctx, K_DECODE);
@@ -435,6 +447,9 @@ int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint6
         a.cpg_pos = ctx->dec_pos.as<uint32_t>(); a.cpg_rel = ctx->dec_rel.as<uint16_t>();
         if (genome && !staged) {
             const int rc = decode_genome_fill(ctx, a);
+            if (rc) return rc;
+        } else if (modtags && !mm_staged) {
+            const int rc = decode_mm_pass(ctx, a, true);
             if (rc) return rc;
         } else {
             LaunchTimer lt(ctx, K_DECODE);
@@ -511,8 +526,18 @@ int mth_decode_reserve(mth_ctx_t *ctx, uint64_t n_reads, uint64_t n_cpgs) {
 int mth_decode_set_genome(mth_ctx_t *ctx, int enabled, int is_paired_end) {
     if (!ctx) return MTH_ERR_INVALID;
     if (enabled && ctx->tag_n_refs < 0) return fail(ctx, MTH_ERR_STATE, "mth_decode_set_genome before mth_tag_set_genome: there is no genome to derive the calls from");
+    if (enabled && ctx->dec_modtags) return fail(ctx, MTH_ERR_STATE, "mth_decode_set_genome while mth_decode_set_modtags is on: a decode has one source of calls");
     ctx->dec_genome = enabled != 0;
     ctx->dec_genome_paired = enabled && is_paired_end;
+    return MTH_OK;
+}
+
+int mth_decode_set_modtags(mth_ctx_t *ctx, int enabled, uint32_t threshold) {
+    if (!ctx) return MTH_ERR_INVALID;
+    if (threshold > 255u) return fail(ctx, MTH_ERR_INVALID, "mth_decode_set_modtags: the threshold is an ML value, 0..=255");
+    if (enabled && ctx->dec_genome) return fail(ctx, MTH_ERR_STATE, "mth_decode_set_modtags while mth_decode_set_genome is on: a decode has one source of calls");
+    ctx->dec_modtags = enabled != 0;
+    ctx->dec_mm_threshold = threshold;
     return MTH_OK;
 }
 

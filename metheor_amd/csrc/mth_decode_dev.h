@@ -1,5 +1,5 @@
 // mth_decode_dev.h -- what the record decode kernels share (mth_decode.hip: calls from XM:Z; mth_decode_genome.hip: calls
-// from the genome): the argument block, unaligned loads, the --cpg-set lookup.
+// from the genome; mth_decode_mm.hip: calls from MM:Z / ML:B:C): the argument block, unaligned loads, the --cpg-set lookup.
 #pragma once
 #include "mth_common.h"
 
@@ -26,6 +26,10 @@ struct DecArgs {
     const uint8_t *xm_base;
     const unsigned long long *xm_off;
     const uint32_t *xm_lens;
+    // mth_decode_set_modtags: the calls come from MM:Z / ML:B:C.  strand_fwd != 0: a record is forward iff its flag has no 0x10
+    // (the position rule of readutil.rs:332 on the strand alone); 0: the flags 0 / 99 / 147 are.  mm_threshold: ML >= this is 'Z'
+    uint32_t strand_fwd;
+    uint32_t mm_threshold;
 };
 
 typedef uint32_t u32x4_a1 __attribute__((ext_vector_type(4), aligned(1)));
