@@ -18,7 +18,11 @@
 // hits only.  What tag.rs does besides and a plain record still has to carry:
 //   * the range checks of tag.rs:155-170 (unplaced, outside the contig or the bases the FASTA gave): the reference panics;
 //   * on a reverse-complemented read EVERY character of the two strings goes through the complement table (tag.rs:19-25)
-//     and one outside it is a panic although no letter depends on it: '=' in SEQ, a stray character in the FASTA.
+//     and one outside it is a panic although no letter depends on it: '=' in SEQ, a stray character in the FASTA;
+//   * a reference C whose context is none of tag.rs:334-372's -- an IUPAC code or a stray character after it, no N beside --
+//     gets NO letter: the string is one short and every later letter is read one query offset early.  So a record whose
+//     reference span [start - 2, end + 2) holds anything but A C G T N (either case) is not treated as plain: it takes the
+//     column walk, which also settles whether that character is a panic.
 // Every other record (I, D, N, =, X, P, SEQ shorter than its CIGAR) takes the exact column walk of mth_tag_dev.h into
 // per-record scratch sized by the count pass (zero for plain records: a file of plain records allocates none), and the
 // decode then reads the letters from there.
@@ -40,6 +44,15 @@ struct GenArgs {
 
 // 0x80 in every byte of v that is zero, exactly (no carry between bytes)
 __device__ __forceinline__ uint32_t zero_bytes(uint32_t v) { return ~(((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v | 0x7f7f7f7fu); }
+
+// 0x80 in every byte of x that is none of A C G T N in either case
+__device__ __forceinline__ uint32_t not_acgtn(uint32_t x) {
+    const uint32_t u = x & 0xdfdfdfdfu;
+    return ~(zero_bytes(u ^ 0x41414141u) | zero_bytes(u ^ 0x43434343u) | zero_bytes(u ^ 0x47474747u) | zero_bytes(u ^ 0x54545454u) |
+             zero_bytes(u ^ 0x4e4e4e4eu)) & 0x80808080u;
+}
+
+enum { GEN_PANIC = 0, GEN_PLAIN = 1, GEN_WALK = 2 };
 
 template <bool FILL>
 struct CallSink {
@@ -82,38 +95,38 @@ __device__ __forceinline__ uint32_t gen_walk_letters(const DecArgs &a, const Tag
     return call.n;
 }
 
-// the plain-record rule (file header); false = the reference panics on this record
+// the plain-record rule (file header) -> GEN_PLAIN; GEN_PANIC = the reference panics on this record; GEN_WALK (count pass
+// only) = its reference span holds a character that can cost a letter, the column walk has to take it
 template <bool FILL>
-__device__ __forceinline__ bool gen_plain(const GenArgs &a, const TagRec &r, uint32_t m, bool forward, unsigned long long w, uint32_t &n_out) {
+__device__ __forceinline__ int gen_plain(const GenArgs &a, const TagRec &r, uint32_t m, bool forward, unsigned long long w, uint32_t &n_out) {
     const TagArgs &t = a.t;
     n_out = 0;
-    if (r.tid < 0 || r.tid >= t.n_refs) return false;                        // tag.rs:155 tid2size[&tid]
+    if (r.tid < 0 || r.tid >= t.n_refs) return GEN_PANIC;                    // tag.rs:155 tid2size[&tid]
     const int64_t start = r.pos, end = start + (m ? m : 1u);                 // htslib bam_endpos
     const bool is_rev = r.flag & 16u, first = r.flag & 64u, last = r.flag & 128u;
     const bool rc = t.paired ? !((!is_rev && first) || (is_rev && last)) : is_rev;
     const int64_t ln = t.g_ln[r.tid], have = (int64_t)(t.g_off[r.tid + 1] - t.g_off[r.tid]);
     const int64_t cs = start - 2 > 0 ? start - 2 : 0, ce = end + 2 < ln ? end + 2 : ln;
-    if (start < 0 || cs > ce || ce > have || end > ln) return false;         // tag.rs:158-170
+    if (start < 0 || cs > ce || ce > have || end > ln) return GEN_PANIC;     // tag.rs:158-170
     const uint8_t *g = t.genome + t.g_off[r.tid];
     auto gat = [&](int64_t p) -> uint8_t { return (p < 0 || p >= ce) ? (uint8_t)'N' : tg_up(g[p]); };
-    if (!FILL && rc) {
-        // tag.rs:246-256: reverse_complement() maps the two flank columns and all m columns of both strings
-        uint32_t bad = 0;
+    if (!FILL) {
+        uint32_t odd = 0;                                                    // anything but A C G T N in [cs, ce): not a plain record
         int64_t p = cs;
-        const int64_t pe = start + m < ce ? start + m : ce;
-        for (; p + 4 <= pe; p += 4) {
-            const uint32_t x = ld_u32(g + p);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bad |= tg_comp(tg_up((uint8_t)(x >> (8 * k)))) ? 0u : 1u;
-        }
-        for (; p < pe; ++p) bad |= tg_comp(tg_up(g[p])) ? 0u : 1u;
-        uint32_t b = 0;                                                      // '=' (nibble 0) is the one SEQ code without a complement
+        for (; p + 4 <= ce; p += 4) odd |= not_acgtn(ld_u32(g + p));
+        for (; p < ce; ++p) odd |= not_acgtn(0x41414100u | g[p]);
+        if (odd) return GEN_WALK;
+    }
+    if (!FILL && rc) {
+        // tag.rs:246-256: reverse_complement() maps the two flank columns and all m columns of both strings.  The reference
+        // bases are A C G T N here, all in the table; '=' (nibble 0) is the one SEQ code without a complement
+        uint32_t bad = 0, b = 0;
         for (; 2u * (b + 4u) <= m; b += 4) {
             const uint32_t x = ld_u32(r.seq + b);
             bad |= zero_bytes(x & 0x0f0f0f0fu) | zero_bytes((x >> 4) & 0x0f0f0f0fu);
         }
         for (uint32_t k = 2u * b; k < m; ++k) bad |= ((r.seq[k >> 1] >> ((k & 1u) ? 0 : 4)) & 15u) ? 0u : 1u;
-        if (bad) return false;
+        if (bad) return GEN_PANIC;
     }
     CallSink<FILL> call{a.d, r.tid, forward, w};
     const int64_t shift = rc ? 1 : 0;                                        // t = P + shift - start for the dinucleotide at P
@@ -157,7 +170,7 @@ __device__ __forceinline__ bool gen_plain(const GenArgs &a, const TagRec &r, uin
         q += len; ref += len;
     }
     n_out = call.n;
-    return true;
+    return GEN_PLAIN;
 }
 
 template <bool FILL>
@@ -193,7 +206,9 @@ __global__ __launch_bounds__(256) void k_decode_genome(const GenArgs a) {
         if (cols >= (1ull << 31)) {
             if (!FILL) atomicOr(a.d.err, (uint32_t)ERRB_FORMAT);
         } else if (FILL ? a.t.ncol[i] == 0u : (plain && m <= r.l_seq)) {
-            if (!gen_plain<FILL>(a, r, (uint32_t)m, forward, FILL ? a.d.cpg_off[i] : 0ull, n) && !FILL) atomicOr(a.d.err, (uint32_t)ERRB_TAGPANIC);
+            const int how = gen_plain<FILL>(a, r, (uint32_t)m, forward, FILL ? a.d.cpg_off[i] : 0ull, n);
+            if (!FILL && how == GEN_PANIC) atomicOr(a.d.err, (uint32_t)ERRB_TAGPANIC);
+            if (!FILL && how == GEN_WALK) ncol = (uint32_t)cols;             // as any record that is not plain
         } else if (FILL) {
             n = gen_walk_letters<true>(a.d, r, tid, forward, a.d.cpg_off[i], a.t.xm + a.t.col_off[i], a.t.xm_len[i]);
         } else {

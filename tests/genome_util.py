@@ -146,7 +146,8 @@ def plain_rule(pos, flag, cigar, seq, contig, paired):
       read not reverse-complemented: genome[p] = C, genome[p + 1] = G, SEQ[t] = C (Z) / T (z)
       reverse-complemented:          genome[p] = G, genome[p - 1] = C, SEQ[t] = G (Z) / A (z)
     (p = pos + t; genome upper-cased, N outside the contig).  The decode reads letter q for the aligned base at query
-    offset q.  -> the calls as decode_walk gives them, or None where tag.rs panics."""
+    offset q.  That holds while the reference span holds A C G T N only; with anything else the record goes the way of every
+    record that is not plain, the column walk.  -> the calls as decode_walk gives them, or None where tag.rs panics."""
     assert all((c & 15) in (0, 4, 5) for c in cigar)
     m = sum(c >> 4 for c in cigar if (c & 15) == 0)
     assert len(seq) >= m
@@ -158,6 +159,9 @@ def plain_rule(pos, flag, cigar, seq, contig, paired):
 
     def gat(p):
         return ord("N") if p < 0 or p >= ce else ord(chr(contig[p]).upper())
+    if any(gat(p) not in b"ACGTN" for p in range(pos - 2, end + 2)):        # an IUPAC code or a stray character after a C can cost
+        xm = pyoracle.tag_xm(pos, flag, cigar, seq, contig, is_paired_end=paired)   # a letter (tag.rs:334-372 push none): not plain
+        return None if xm is None else decode_walk(pos, flag, cigar, xm)
     rc = is_rc(flag, paired)
     if rc:                                                                   # tag.rs:19-25: every character is complemented
         if any(gat(p) not in COMP_OK for p in range(pos - 2, pos + m)) or any(seq[t] not in COMP_OK for t in range(m)):
