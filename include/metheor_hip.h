@@ -224,6 +224,18 @@ int  mth_lpmd_pairs_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const m
  * (lpmd.rs:111); *n_rows always set, arrays may be NULL */
 int  mth_lpmd_pairs_fetch(mth_ctx_t *ctx, uint64_t *n_rows, int32_t *tid, int32_t *pos1, int32_t *pos2, float *lpmd,
                           uint32_t *n_concordant, uint32_t *n_discordant);
+/* ---- LPMD per interval (`lpmd --intervals`; lpmd.rs:70-87, readutil.rs:87-94) ------------------------
+ * The pairs table accumulated so far, reduced on the device by interval: for each of the n intervals [beg[i], end[i]) on contig
+ * tid[i] (host arrays; 0-based, half-open, 0 <= beg <= end; any order, overlap, nesting and duplicates), the exact sums of
+ * n_concordant and n_discordant (add_pair_concordance, lpmd.rs:70-87) over the rows with that contig, beg <= cpg1 and cpg2 < end.
+ * That is what `lpmd -c` counts for the set "every position of the interval": BismarkRead::filter_isin (readutil.rs:87-94) keeps
+ * the calls inside, and a pair of kept calls is a pair of the table.  mth_lpmd_from_counts of the two sums is the interval's LPMD.
+ * A call at position -1 lies in no interval; a contig without batches gives zeros.  Rows of contig groups are compared in the
+ * group's coordinates (the interval is shifted by its contig's voff).  Queued on the context's stream, one synchronisation at the
+ * end; the table is not changed: a second call gives the same sums and mth_lpmd_pairs_fetch is unaffected.  With several contexts
+ * (a pair is owned by the context whose region holds cpg1) the caller adds the contexts' sums. */
+int  mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, const int32_t *beg, const int32_t *end,
+                              int64_t *n_concordant, int64_t *n_discordant);
 
 /* ---- contig groups: many contigs in one batch -------------------------------------------------------------------------------------
  * A batch is a coordinate interval of ONE contig (mth_batch_t.tid).  A job over many contigs -- 24 for a human genome, thousands with

@@ -15,7 +15,7 @@ SYMBOLS = [
     "mth_strerror", "mth_last_error", "mth_notes", "mth_batch_prepare", "mth_batch_release", "mth_reset", "mth_pdr_lpmd_accumulate", "mth_pdr_count",
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
-    "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch",
+    "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch", "mth_lpmd_intervals_fetch",
     "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome", "mth_decode_set_modtags",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
@@ -188,6 +188,7 @@ def lib():
         L.mth_multi_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
         L.mth_lpmd_pairs_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_lpmd_pairs_params_t)]
         L.mth_lpmd_pairs_fetch.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 6
+        L.mth_lpmd_intervals_fetch.argtypes = [vp, C.c_uint64] + [vp] * 5
         L.mth_decode_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_decoded_t)]
         L.mth_decode_set_cpg_filter.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mth_decode_set_xm_min_mapq.argtypes = [vp, C.c_uint32]
@@ -516,6 +517,20 @@ class Engine:
                    lpmd=np.zeros(k, np.float32), n_concordant=np.zeros(k, np.uint32), n_discordant=np.zeros(k, np.uint32))
         self._check(self.L.mth_lpmd_pairs_fetch(self.h, C.byref(n), *[out[x].ctypes.data_as(C.c_void_p) for x in
                                                                       ("tid", "pos1", "pos2", "lpmd", "n_concordant", "n_discordant")]))
+        return out
+
+    def lpmd_intervals_fetch(self, tid, beg, end):
+        """the pairs table accumulated so far, reduced on the device by interval [beg, end) of contig tid (0-based, half-open): exact
+        int64 sums of the rows with beg <= cpg1 and cpg2 < end, and lpmd = lpmd_from_counts of the two (lpmd.rs:51-55)"""
+        t, b, e = (np.ascontiguousarray(x, np.int32) for x in (tid, beg, end))
+        assert t.ndim == 1 and t.shape == b.shape == e.shape
+        k = len(t)
+        out = dict(n_concordant=np.zeros(k, np.int64), n_discordant=np.zeros(k, np.int64))
+        self._check(self.L.mth_lpmd_intervals_fetch(self.h, k, *[x.ctypes.data_as(C.c_void_p) for x in
+                                                                 (t, b, e, out["n_concordant"], out["n_discordant"])]))
+        self._settled()
+        out["lpmd"] = np.array([self.L.mth_lpmd_from_counts(int(c), int(d)) for c, d in zip(out["n_concordant"], out["n_discordant"])],
+                               np.float32)
         return out
 
     # ---- device-side BAM record decode (mth_decode.hip) ----

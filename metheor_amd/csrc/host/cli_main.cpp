@@ -57,6 +57,8 @@ const Opt O_GENOME = {"genome", 'g', "GENOME", "(MI355X extension) Reference FAS
 // not in the reference: 5mC calls as current instruments write them, the SAM base-modification tags
 const Opt O_MMTAGS = {"mm-tags", 0, "", "(MI355X extension) Take the methylation calls from the MM:Z / ML:B:C base-modification tags (5mC, C+m, in read CpG context) instead of XM:Z tags; XM:Z tags in the input are ignored", nullptr, false, 'F'};
 const Opt O_MMTHR = {"mm-threshold", 0, "MM_THRESHOLD", "(MI355X extension) With the MM / ML tags as the source of calls: a listed C whose ML probability is at least this (0..=255) is methylated", "128", false, 'B'};
+// not in the reference: LPMD per interval of a BED file, reduced on the device from the pairs table
+const Opt O_INTERVALS = {"intervals", 0, "INTERVALS", "(MI355X extension) BED file of intervals: LPMD of each one, as `-c` with all of the interval's positions would give it", nullptr, false, 's'};
 const Opt O_BAI = {"bai", 'b', "BAI", "(MI355X extension) BAM index for --region [default: <input>.bai]", nullptr, false, 's'};
 
 // lib.rs:24-231
@@ -100,7 +102,8 @@ const std::vector<Cmd> &commands() {
           {"pairs", 'p', "PAIRS", "(Optional) Concordance information for all CpG pairs", nullptr, false, 's'},
           {"min-distance", 'm', "MIN_DISTANCE", "Minimum distance between CpG pairs to consider", "2", false, 'I'},
           {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
-          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR,
+          O_INTERVALS, {"intervals-output", 0, "INTERVALS_OUTPUT", "(MI355X extension) Output table of the per-interval LPMD (needs --intervals)", nullptr, false, 's'}}},
         // not in the reference: any subset of the seven measures from ONE decode of the input (the parameters are shared by every
         // measure that has them, under the single commands' names and defaults; --lpmd-pairs is lpmd's --pairs, whose -p is min-cpgs here)
         {"all", "(MI355X extension) Compute any of the seven measures from one decode of the input",
@@ -120,7 +123,8 @@ const std::vector<Cmd> &commands() {
           {"max-distance", 'M', "MAX_DISTANCE", "Maximum distance between CpG pairs to consider", "16", false, 'I'},
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
           {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'},
-          O_CPG, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR}},
+          O_CPG, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR,
+          O_INTERVALS, {"lpmd-intervals", 0, "LPMD_INTERVALS", "(MI355X extension) Output table of the per-interval LPMD (needs --lpmd and --intervals)", nullptr, false, 's'}}},
         {"tag", "Add bismark XM tag to BAM file",
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
           {"genome", 'g', "GENOME", "", nullptr, true, 's'},
@@ -283,7 +287,7 @@ struct Shard {
 thread_local Shard g_shard;
 
 // what one shard contributes to the output files (filled through open_memstream when world > 1)
-struct Part { char *out = nullptr; size_t out_len = 0; char *pairs = nullptr; size_t pairs_len = 0; };
+struct Part { char *out = nullptr; size_t out_len = 0; char *pairs = nullptr; size_t pairs_len = 0; std::vector<int64_t> iv_c, iv_d; };
 thread_local Part *g_part = nullptr;
 
 // the shards' threads meet here once: the last to arrive runs the collective for all of them
@@ -1255,6 +1259,86 @@ void lpmd_pairs_write(mth_ctx_t *ctx, const Input &in, const std::string &path) 
     if (fclose(g) != 0) die("Error writing to output file.");
 }
 
+// ---- lpmd --intervals: LPMD per interval of a BED file -------------------------------------------------------
+// Read by main() before any device or output is touched; every shard of a --gpus N run reduces its own rows for all of them.
+struct Intervals {
+    std::string path, out_path;
+    std::vector<std::string> chrom, name;
+    std::vector<int32_t> tid, beg, end;
+    bool on() const { return !out_path.empty(); }
+} g_intervals;
+
+// BED: tab-separated, chrom start end [name [...]], 0-based half-open; empty lines and '#' / track / browser lines are skipped
+void intervals_read(const mth_host_t *h) {
+    Intervals &iv = g_intervals;
+    FILE *f = fopen(iv.path.c_str(), "rb");
+    if (!f) die("Error opening intervals file " + iv.path + ": " + strerror(errno));
+    std::string text;
+    char chunk[1 << 16];
+    for (size_t k; (k = fread(chunk, 1, sizeof chunk, f)) > 0;) text.append(chunk, k);
+    fclose(f);
+    auto bad = [&](size_t line_no, const std::string &why) { die("Error reading intervals file " + iv.path + ": line " + std::to_string(line_no) + ": " + why); };
+    auto number = [&](const std::string &v, size_t line_no, const char *what) -> int32_t {
+        if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != std::string::npos)
+            bad(line_no, std::string(what) + " '" + v + "' is not a number in 0..=2147483647");
+        const long long x = strtoll(v.c_str(), nullptr, 10);
+        if (x > INT32_MAX) bad(line_no, std::string(what) + " '" + v + "' is not a number in 0..=2147483647");
+        return (int32_t)x;
+    };
+    size_t line_no = 0;
+    for (size_t p = 0; p < text.size();) {
+        size_t e = text.find('\n', p);
+        if (e == std::string::npos) e = text.size();
+        std::string line = text.substr(p, e - p);
+        p = e + 1;
+        ++line_no;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#' || line.rfind("track", 0) == 0 || line.rfind("browser", 0) == 0) continue;
+        std::vector<std::string> col;
+        for (size_t c = 0;;) {
+            const size_t t = line.find('\t', c);
+            col.push_back(line.substr(c, t == std::string::npos ? std::string::npos : t - c));
+            if (t == std::string::npos || col.size() == 4) break;
+            c = t + 1;
+        }
+        if (col.size() < 3) bad(line_no, "fewer than 3 tab-separated columns");
+        const int32_t b = number(col[1], line_no, "start"), en = number(col[2], line_no, "end");
+        if (b > en) bad(line_no, "start " + col[1] + " is beyond end " + col[2]);
+        const int tid = mth_host_ref_tid(h, col[0].c_str());
+        if (tid < 0) bad(line_no, "the input's header has no reference named '" + col[0] + "'");
+        iv.chrom.push_back(col[0]); iv.name.push_back(col.size() > 3 && !col[3].empty() ? col[3] : ".");
+        iv.tid.push_back(tid); iv.beg.push_back(b); iv.end.push_back(en);
+    }
+}
+
+// chrom, start, end, name, lpmd (lpmd.rs:51-55 over the interval's own counters), n_concordant, n_discordant: one row per BED line
+void intervals_write(const std::vector<int64_t> &nc, const std::vector<int64_t> &nd) {
+    const Intervals &iv = g_intervals;
+    FILE *f = open_file(iv.out_path);
+    fprintf(f, "chrom\tstart\tend\tname\tlpmd\tn_concordant\tn_discordant\n");
+    LineWriter w(f);
+    for (size_t i = 0; i < iv.tid.size(); ++i) {
+        w.str(iv.chrom[i].c_str()); w.ch('\t'); w.i32(iv.beg[i]); w.ch('\t'); w.i32(iv.end[i]); w.ch('\t'); w.str(iv.name[i].c_str()); w.ch('\t');
+        w.f32(mth_lpmd_from_counts(nc[i], nd[i])); w.ch('\t'); w.i64(nc[i]); w.ch('\t'); w.i64(nd[i]); w.eol();
+    }
+    w.flush();
+    if (fclose(f) != 0) die("Error writing to output file.");
+}
+
+// the pairs table accumulated on this context, reduced by interval on the device (a shard of several: its sums go to main(), which
+// adds the shards' -- a pair is owned by the shard that holds cpg1 -- and writes the file)
+void lpmd_intervals_write(mth_ctx_t *ctx) {
+    const Intervals &iv = g_intervals;
+    const size_t n = iv.tid.size();
+    std::vector<int64_t> nc(n), nd(n);
+    {
+        Phase ph("interval reduction (kernel, sync)");
+        check(ctx, mth_lpmd_intervals_fetch(ctx, n, iv.tid.data(), iv.beg.data(), iv.end.data(), nc.data(), nd.data()));
+    }
+    if (g_shard.world > 1) { g_part->iv_c.swap(nc); g_part->iv_d.swap(nd); return; }
+    intervals_write(nc, nd);
+}
+
 // me.rs:68-88 / pm.rs:63-83: one line per quartet with depth >= min_depth,
 // chrom, pos1..pos4, value (me.rs:57-65).  The reference iterates a HashMap (random order).
 void quartet_write(mth_ctx_t *ctx, const Input &in, uint32_t min_depth, bool want_me, const std::string &path) {
@@ -1351,14 +1435,15 @@ int run_lpmd(const Args &a) {
     p.want_lpmd = 1;
     submit(ctx, in, p);
     lpmd_write(ctx, in, input, p.lpmd_min_qual, a.s.at("output"));
-    if (a.has("pairs")) {                                       // lpmd.rs:149-151, 89-122
+    if (a.has("pairs") || g_intervals.on()) {                   // lpmd.rs:149-151, 89-122
         mth_lpmd_pairs_params_t pp;
         pp.min_distance = mind; pp.max_distance = maxd; pp.min_qual = p.lpmd_min_qual;
         for (const Contig &c : in.contigs) {
             const mth_batch_t b = make_batch(in, c);
             check(ctx, mth_lpmd_pairs_accumulate(ctx, &b, &pp));
         }
-        lpmd_pairs_write(ctx, in, a.s.at("pairs"));
+        if (a.has("pairs")) lpmd_pairs_write(ctx, in, a.s.at("pairs"));
+        if (g_intervals.on()) lpmd_intervals_write(ctx);        // --intervals alone: the table stays on the device
     }
     return finish(ctx, in.h);
 }
@@ -1443,7 +1528,7 @@ int run_fdrp(const Args &a, bool quantitative) {
 int run_all(const Args &a) {
     const std::string input = a.s.at("input");
     const char *cpg_set = a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr;
-    const bool w_pdr = a.has("pdr"), w_lpmd = a.has("lpmd"), w_pairs = a.has("lpmd-pairs"), w_mhl = a.has("mhl"), w_me = a.has("me"),
+    const bool w_pdr = a.has("pdr"), w_lpmd = a.has("lpmd"), w_pairs = a.has("lpmd-pairs"), w_iv = g_intervals.on(), w_mhl = a.has("mhl"), w_me = a.has("me"),
                w_pm = a.has("pm"), w_fdrp = a.has("fdrp"), w_qfdrp = a.has("qfdrp");
     const uint32_t min_depth = (uint32_t)a.n.at("min-depth");
     const uint32_t min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
@@ -1509,10 +1594,10 @@ int run_all(const Args &a) {
             host_in = load(input, cpg_set, true, ctx);
             bin = &host_in;
         }
-        mp.want = (w_lpmd ? MTH_MULTI_LPMD : 0u) | ((w_me || w_pm) ? MTH_MULTI_QUARTET : 0u) | (w_pairs ? MTH_MULTI_PAIRS : 0u);
+        mp.want = (w_lpmd ? MTH_MULTI_LPMD : 0u) | ((w_me || w_pm) ? MTH_MULTI_QUARTET : 0u) | ((w_pairs || w_iv) ? MTH_MULTI_PAIRS : 0u);
     } else {
         mp.want = (w_pdr ? MTH_MULTI_PDR : 0u) | (w_lpmd ? MTH_MULTI_LPMD : 0u) | ((w_me || w_pm) ? MTH_MULTI_QUARTET : 0u) |
-                  (w_mhl ? MTH_MULTI_MHL : 0u) | ((w_fdrp || w_qfdrp) ? MTH_MULTI_FDRP : 0u) | (w_pairs ? MTH_MULTI_PAIRS : 0u);
+                  (w_mhl ? MTH_MULTI_MHL : 0u) | ((w_fdrp || w_qfdrp) ? MTH_MULTI_FDRP : 0u) | ((w_pairs || w_iv) ? MTH_MULTI_PAIRS : 0u);
     }
     {
         Phase ph("H2D + kernels (sync)");
@@ -1527,6 +1612,7 @@ int run_all(const Args &a) {
     if (mp.want & MTH_MULTI_PDR) pdr_write(ctx, *bin, a.s.at("pdr"));
     if (w_lpmd) lpmd_write(ctx, *bin, input, min_qual, a.s.at("lpmd"));
     if (w_pairs) lpmd_pairs_write(ctx, *bin, a.s.at("lpmd-pairs"));
+    if (w_iv) lpmd_intervals_write(ctx);
     if (w_me) quartet_write(ctx, *bin, min_depth, true, a.s.at("me"));
     if (w_pm) quartet_write(ctx, *bin, min_depth, false, a.s.at("pm"));
     if (mp.want & MTH_MULTI_MHL) mhl_write(ctx, *bin, a.s.at("mhl"));
@@ -1790,6 +1876,14 @@ int main(int argc, char **argv) {
         if (!any)
             usage_error(cmd, "the following required arguments were not provided:\n  <--pdr <PDR>|--lpmd <LPMD>|--mhl <MHL>|--me <ME>|--pm <PM>|--fdrp <FDRP>|--qfdrp <QFDRP>>");
         if (a.has("lpmd-pairs") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
+        // --intervals and --lpmd-intervals come together, and the table is LPMD's
+        if (a.has("intervals") && !a.has("lpmd-intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd-intervals <LPMD_INTERVALS>");
+        if (a.has("lpmd-intervals") && !a.has("intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals <INTERVALS>");
+        if (a.has("intervals") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
+    }
+    if (sub == "lpmd") {     // `requires`, both ways
+        if (a.has("intervals") && !a.has("intervals-output")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals-output <INTERVALS_OUTPUT>");
+        if (a.has("intervals-output") && !a.has("intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals <INTERVALS>");
     }
     if (a.has("genome")) g_genome.path = a.s.at("genome");
     if (a.has("mm-threshold") && !a.has("mm-tags")) usage_error(cmd, "the argument '--mm-threshold <MM_THRESHOLD>' cannot be used without '--mm-tags'");
@@ -1817,6 +1911,15 @@ int main(int argc, char **argv) {
     } else if (a.has("bai")) usage_error(cmd, "the argument '--bai <BAI>' needs '--region <REGION>'");
     const int world = (int)std::min<int64_t>(gpus, 4096);
     if (world < 1) usage_error(cmd, "invalid value '0' for '--gpus <GPUS>': at least one GPU");
+    if (a.has("intervals")) {    // the BED is read against the input's header before any device or output file is touched
+        g_intervals.path = a.s.at("intervals");
+        g_intervals.out_path = a.s.at(sub == "all" ? "lpmd-intervals" : "intervals-output");
+        mth_host_t *h = nullptr;
+        char err[1024];
+        if (mth_host_open(a.s.at("input").c_str(), &h, err, sizeof err) != 0) die(err);
+        { Phase ph("intervals BED (header + parse)"); intervals_read(h); }
+        mth_host_close(h);
+    }
     if (world == 1) {
         if (const char *dev = getenv("METHEOR_DEVICE")) g_shard.device = atoi(dev);
         g_shard.halo = halo;
@@ -1855,6 +1958,13 @@ int main(int argc, char **argv) {
     };
     write_parts(a.s.at("output"), false);
     if (sub == "lpmd" && a.has("pairs")) write_parts(a.s.at("pairs"), true);
+    if (g_intervals.on()) {      // every shard reduced its own rows for all the intervals: the sums add up
+        const size_t n = g_intervals.tid.size();
+        std::vector<int64_t> nc(n, 0), nd(n, 0);
+        for (const Part &p : parts)
+            for (size_t i = 0; i < n && i < p.iv_c.size(); ++i) { nc[i] += p.iv_c[i]; nd[i] += p.iv_d[i]; }
+        intervals_write(nc, nd);
+    }
     fflush(nullptr);
     _exit(0);
 }

@@ -15,7 +15,7 @@ static const char *kKernelNames[K_NUM] = {"k_build_index", "k_pdr_lpmd_tile", "k
                                           "k_fdrp_walk", "k_fdrp_emit", "k_pairs", "k_pairs_tile", "k_decode", "k_inflate", "k_crc32", "k_mhl_tile", "k_pdr_lpmd_wide",
                                           "k_fdrp_tile", "k_fdrp_chain", "k_fdrp_walk4", "k_fdrp_wtile", "k_mhl_rowcheck", "k_decode_genome",
                                           "k_straddle_guess", "k_straddle_walk", "k_straddle_repair", "k_fasta_pack", "k_deflate", "k_tag_assemble", "k_bgzf_compact", "bgzf_d2h",
-                                          "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill", "k_decode_mm", "k_mm_xm"};
+                                          "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill", "k_decode_mm", "k_mm_xm", "k_pairs_intervals"};
 
 __global__ void k_lpmd_add2(DevState *st, long long n_read, long long n_valid) { st->lpmd[2] += n_read; st->lpmd[3] += n_valid; }
 
@@ -350,7 +350,7 @@ void mth_ctx_destroy(mth_ctx_t *ctx) {
                       &ctx->s_pos, &ctx->s_pdr, &ctx->s_nc, &ctx->s_nd, &ctx->s_batch_cnt, &ctx->w_val, &ctx->w_cov, &ctx->w_aux, &ctx->w_flags,
                       &ctx->w_blk, &ctx->w_huge, &ctx->m_state, &ctx->m_pos, &ctx->m_val, &ctx->m_cov, &ctx->m_batch_rows,
                       &ctx->f_state, &ctx->f_pos, &ctx->f_val, &ctx->f_qval, &ctx->f_n, &ctx->f_batch_rows, &ctx->f_rows, &ctx->f_pairtab, &ctx->fo_sel, &ctx->fo_flag, &ctx->fo_tmp, &ctx->fo_out, &ctx->f_redo, &ctx->f_terms, &ctx->f_soff, &ctx->f_snz, &ctx->f_sdisc, &ctx->f_quot,
-                      &ctx->p_keys, &ctx->p_cnt, &ctx->p_out_key, &ctx->p_out_cnt, &ctx->p_batch_rows})
+                      &ctx->p_keys, &ctx->p_cnt, &ctx->p_out_key, &ctx->p_out_cnt, &ctx->p_batch_rows, &ctx->iv_tab, &ctx->iv_acc})
         b->release();
     for (TileRowTable *t : {&ctx->quartets, &ctx->pairs})
         for (DevBuf *b : {&t->state, &t->snap, &t->tflag, &t->tile_row0, &t->tile_rows}) b->release();

@@ -259,6 +259,8 @@ struct mth_ctx {
     // LPMD per-pair table (mth_pairs.hip)
     mth::TileRowTable pairs{"pairs", "pairs", "MTH_PAIRS", 0.1, mth::pairs_measure()};
     mth::DevBuf p_keys, p_cnt, p_out_key, p_out_cnt, p_batch_rows;
+    // LPMD per interval (mth_intervals.hip): the sorted intervals + work items of the call in flight, the per-interval sums
+    mth::DevBuf iv_tab, iv_acc;
 
     // multi-GPU exchange step (mth_rccl.hip): communicator of the one-process-per-GPU form; lpmd_reduced = DevState.lpmd
     // already holds the all-reduced totals (cleared by the next batch that adds to them)

@@ -1,0 +1,303 @@
+// mth_intervals.hip -- LPMD per interval (`metheor lpmd --intervals BED`): the pairs table of mth_pairs.hip (lpmd.rs:70-87,
+// add_pair_concordance) reduced by interval on the device.
+//
+// The reference restricts LPMD to a set of positions with `-c`: BismarkRead::filter_isin (readutil.rs:87-94) drops the calls whose
+// abspos is not in the set, and compute_pairwise_cpg_concordance_discordance (readutil.rs:166-224) pairs the calls that are left by
+// their relpos distance -- a pure function of the two calls.  For the set "every position of [beg, end) on a contig" the counters
+// are therefore the pairs-table rows (cpg1, cpg2) of that contig with beg <= cpg1 and cpg2 < end, summed.
+//
+// Device: the table is not one sorted array (per-tile runs with gaps; the global path's rows unsorted behind each batch; virtual
+// coordinates under contig groups), so the reduction runs over the ROWS and needs no order of them.  The intervals are sorted once
+// on the host, per domain (a batch's tid: a contig or a contig group, whose intervals are shifted by their contig's voff and cut at
+// its end) and per length class (lengths within a factor 4), with a running maximum of the ends.  One workgroup takes one tile's
+// rows (or 2048 rows of the global path): per class it finds the intervals that start at or before the rows' largest cpg1 -- none,
+// or none that reaches the rows' smallest cpg2, ends the class there -- stages the starts its rows can land on in LDS, and every row
+// finds its last interval with start <= cpg1 by binary search and walks back while the running maximum says an end > cpg2 is still
+// ahead.  A class keeps the walk short: an interval k steps back starts at least k / depth interval lengths earlier, and the class's
+// longest is at most 4x its shortest, so a row passes at most ~4x the intervals that hold it, whatever other lengths the BED mixes in
+// (a chromosome-long interval sits in a class of its own and costs one step).  A row adds its counters to its intervals in LDS --
+// the workgroup's rows can only touch the intervals from the first whose running maximum passes their smallest cpg2 on -- and the
+// workgroup then adds each interval it touched to memory once: a 1 Mbp interval takes two 64-bit atomics per tile, not per row.
+// Rows that can touch more than IV_ACC intervals of a class (windows nested thousands deep) add to memory directly: slower, never
+// a capacity error.
+#include <algorithm>
+#include <unordered_map>
+
+#include "mth_ctx.h"
+
+namespace mth {
+
+constexpr int IV_B = 256;              // threads of a workgroup
+constexpr int IV_LDS = 2048;           // interval starts a workgroup stages (8 KiB); a wider window is searched in memory
+constexpr int IV_ACC = 1024;           // intervals a workgroup sums in LDS (16 KiB); rows that can touch more add straight to memory
+constexpr uint32_t IV_CHUNK = 2048;    // rows of the global path per work item (a tile's LDS table holds as many)
+
+struct IvArgs {
+    const unsigned long long *key;                 // rows of the pairs table: cpg1 << 32 | cpg2
+    const uint2 *cnt;                              //                          concordant, discordant
+    const unsigned long long *tile_row0;           // work items [0, n_tiles): a tile's rows
+    const uint32_t *tile_rows;
+    const unsigned long long *b_tile_end;          // per batch: tiles of all batches up to and including it
+    const uint32_t *b_slice;                       // per batch: its domain's slices [b_slice[2b], b_slice[2b + 1])
+    const unsigned long long *c_row0;              // work items [n_tiles, n_tiles + n_chunks): rows of the global path
+    const uint32_t *c_n, *c_batch;
+    const int32_t *s_beg, *s_end;                  // per slice (one domain, one length class): its entries
+    const int32_t *e_start, *e_end, *e_maxend;     // per entry, sorted by start within the slice; maxend: running maximum of e_end
+    const uint32_t *e_out;                         // the interval (caller's index) the entry adds to
+    unsigned long long *acc;                       // per interval: concordant, discordant
+    unsigned long long n_tiles;
+    uint32_t n_chunks, n_batches;
+};
+
+// first index in [lo, hi) whose value is > v
+__device__ __forceinline__ int32_t iv_upper(const int32_t *__restrict__ a, int32_t lo, int32_t hi, int32_t v) {
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The same for a value the whole wave shares, called where every lane of the wave is active (block-uniform code): 64 probes a round,
+// so a slice of 10^5 intervals takes three dependent loads instead of seventeen.  The work items are small (a tile's rows) and these
+// searches are what each of them waits for.
+__device__ __forceinline__ int32_t iv_upper_wave(const int32_t *__restrict__ a, int32_t lo, int32_t hi, int32_t v, int lane) {
+    while (hi - lo > 64) {
+        const int32_t step = (hi - lo + 63) >> 6;
+        const long long last = (long long)hi - 1;
+        const int32_t idx = (int32_t)min((long long)lo + (long long)(lane + 1) * step - 1, last);   // ascending over the lanes; lane 63 probes hi - 1
+        const int k = __popcll(__ballot(a[idx] <= v));                        // a is sorted: the probes <= v are the first k
+        if (k == 64) return hi;
+        hi = (int32_t)min((long long)lo + (long long)(k + 1) * step - 1, last);   // the first probe > v: the answer is at or before it
+        if (k) lo = lo + k * step;                                            // the last probe <= v (never the clamped one): the answer is behind it
+    }
+    const int32_t idx = lo + lane;
+    return lo + __popcll(__ballot(idx < hi && a[idx] <= v));
+}
+
+__global__ __launch_bounds__(IV_B) void k_pairs_intervals(const IvArgs a) {
+    __shared__ int32_t s_start[IV_LDS];
+    __shared__ unsigned long long s_acc[2 * IV_ACC];
+    __shared__ int32_t s_red[3][IV_B / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long n_items = a.n_tiles + a.n_chunks;
+    for (unsigned long long it = blockIdx.x; it < n_items; it += gridDim.x) {
+        unsigned long long r0;
+        uint32_t n, b;
+        if (it < a.n_tiles) {
+            n = a.tile_rows[it];
+            if (!n) continue;
+            r0 = a.tile_row0[it];
+            uint32_t lo = 0, hi = a.n_batches;                  // the tile's batch: the first whose tile_end lies beyond it
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (a.b_tile_end[mid] > it) hi = mid; else lo = mid + 1;
+            }
+            b = lo;
+        } else {
+            const unsigned long long k = it - a.n_tiles;
+            r0 = a.c_row0[k]; n = a.c_n[k]; b = a.c_batch[k];
+        }
+        const uint32_t sl0 = a.b_slice[2 * b], sl1 = a.b_slice[2 * b + 1];
+        if (sl0 == sl1) continue;                               // no interval on the batch's contig(s)
+        // the rows' smallest and largest cpg1 and smallest cpg2: what of a slice they can touch
+        int32_t mn1 = INT32_MAX, mx1 = -1, mn2 = INT32_MAX;
+        for (uint32_t i = tid; i < n; i += IV_B) {
+            const unsigned long long k = a.key[r0 + i];
+            const int32_t p1 = (int32_t)(k >> 32), p2 = (int32_t)(k & 0x7fffffffull);
+            mn1 = min(mn1, p1); mx1 = max(mx1, p1); mn2 = min(mn2, p2);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mn1 = min(mn1, __shfl_xor(mn1, o, 64)); mx1 = max(mx1, __shfl_xor(mx1, o, 64)); mn2 = min(mn2, __shfl_xor(mn2, o, 64));
+        }
+        __syncthreads();                                        // the previous item's readers of s_red and s_start are done
+        if (lane == 0) { s_red[0][wave] = mn1; s_red[1][wave] = mx1; s_red[2][wave] = mn2; }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < IV_B / 64; ++w) { mn1 = min(mn1, s_red[0][w]); mx1 = max(mx1, s_red[1][w]); mn2 = min(mn2, s_red[2][w]); }
+        for (uint32_t s = sl0; s < sl1; ++s) {                  // everything up to the row loop is block-uniform
+            const int32_t lo = a.s_beg[s], hi = a.s_end[s];
+            const int32_t w_hi = iv_upper_wave(a.e_start, lo, hi, mx1, lane);
+            if (w_hi == lo) continue;                           // every interval starts beyond the rows
+            // the running maximum ascends: below w_min no interval reaches the rows' smallest cpg2, and no walk gets there
+            const int32_t w_min = iv_upper_wave(a.e_maxend, lo, w_hi, mn2, lane);
+            if (w_min == w_hi) continue;                        // every interval that starts in time ends before the rows
+            const int32_t w_lo = iv_upper_wave(a.e_start, lo, w_hi, mn1, lane);
+            const int32_t w_n = w_hi - w_lo, acc_n = w_hi - w_min;
+            const bool in_lds = w_n <= IV_LDS, acc_lds = acc_n <= IV_ACC;
+            __syncthreads();                                    // the previous slice's searches and its flush are done
+            if (in_lds)
+                for (int32_t i = tid; i < w_n; i += IV_B) s_start[i] = a.e_start[w_lo + i];
+            if (acc_lds)
+                for (int32_t i = tid; i < 2 * acc_n; i += IV_B) s_acc[i] = 0ull;
+            __syncthreads();
+            for (uint32_t i = (uint32_t)tid; i < n; i += IV_B) {
+                const unsigned long long k = a.key[r0 + i];
+                const int32_t p1 = (int32_t)(k >> 32), p2 = (int32_t)(k & 0x7fffffffull);
+                const uint2 c = a.cnt[r0 + i];
+                // the last interval of the slice with start <= cpg1 (every one before the window starts at or before the rows' smallest
+                // cpg1), then back while the running maximum says that an end beyond cpg2 is still ahead
+                int32_t j = (in_lds ? w_lo + iv_upper(s_start, 0, w_n, p1) : iv_upper(a.e_start, w_lo, w_hi, p1)) - 1;
+                for (; j >= w_min && a.e_maxend[j] > p2; --j) {
+                    if (a.e_end[j] <= p2) continue;                     // start <= cpg1 and cpg2 < end: the row is the interval's
+                    if (acc_lds) {
+                        if (c.x) atomicAdd(&s_acc[2 * (j - w_min)], (unsigned long long)c.x);
+                        if (c.y) atomicAdd(&s_acc[2 * (j - w_min) + 1], (unsigned long long)c.y);
+                    } else {
+                        const unsigned long long t = a.e_out[j];
+                        if (c.x) atomicAdd(&a.acc[2ull * t], (unsigned long long)c.x);
+                        if (c.y) atomicAdd(&a.acc[2ull * t + 1], (unsigned long long)c.y);
+                    }
+                }
+            }
+            if (!acc_lds) continue;
+            __syncthreads();
+            for (int32_t i = tid; i < acc_n; i += IV_B) {       // one pair of global atomics per interval the workgroup's rows touched
+                const unsigned long long nc = s_acc[2 * i], nd = s_acc[2 * i + 1];
+                if (!(nc | nd)) continue;
+                const unsigned long long t = a.e_out[w_min + i];
+                if (nc) atomicAdd(&a.acc[2ull * t], nc);
+                if (nd) atomicAdd(&a.acc[2ull * t + 1], nd);
+            }
+        }
+    }
+}
+
+// an interval as the rows of one domain see it
+struct IvEntry { int32_t start, end; uint32_t out; };
+
+}  // namespace mth
+
+using namespace mth;
+
+extern "C" {
+
+int mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, const int32_t *beg, const int32_t *end,
+                             int64_t *n_concordant, int64_t *n_discordant) {
+    if (!ctx) return MTH_ERR_INVALID;
+    if (n && (!tid || !beg || !end || !n_concordant || !n_discordant)) return fail(ctx, MTH_ERR_INVALID, "intervals: an array is missing");
+    if (n >= (1ull << 31)) return fail(ctx, MTH_ERR_CAPACITY, "intervals: 2^31 or more intervals in one call");
+    for (uint64_t i = 0; i < n; ++i)
+        if (tid[i] < 0 || beg[i] < 0 || end[i] < beg[i]) return fail(ctx, MTH_ERR_INVALID, "intervals: want tid >= 0 and 0 <= beg <= end");
+    MTH_ENTER(ctx);                                       // settles the queued batches of the table: its metas are exact from here
+    if (n == 0) return sync_and_check(ctx);
+    const TileRowTable &t = ctx->pairs;
+    hipStream_t s = ctx->stream;
+
+    // ---- the intervals per domain and length class, sorted by start ----
+    std::unordered_map<int32_t, std::vector<uint32_t>> by_tid;
+    for (uint64_t i = 0; i < n; ++i)
+        if (beg[i] < end[i]) by_tid[tid[i]].push_back((uint32_t)i);
+    std::vector<int32_t> s_beg, s_end, e_start, e_end, e_maxend;
+    std::vector<uint32_t> e_out;
+    std::unordered_map<int32_t, std::pair<uint32_t, uint32_t>> dom_slices;     // a batch tid -> its slices
+    auto add_domain = [&](int32_t dom) -> int {
+        constexpr int NCLS = 17;
+        std::vector<IvEntry> cls[NCLS];
+        auto put = [&](int64_t vb, int64_t ve, uint32_t out) {
+            if (vb >= ve) return;
+            const int bits = 64 - __builtin_clzll((unsigned long long)(ve - vb));     // 1 .. 31
+            cls[(bits + 1) / 2].push_back(IvEntry{(int32_t)vb, (int32_t)ve, out});
+        };
+        if (dom >= 0) {
+            const auto f = by_tid.find(dom);
+            if (f != by_tid.end())
+                for (uint32_t i : f->second) put(beg[i], end[i], i);
+        } else {
+            const size_t gi = (size_t)(-2 - (int64_t)dom);
+            if (dom > -2 || gi >= ctx->groups.size())
+                return fail(ctx, MTH_ERR_STATE, "intervals: a batch of the pairs table carries the handle of a contig group that is not defined (any more)");
+            const mth_ctx::ContigGroup &g = ctx->groups[gi];
+            for (size_t k = 0; k < g.tids.size(); ++k) {
+                const auto f = by_tid.find(g.tids[k]);
+                if (f == by_tid.end()) continue;
+                // contig k lies at [voff[k], ...); the next contig's position -1 at voff[k + 1] - 1 is the first word that is not contig k's
+                const int64_t limit = k + 1 < g.tids.size() ? g.voff[k + 1] - 1 : (int64_t)INT32_MAX;
+                for (uint32_t i : f->second) put(g.voff[k] + beg[i], std::min<int64_t>(g.voff[k] + end[i], limit), i);
+            }
+        }
+        const uint32_t first = (uint32_t)s_beg.size();
+        for (auto &v : cls) {
+            if (v.empty()) continue;
+            std::sort(v.begin(), v.end(), [](const IvEntry &x, const IvEntry &y) { return x.start != y.start ? x.start < y.start : x.out < y.out; });
+            s_beg.push_back((int32_t)e_start.size());
+            int32_t mx = 0;
+            for (const IvEntry &e : v) {
+                mx = std::max(mx, e.end);
+                e_start.push_back(e.start); e_end.push_back(e.end); e_maxend.push_back(mx); e_out.push_back(e.out);
+            }
+            s_end.push_back((int32_t)e_start.size());
+        }
+        dom_slices[dom] = {first, (uint32_t)s_beg.size()};
+        return MTH_OK;
+    };
+
+    // ---- the work items: every tile of the table, and the global path's rows of every batch in chunks ----
+    const size_t nb = t.meta.size();
+    std::vector<unsigned long long> b_tile_end(nb), c_row0;
+    std::vector<uint32_t> b_slice(2 * nb), c_n, c_batch;
+    uint64_t rows_end = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        const TileBatch &mb = t.meta[b];
+        if (!dom_slices.count(mb.tid)) {
+            const int rc = add_domain(mb.tid);
+            if (rc) return rc;
+            if (e_start.size() >= (size_t)INT32_MAX) return fail(ctx, MTH_ERR_CAPACITY, "intervals: 2^31 or more interval entries");
+        }
+        const auto sl = dom_slices[mb.tid];
+        b_tile_end[b] = mb.tile_end; b_slice[2 * b] = sl.first; b_slice[2 * b + 1] = sl.second;
+        rows_end += mb.rows;
+        if (sl.first != sl.second)
+            for (uint64_t r = mb.heavy0; r < rows_end; r += IV_CHUNK) {
+                c_row0.push_back(r); c_n.push_back((uint32_t)std::min<uint64_t>(IV_CHUNK, rows_end - r)); c_batch.push_back((uint32_t)b);
+            }
+    }
+    if (c_row0.size() >= (1ull << 32) || nb >= (1ull << 32)) return fail(ctx, MTH_ERR_CAPACITY, "intervals: too many work items");
+    const uint64_t n_tiles = t.tiles(), n_items = n_tiles + c_row0.size();
+
+    MTH_HIP(ctx, ctx->iv_acc.reserve((size_t)n * 16, s));
+    MTH_HIP(ctx, hipMemsetAsync(ctx->iv_acc.p, 0, (size_t)n * 16, s));
+    std::vector<unsigned long long> tab;                  // everything the kernel reads besides the table, as one upload (8-byte words first)
+    if (!e_start.empty() && n_items && t.rows) {
+        size_t off_w = 0;
+        auto place = [&](const void *src, size_t bytes) {
+            const size_t at = off_w;
+            const size_t words = (bytes + 7) / 8;
+            tab.resize(off_w + words);
+            if (bytes) memcpy(tab.data() + at, src, bytes);
+            off_w += words;
+            return at;
+        };
+        const size_t o_bte = place(b_tile_end.data(), nb * 8), o_cr0 = place(c_row0.data(), c_row0.size() * 8);
+        const size_t o_bsl = place(b_slice.data(), b_slice.size() * 4), o_cn = place(c_n.data(), c_n.size() * 4), o_cb = place(c_batch.data(), c_batch.size() * 4);
+        const size_t o_sb = place(s_beg.data(), s_beg.size() * 4), o_se = place(s_end.data(), s_end.size() * 4);
+        const size_t o_es = place(e_start.data(), e_start.size() * 4), o_ee = place(e_end.data(), e_end.size() * 4);
+        const size_t o_em = place(e_maxend.data(), e_maxend.size() * 4), o_eo = place(e_out.data(), e_out.size() * 4);
+        MTH_HIP(ctx, ctx->iv_tab.reserve(tab.size() * 8, s));
+        MTH_HIP(ctx, hipMemcpyAsync(ctx->iv_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+        const unsigned long long *base = ctx->iv_tab.as<unsigned long long>();
+        IvArgs a;
+        a.key = ctx->p_out_key.as<unsigned long long>(); a.cnt = ctx->p_out_cnt.as<uint2>();
+        a.tile_row0 = t.tile_row0.as<unsigned long long>(); a.tile_rows = t.tile_rows.as<uint32_t>();
+        a.b_tile_end = base + o_bte; a.c_row0 = base + o_cr0;
+        a.b_slice = reinterpret_cast<const uint32_t *>(base + o_bsl);
+        a.c_n = reinterpret_cast<const uint32_t *>(base + o_cn); a.c_batch = reinterpret_cast<const uint32_t *>(base + o_cb);
+        a.s_beg = reinterpret_cast<const int32_t *>(base + o_sb); a.s_end = reinterpret_cast<const int32_t *>(base + o_se);
+        a.e_start = reinterpret_cast<const int32_t *>(base + o_es); a.e_end = reinterpret_cast<const int32_t *>(base + o_ee);
+        a.e_maxend = reinterpret_cast<const int32_t *>(base + o_em); a.e_out = reinterpret_cast<const uint32_t *>(base + o_eo);
+        a.acc = ctx->iv_acc.as<unsigned long long>();
+        a.n_tiles = n_tiles; a.n_chunks = (uint32_t)c_row0.size(); a.n_batches = (uint32_t)nb;
+        LaunchTimer lt(ctx, K_PAIRS_INTERVALS);
+        hipLaunchKernelGGL(k_pairs_intervals, dim3((uint32_t)std::min<uint64_t>(n_items, 4096)), dim3(IV_B), 0, s, a);
+    }
+    MTH_HIP(ctx, hipGetLastError());
+    std::vector<unsigned long long> acc((size_t)n * 2);
+    MTH_HIP(ctx, hipMemcpyAsync(acc.data(), ctx->iv_acc.p, (size_t)n * 16, hipMemcpyDeviceToHost, s));
+    const int rc = sync_and_check(ctx);                   // the call's one synchronisation (tab and acc are locals)
+    if (rc) return rc;
+    for (uint64_t i = 0; i < n; ++i) { n_concordant[i] = (int64_t)acc[2 * i]; n_discordant[i] = (int64_t)acc[2 * i + 1]; }
+    return MTH_OK;
+}
+
+}  // extern "C"
