@@ -294,6 +294,43 @@ int  mth_mhl_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_mhl_
  * coverage = number of reads of the segment the value comes from */
 int  mth_mhl_fetch(mth_ctx_t *ctx, uint64_t *n_rows, int32_t *tid, int32_t *pos, float *mhl, uint32_t *coverage);
 
+/* ---- MHL per interval (`mhl-regions`; mhl.rs:43-73, 176-183, readutil.rs:87-94, 147-164) -------------------------------
+ * MHL of a REGION: one value per interval [beg, end) of contig tid, from every read taken once.  Per record: BismarkRead
+ * (readutil.rs:24-53); the calls with beg <= abspos < end are kept -- filter_isin (readutil.rs:87-94) with the set "every position
+ * of the interval", a call at position -1 lies in no interval --; with n calls kept the read contributes if mapq >= min_qual and
+ * n >= max(min_cpgs, 1) (mhl.rs:176-183, applied after the filter as the reference applies them); a contributing read adds n to the
+ * interval's num_cpgs and its get_stretch_info() (readutil.rs:147-164) to the interval's stretch_info (mhl.rs:75-80, 36-41: one
+ * AssociatedReads per interval instead of one per CpG); the value is compute_mhl() (mhl.rs:43-73) of it, NaN below
+ * max(min_depth, 1) contributing reads.  No flush and no re-open: the value does not depend on the record order or on how the
+ * reads are split over batches and contexts.
+ * Two histograms per interval carry it: runs[r], maximal methylated runs of length r, and reads[n], contributing reads with n
+ * kept calls.  The device counts them as integers; the finaliser derives stretch_info[l] = sum_{r >= l} runs[r] (r - l + 1) and the
+ * denominator of l = sum_{n >= l} reads[n] (n - l + 1) as exact 64-bit integers, converts each to f32 ONCE and then follows
+ * compute_mhl's arithmetic (terms in ascending l, running f32 l_sum, no contraction).  The reference adds its denominator in f32
+ * read by read: the same bits whenever the interval's sum of n is below 2^24; beyond that the reference's value depends on the
+ * record order and this definition takes over.
+ *   begin       declares the n intervals (host arrays, copied; 0-based, half-open, 0 <= beg <= end; any order, overlap, nesting
+ *               and duplicates; fewer than 2^31) and clears the sums.  mth_reset clears the sums and keeps the intervals.
+ *   accumulate  one batch (host, device-resident or prepared; a contig or a contig group, whose intervals are shifted by their
+ *               contig's voff).  Only the reads the batch OWNS count (region_beg <= read_start < region_end): with several
+ *               batches or contexts over one contig every read is owned once.  min_depth is not used here.  Synchronous: data
+ *               errors are the return value; a read with more than 16384 kept calls in an interval is MTH_ERR_CAPACITY, a batch
+ *               that carries the word of position -1 MTH_ERR_RANGE.  The calls of a read lie between its first and its last one.
+ *   counts      the histograms as sparse rows sorted by (interval, length): *n_rows always set, arrays may be NULL.  Several
+ *               contexts (shards): add their rows and finalise once.
+ *   finalise    host only, no context: the value of ONE interval from its k rows of ascending length; *n_reads = contributing
+ *               reads, *max_cpgs = the largest n among them (0 when there are none); either may be NULL.
+ *   fetch       finalise of every declared interval, in the caller's order; arrays of n, any may be NULL.
+ *   stats       out[4] = overflow-list entries so far (lengths above the dense rows' 64), batches run a second time because
+ *               the list was too short, batches, reads of those batches. */
+int  mth_mhl_regions_begin(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, const int32_t *beg, const int32_t *end);
+int  mth_mhl_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_mhl_params_t *params);
+int  mth_mhl_regions_counts(mth_ctx_t *ctx, uint64_t *n_rows, uint32_t *interval, uint32_t *length, uint64_t *runs, uint64_t *reads);
+float mth_mhl_regions_finalise(uint64_t k, const uint32_t *length, const uint64_t *runs, const uint64_t *reads, uint32_t min_depth,
+                               uint64_t *n_reads, uint32_t *max_cpgs);
+int  mth_mhl_regions_fetch(mth_ctx_t *ctx, uint32_t min_depth, float *mhl, uint64_t *n_reads, uint32_t *max_cpgs);
+int  mth_mhl_regions_stats(mth_ctx_t *ctx, uint64_t out[4]);
+
 /* ---- FDRP and qFDRP (fdrp.rs:176-246, qfdrp.rs:188-258): both from one pass ---------------------
  * Exact stream semantics (strict '<' flush by reads passing mapq with >= 1 CpG, +-201-bp window
  * drop, fill to max_depth in file order).  Beyond max_depth the reference replaces stored reads at

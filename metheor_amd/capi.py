@@ -16,6 +16,7 @@ SYMBOLS = [
     "mth_pdr_fetch", "mth_result_buffer_alloc", "mth_result_buffer_free", "mth_pdr_device_view", "mth_lpmd_global", "mth_lpmd_add_unbatched", "mth_lpmd_from_counts",
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch", "mth_lpmd_intervals_fetch",
+    "mth_mhl_regions_begin", "mth_mhl_regions_accumulate", "mth_mhl_regions_counts", "mth_mhl_regions_finalise", "mth_mhl_regions_fetch", "mth_mhl_regions_stats",
     "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome", "mth_decode_set_modtags",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
@@ -189,6 +190,13 @@ def lib():
         L.mth_lpmd_pairs_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_lpmd_pairs_params_t)]
         L.mth_lpmd_pairs_fetch.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 6
         L.mth_lpmd_intervals_fetch.argtypes = [vp, C.c_uint64] + [vp] * 5
+        L.mth_mhl_regions_begin.argtypes = [vp, C.c_uint64] + [vp] * 3
+        L.mth_mhl_regions_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_mhl_params_t)]
+        L.mth_mhl_regions_counts.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 4
+        L.mth_mhl_regions_finalise.restype = C.c_float
+        L.mth_mhl_regions_finalise.argtypes = [C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.mth_mhl_regions_fetch.argtypes = [vp, C.c_uint32] + [vp] * 3
+        L.mth_mhl_regions_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
         L.mth_decode_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_decoded_t)]
         L.mth_decode_set_cpg_filter.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mth_decode_set_xm_min_mapq.argtypes = [vp, C.c_uint32]
@@ -230,6 +238,16 @@ def lib():
         L.mth_timing_kernel_name.restype = C.c_char_p; L.mth_timing_kernel_name.argtypes = [C.c_int]
         _LIB = L
     return _LIB
+
+
+def mhl_regions_finalise(length, runs, reads, min_depth=10):
+    """the host finaliser (mth_regions_host.h) of ONE interval from its sparse histogram rows of ascending length -> (mhl, n_reads,
+    max_cpgs); no context, no device"""
+    ln, ru, re_ = np.ascontiguousarray(length, np.uint32), np.ascontiguousarray(runs, np.uint64), np.ascontiguousarray(reads, np.uint64)
+    assert ln.shape == ru.shape == re_.shape and ln.ndim == 1
+    n, mx = C.c_uint64(0), C.c_uint32(0)
+    v = lib().mth_mhl_regions_finalise(len(ln), *[x.ctypes.data_as(C.c_void_p) for x in (ln, ru, re_)], min_depth, C.byref(n), C.byref(mx))
+    return np.float32(v), int(n.value), int(mx.value)
 
 
 class PdrLpmdParams:
@@ -532,6 +550,48 @@ class Engine:
         out["lpmd"] = np.array([self.L.mth_lpmd_from_counts(int(c), int(d)) for c, d in zip(out["n_concordant"], out["n_discordant"])],
                                np.float32)
         return out
+
+    # ---- MHL per interval (mth_mhl_regions.hip) ----
+    def mhl_regions_begin(self, tid, beg, end):
+        """declare the intervals [beg, end) of contig tid (0-based, half-open; any order, overlap, nesting, duplicates) and clear the sums"""
+        t, b, e = (np.ascontiguousarray(x, np.int32) for x in (tid, beg, end))
+        assert t.ndim == 1 and t.shape == b.shape == e.shape
+        self._mr_n = len(t)
+        self._check(self.L.mth_mhl_regions_begin(self.h, len(t), *[x.ctypes.data_as(C.c_void_p) for x in (t, b, e)]))
+        self._settled()
+
+    def mhl_regions_accumulate(self, batch, min_cpgs=4, min_qual=10):
+        """the batch's OWNED reads (region_beg <= read_start < region_end) into the histograms of every declared interval (mhl.rs:176-183
+        after readutil.rs:87-94 with the interval's positions); synchronous"""
+        p = mth_mhl_params_t(0, min_cpgs, min_qual)
+        self._check(self.L.mth_mhl_regions_accumulate(self.h, C.byref(batch.c), C.byref(p)))
+        self._settled()
+
+    def mhl_regions_counts(self):
+        """the two histograms as sparse rows sorted by (interval, length): runs = maximal methylated runs of that length, reads =
+        contributing reads with that many kept calls.  Shards add these."""
+        n = C.c_uint64(0)
+        self._check(self.L.mth_mhl_regions_counts(self.h, C.byref(n), None, None, None, None))
+        k = n.value
+        out = dict(interval=np.empty(k, np.uint32), length=np.empty(k, np.uint32), runs=np.empty(k, np.uint64), reads=np.empty(k, np.uint64))
+        if k:
+            self._check(self.L.mth_mhl_regions_counts(self.h, C.byref(n), *[out[c].ctypes.data_as(C.c_void_p) for c in ("interval", "length", "runs", "reads")]))
+        self._settled()
+        return out
+
+    def mhl_regions_fetch(self, min_depth=10):
+        """per declared interval: mhl (compute_mhl, mhl.rs:43-73; NaN below max(min_depth, 1) contributing reads), n_reads, max_cpgs"""
+        k = self._mr_n
+        out = dict(mhl=np.empty(k, np.float32), n_reads=np.empty(k, np.uint64), max_cpgs=np.empty(k, np.uint32))
+        self._check(self.L.mth_mhl_regions_fetch(self.h, min_depth, *[out[c].ctypes.data_as(C.c_void_p) for c in ("mhl", "n_reads", "max_cpgs")]))
+        self._settled()
+        return out
+
+    def mhl_regions_stats(self):
+        """overflow-list entries so far, batches run a second time for a list that was too short, batches, reads of those batches"""
+        out = (C.c_uint64 * 4)()
+        self._check(self.L.mth_mhl_regions_stats(self.h, C.byref(out)))
+        return [int(x) for x in out]
 
     # ---- device-side BAM record decode (mth_decode.hip) ----
     def decode_records(self, raw, rec_off, append=False):

@@ -28,6 +28,7 @@
 
 #include "../../../include/metheor_hip.h"
 #include "../../../include/metheor_host.h"
+#include "../mth_regions_host.h"
 
 namespace {
 
@@ -59,6 +60,9 @@ const Opt O_MMTAGS = {"mm-tags", 0, "", "(MI355X extension) Take the methylation
 const Opt O_MMTHR = {"mm-threshold", 0, "MM_THRESHOLD", "(MI355X extension) With the MM / ML tags as the source of calls: a listed C whose ML probability is at least this (0..=255) is methylated", "128", false, 'B'};
 // not in the reference: LPMD per interval of a BED file, reduced on the device from the pairs table
 const Opt O_INTERVALS = {"intervals", 0, "INTERVALS", "(MI355X extension) BED file of intervals: LPMD of each one, as `-c` with all of the interval's positions would give it", nullptr, false, 's'};
+// ... and MHL per interval, counted on the device from the reads; on `all` the BED is shared by the two tables
+const Opt O_INTERVALS_MHL = {"intervals", 0, "INTERVALS", "BED file of intervals: MHL of each one, from the reads' calls inside it, as `-c` with all of the interval's positions would keep them", nullptr, true, 's'};
+const Opt O_INTERVALS_ALL = {"intervals", 0, "INTERVALS", "(MI355X extension) BED file of intervals for --lpmd-intervals and / or --mhl-intervals: each measure restricted to an interval's positions, as `-c` with all of them would", nullptr, false, 's'};
 const Opt O_BAI = {"bai", 'b', "BAI", "(MI355X extension) BAM index for --region [default: <input>.bai]", nullptr, false, 's'};
 
 // lib.rs:24-231
@@ -124,7 +128,15 @@ const std::vector<Cmd> &commands() {
           {"max-depth", 'D', "MAX_DEPTH", "Maximum number of reads to consider", "40", false, 'Z'},
           {"min-overlap", 'l', "MIN_OVERLAP", "Minimum overlap between two reads to consider in bp", "35", false, 'I'},
           O_CPG, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR,
-          O_INTERVALS, {"lpmd-intervals", 0, "LPMD_INTERVALS", "(MI355X extension) Output table of the per-interval LPMD (needs --lpmd and --intervals)", nullptr, false, 's'}}},
+          O_INTERVALS_ALL, {"lpmd-intervals", 0, "LPMD_INTERVALS", "(MI355X extension) Output table of the per-interval LPMD (needs --lpmd and the BED)", nullptr, false, 's'},
+          {"mhl-intervals", 0, "MHL_INTERVALS", "(MI355X extension) Output table of the per-interval MHL, one row per line of the BED (needs the BED; an output of its own, --mhl is not needed)", nullptr, false, 's'}}},
+        // not in the reference: MHL of a region, as Guo et al. (2017) define it, for every interval of a BED file
+        {"mhl-regions", "(MI355X extension) Compute methylation haplotype load (MHL) per interval of a BED file",
+         {O_IN, {"output", 'o', "OUTPUT", "Path to output table: chrom, start, end, name, mhl, n_reads, max_cpgs, one row per line of the BED", nullptr, true, 's'},
+          O_INTERVALS_MHL,
+          {"min-depth", 'd', "MIN_DEPTH", "Minimum number of contributing reads of an interval (fewer: NaN)", "10", false, 'U'},
+          {"min-cpgs", 'p', "MIN_CPGS", "Minimum number of CpGs of a read inside an interval for the read to contribute", "4", false, 'Z'},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"tag", "Add bismark XM tag to BAM file",
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
           {"genome", 'g', "GENOME", "", nullptr, true, 's'},
@@ -138,8 +150,8 @@ const std::vector<Cmd> &commands() {
 
 void print_main_help(FILE *f) {
     fprintf(f, "Summarizes the heterogeneity of DNA methylation states using BAM files.\n\nUsage: metheor <COMMAND>\n\nCommands:\n");
-    for (const Cmd &c : commands()) fprintf(f, "  %-6s %s\n", c.name, c.about);
-    fprintf(f, "  help   Print this message or the help of the given subcommand(s)\n\nOptions:\n"
+    for (const Cmd &c : commands()) fprintf(f, "  %-11s %s\n", c.name, c.about);
+    fprintf(f, "  help        Print this message or the help of the given subcommand(s)\n\nOptions:\n"
                "  -h, --help     Print help\n  -V, --version  Print version\n");
 }
 
@@ -287,7 +299,8 @@ struct Shard {
 thread_local Shard g_shard;
 
 // what one shard contributes to the output files (filled through open_memstream when world > 1)
-struct Part { char *out = nullptr; size_t out_len = 0; char *pairs = nullptr; size_t pairs_len = 0; std::vector<int64_t> iv_c, iv_d; };
+struct Part { char *out = nullptr; size_t out_len = 0; char *pairs = nullptr; size_t pairs_len = 0; std::vector<int64_t> iv_c, iv_d;
+              std::vector<uint32_t> mr_iv, mr_len; std::vector<uint64_t> mr_runs, mr_reads; };
 thread_local Part *g_part = nullptr;
 
 // the shards' threads meet here once: the last to arrive runs the collective for all of them
@@ -1262,10 +1275,11 @@ void lpmd_pairs_write(mth_ctx_t *ctx, const Input &in, const std::string &path) 
 // ---- lpmd --intervals: LPMD per interval of a BED file -------------------------------------------------------
 // Read by main() before any device or output is touched; every shard of a --gpus N run reduces its own rows for all of them.
 struct Intervals {
-    std::string path, out_path;
+    std::string path, out_path, mhl_path;          // out_path: the per-interval LPMD table, mhl_path: the per-interval MHL table
     std::vector<std::string> chrom, name;
     std::vector<int32_t> tid, beg, end;
     bool on() const { return !out_path.empty(); }
+    bool mhl_on() const { return !mhl_path.empty(); }
 } g_intervals;
 
 // BED: tab-separated, chrom start end [name [...]], 0-based half-open; empty lines and '#' / track / browser lines are skipped
@@ -1337,6 +1351,41 @@ void lpmd_intervals_write(mth_ctx_t *ctx) {
     }
     if (g_shard.world > 1) { g_part->iv_c.swap(nc); g_part->iv_d.swap(nd); return; }
     intervals_write(nc, nd);
+}
+
+// ---- mhl-regions: MHL per interval of a BED file ---------------------------------------------------------------
+// chrom, start, end, name, mhl (compute_mhl, mhl.rs:43-73, of the interval's own histograms), n_reads, max_cpgs: one row per BED line.
+// The rows are the sparse histograms (interval, length, runs, reads) sorted by (interval, length): one context's, or the shards' added.
+void mhl_regions_write(const std::vector<uint32_t> &r_iv, const std::vector<uint32_t> &r_len, const std::vector<uint64_t> &r_runs,
+                       const std::vector<uint64_t> &r_reads, uint32_t min_depth) {
+    const Intervals &iv = g_intervals;
+    FILE *f = open_file(iv.mhl_path);
+    fprintf(f, "chrom\tstart\tend\tname\tmhl\tn_reads\tmax_cpgs\n");
+    LineWriter w(f);
+    size_t o = 0;
+    for (size_t i = 0; i < iv.tid.size(); ++i) {
+        const size_t o0 = o;
+        while (o < r_iv.size() && r_iv[o] == (uint32_t)i) ++o;
+        uint64_t n_reads = 0;
+        uint32_t max_cpgs = 0;
+        const float v = mth::mhl_regions_finalise(o - o0, r_len.data() + o0, r_runs.data() + o0, r_reads.data() + o0, min_depth, &n_reads, &max_cpgs);
+        w.str(iv.chrom[i].c_str()); w.ch('\t'); w.i32(iv.beg[i]); w.ch('\t'); w.i32(iv.end[i]); w.ch('\t'); w.str(iv.name[i].c_str()); w.ch('\t');
+        w.f32(v); w.ch('\t'); w.i64((long long)n_reads); w.ch('\t'); w.u32(max_cpgs); w.eol();
+    }
+    w.flush();
+    if (fclose(f) != 0) die("Error writing to output file.");
+}
+
+// the histograms counted on this context (a shard of several: its rows go to main(), which adds the shards' -- a read is owned by the
+// shard that holds its start -- finalises once and writes the file)
+void mhl_regions_finish(mth_ctx_t *ctx, uint32_t min_depth) {
+    uint64_t k = 0;
+    check(ctx, mth_mhl_regions_counts(ctx, &k, nullptr, nullptr, nullptr, nullptr));
+    std::vector<uint32_t> r_iv(k), r_len(k);
+    std::vector<uint64_t> r_runs(k), r_reads(k);
+    check(ctx, mth_mhl_regions_counts(ctx, &k, r_iv.data(), r_len.data(), r_runs.data(), r_reads.data()));
+    if (g_shard.world > 1) { g_part->mr_iv.swap(r_iv); g_part->mr_len.swap(r_len); g_part->mr_runs.swap(r_runs); g_part->mr_reads.swap(r_reads); return; }
+    mhl_regions_write(r_iv, r_len, r_runs, r_reads, min_depth);
 }
 
 // me.rs:68-88 / pm.rs:63-83: one line per quartet with depth >= min_depth,
@@ -1486,6 +1535,28 @@ int run_mhl(const Args &a) {
     return finish(ctx, in.h);
 }
 
+// every read counts once, whatever the order of the records: input that is not coordinate-sorted is routed as lpmd routes it
+int run_mhl_regions(const Args &a) {
+    g_shard.order_free = true;
+    Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
+    mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
+    mth_mhl_params_t p;
+    p.min_depth = (uint32_t)a.n.at("min-depth");
+    p.min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
+    p.min_qual = (uint8_t)a.n.at("min-qual");
+    const Intervals &iv = g_intervals;
+    {
+        Phase ph("H2D + kernels (sync)");
+        check(ctx, mth_mhl_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
+        for (const Contig &c : in.contigs) {
+            const mth_batch_t b = make_batch(in, c);
+            check(ctx, mth_mhl_regions_accumulate(ctx, &b, &p));
+        }
+    }
+    mhl_regions_finish(ctx, p.min_depth);
+    return finish(ctx, in.h);
+}
+
 int run_fdrp(const Args &a, bool quantitative) {
     Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
     mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
@@ -1528,7 +1599,7 @@ int run_fdrp(const Args &a, bool quantitative) {
 int run_all(const Args &a) {
     const std::string input = a.s.at("input");
     const char *cpg_set = a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr;
-    const bool w_pdr = a.has("pdr"), w_lpmd = a.has("lpmd"), w_pairs = a.has("lpmd-pairs"), w_iv = g_intervals.on(), w_mhl = a.has("mhl"), w_me = a.has("me"),
+    const bool w_pdr = a.has("pdr"), w_lpmd = a.has("lpmd"), w_pairs = a.has("lpmd-pairs"), w_iv = g_intervals.on(), w_mr = g_intervals.mhl_on(), w_mhl = a.has("mhl"), w_me = a.has("me"),
                w_pm = a.has("pm"), w_fdrp = a.has("fdrp"), w_qfdrp = a.has("qfdrp");
     const uint32_t min_depth = (uint32_t)a.n.at("min-depth");
     const uint32_t min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
@@ -1537,8 +1608,8 @@ int run_all(const Args &a) {
     if (w_lpmd)   // lpmd.rs:161-164
         fprintf(stderr, "Computing subset-LPMD with parameters input=%s, min_distance=%d, max_distance=%d\n", input.c_str(), mind, maxd);
     const bool any_flush = w_pdr || w_mhl || w_fdrp || w_qfdrp;          // the measures whose result depends on the record order
-    const bool any_free = w_lpmd || w_me || w_pm;
-    g_shard.xm_min_mapq = (any_flush || w_me || w_pm) ? 0 : (int)min_qual;
+    const bool any_free = w_lpmd || w_me || w_pm || w_mr;
+    g_shard.xm_min_mapq = (any_flush || w_me || w_pm || w_mr) ? 0 : (int)min_qual;
     g_shard.order_free = !any_flush;
     Input in = load(input, cpg_set);
     mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
@@ -1601,11 +1672,14 @@ int run_all(const Args &a) {
     }
     {
         Phase ph("H2D + kernels (sync)");
+        const Intervals &iv = g_intervals;
+        if (w_mr) check(ctx, mth_mhl_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
         for (const Contig &c : bin->contigs) {
             const mth_batch_t b = make_batch(*bin, c);
             mth_batch_t pb;
             check(ctx, mth_batch_prepare(ctx, &b, &pb));      // one device copy and one read index for every measure of the batch
-            check(ctx, mth_multi_accumulate(ctx, &pb, &mp));
+            if (mp.want) check(ctx, mth_multi_accumulate(ctx, &pb, &mp));
+            if (w_mr) check(ctx, mth_mhl_regions_accumulate(ctx, &pb, &mp.mhl));      // the per-interval MHL, on the batch as it is prepared
             check(ctx, mth_batch_release(ctx, &pb));
         }
     }
@@ -1613,6 +1687,7 @@ int run_all(const Args &a) {
     if (w_lpmd) lpmd_write(ctx, *bin, input, min_qual, a.s.at("lpmd"));
     if (w_pairs) lpmd_pairs_write(ctx, *bin, a.s.at("lpmd-pairs"));
     if (w_iv) lpmd_intervals_write(ctx);
+    if (w_mr) mhl_regions_finish(ctx, min_depth);
     if (w_me) quartet_write(ctx, *bin, min_depth, true, a.s.at("me"));
     if (w_pm) quartet_write(ctx, *bin, min_depth, false, a.s.at("pm"));
     if (mp.want & MTH_MULTI_MHL) mhl_write(ctx, *bin, a.s.at("mhl"));
@@ -1854,6 +1929,7 @@ int main(int argc, char **argv) {
         if (sub == "pdr") return run_pdr(a);
         if (sub == "lpmd") return run_lpmd(a);
         if (sub == "mhl") return run_mhl(a);
+        if (sub == "mhl-regions") return run_mhl_regions(a);
         if (sub == "fdrp") return run_fdrp(a, false);
         if (sub == "qfdrp") return run_fdrp(a, true);
         if (sub == "me") return run_quartet(a, true);
@@ -1870,16 +1946,19 @@ int main(int argc, char **argv) {
         return run_tag(a);
     }
     if (sub == "all") {      // clap-style: an ArgGroup of the outputs (required, multiple) and `requires` on --lpmd-pairs
-        static const char *outs[] = {"pdr", "lpmd", "mhl", "me", "pm", "fdrp", "qfdrp"};
+        static const char *outs[] = {"pdr", "lpmd", "mhl", "me", "pm", "fdrp", "qfdrp", "mhl-intervals"};
         bool any = false;
         for (const char *o : outs) any |= a.has(o);
         if (!any)
-            usage_error(cmd, "the following required arguments were not provided:\n  <--pdr <PDR>|--lpmd <LPMD>|--mhl <MHL>|--me <ME>|--pm <PM>|--fdrp <FDRP>|--qfdrp <QFDRP>>");
+            usage_error(cmd, "the following required arguments were not provided:\n  <--pdr <PDR>|--lpmd <LPMD>|--mhl <MHL>|--me <ME>|--pm <PM>|--fdrp <FDRP>|--qfdrp <QFDRP>|--mhl-intervals <MHL_INTERVALS>>");
         if (a.has("lpmd-pairs") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
-        // --intervals and --lpmd-intervals come together, and the table is LPMD's
-        if (a.has("intervals") && !a.has("lpmd-intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd-intervals <LPMD_INTERVALS>");
-        if (a.has("lpmd-intervals") && !a.has("intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals <INTERVALS>");
-        if (a.has("intervals") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
+        // the BED comes with at least one of its two tables and each table with the BED; the LPMD table is LPMD's, the MHL table stands alone
+        if (a.has("intervals") && !a.has("lpmd-intervals") && !a.has("mhl-intervals"))
+            usage_error(cmd, "the following required arguments were not provided:\n  <--lpmd-intervals <LPMD_INTERVALS>|--mhl-intervals <MHL_INTERVALS>>");
+        if ((a.has("lpmd-intervals") || a.has("mhl-intervals")) && !a.has("intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals <INTERVALS>");
+        if (a.has("lpmd-intervals") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
+        // a region owns reads by their start: an interval at its left edge would see part of its reads
+        if (a.has("mhl-intervals") && a.has("region")) usage_error(cmd, "the argument '--mhl-intervals <MHL_INTERVALS>' cannot be used with '--region <REGION>'");
     }
     if (sub == "lpmd") {     // `requires`, both ways
         if (a.has("intervals") && !a.has("intervals-output")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals-output <INTERVALS_OUTPUT>");
@@ -1913,7 +1992,12 @@ int main(int argc, char **argv) {
     if (world < 1) usage_error(cmd, "invalid value '0' for '--gpus <GPUS>': at least one GPU");
     if (a.has("intervals")) {    // the BED is read against the input's header before any device or output file is touched
         g_intervals.path = a.s.at("intervals");
-        g_intervals.out_path = a.s.at(sub == "all" ? "lpmd-intervals" : "intervals-output");
+        if (sub == "mhl-regions") g_intervals.mhl_path = a.s.at("output");
+        else if (sub == "lpmd") g_intervals.out_path = a.s.at("intervals-output");
+        else {
+            if (a.has("lpmd-intervals")) g_intervals.out_path = a.s.at("lpmd-intervals");
+            if (a.has("mhl-intervals")) g_intervals.mhl_path = a.s.at("mhl-intervals");
+        }
         mth_host_t *h = nullptr;
         char err[1024];
         if (mth_host_open(a.s.at("input").c_str(), &h, err, sizeof err) != 0) die(err);
@@ -1956,8 +2040,20 @@ int main(int argc, char **argv) {
         }
         if (fclose(f) != 0) die("Error writing to output file.");
     };
-    write_parts(a.s.at("output"), false);
+    if (sub != "mhl-regions") write_parts(a.s.at("output"), false);
     if (sub == "lpmd" && a.has("pairs")) write_parts(a.s.at("pairs"), true);
+    if (g_intervals.mhl_on()) {  // every shard counted its own reads for all the intervals: the histograms add up, the value is finalised once
+        std::map<std::pair<uint32_t, uint32_t>, std::pair<uint64_t, uint64_t>> sum;
+        for (const Part &p : parts)
+            for (size_t i = 0; i < p.mr_iv.size(); ++i) {
+                auto &e = sum[{p.mr_iv[i], p.mr_len[i]}];
+                e.first += p.mr_runs[i]; e.second += p.mr_reads[i];
+            }
+        std::vector<uint32_t> r_iv, r_len;
+        std::vector<uint64_t> r_runs, r_reads;
+        for (const auto &kv : sum) { r_iv.push_back(kv.first.first); r_len.push_back(kv.first.second); r_runs.push_back(kv.second.first); r_reads.push_back(kv.second.second); }
+        mhl_regions_write(r_iv, r_len, r_runs, r_reads, (uint32_t)a.n.at("min-depth"));
+    }
     if (g_intervals.on()) {      // every shard reduced its own rows for all the intervals: the sums add up
         const size_t n = g_intervals.tid.size();
         std::vector<int64_t> nc(n, 0), nd(n, 0);

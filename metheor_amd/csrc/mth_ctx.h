@@ -45,7 +45,7 @@ struct PdrLane {
 }  // namespace mth
 
 struct mth_ctx;
-namespace mth { struct FusedQuartet; }
+namespace mth { struct FusedQuartet; struct MhlRegions; }
 
 namespace mth {
 // ---- the tile-row table of a tile-kernel measure (ME / PM, LPMD pairs; driver: mth_tile_rows.hip) ----
@@ -261,6 +261,8 @@ struct mth_ctx {
     mth::DevBuf p_keys, p_cnt, p_out_key, p_out_cnt, p_batch_rows;
     // LPMD per interval (mth_intervals.hip): the sorted intervals + work items of the call in flight, the per-interval sums
     mth::DevBuf iv_tab, iv_acc;
+    // MHL per interval (mth_mhl_regions.hip): the declared intervals, their sorted slices, the histograms (nullptr until the first begin)
+    mth::MhlRegions *mhl_regions = nullptr;
 
     // multi-GPU exchange step (mth_rccl.hip): communicator of the one-process-per-GPU form; lpmd_reduced = DevState.lpmd
     // already holds the all-reduced totals (cleared by the next batch that adds to them)
@@ -346,6 +348,9 @@ int deflate_core(mth_ctx *ctx, const uint8_t *d_src, const uint64_t *h_cut, uint
 int bai_window(mth_ctx *ctx, const uint8_t *d_raw, const unsigned long long *d_off, uint32_t n, const unsigned long long *d_cut,
                const unsigned long long *d_coff, unsigned long long coff_base, uint32_t n_blocks);
 void bai_release(mth_ctx *ctx);
+// mth_mhl_regions.hip: the per-interval MHL state's buffers (mth_ctx_destroy); its sums cleared, the intervals kept (mth_reset)
+void mhl_regions_release(mth_ctx *ctx);
+int mhl_regions_clear(mth_ctx *ctx);
 struct DecArgs;
 // mth_decode_genome.hip: the two passes of the decode with the calls derived from the genome (k_decode_genome); `a` as decode_core
 // fills it for k_decode<false>.  count: ncpg / tid / start / end / mapq / fwd; fill: cpg_pos / cpg_rel at a.cpg_off

@@ -21,9 +21,10 @@
 // Rows that can touch more than IV_ACC intervals of a class (windows nested thousands deep) add to memory directly: slower, never
 // a capacity error.
 #include <algorithm>
-#include <unordered_map>
 
 #include "mth_ctx.h"
+#include "mth_intervals_dev.h"
+#include "mth_regions_host.h"
 
 namespace mth {
 
@@ -48,32 +49,6 @@ struct IvArgs {
     unsigned long long n_tiles;
     uint32_t n_chunks, n_batches;
 };
-
-// first index in [lo, hi) whose value is > v
-__device__ __forceinline__ int32_t iv_upper(const int32_t *__restrict__ a, int32_t lo, int32_t hi, int32_t v) {
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// The same for a value the whole wave shares, called where every lane of the wave is active (block-uniform code): 64 probes a round,
-// so a slice of 10^5 intervals takes three dependent loads instead of seventeen.  The work items are small (a tile's rows) and these
-// searches are what each of them waits for.
-__device__ __forceinline__ int32_t iv_upper_wave(const int32_t *__restrict__ a, int32_t lo, int32_t hi, int32_t v, int lane) {
-    while (hi - lo > 64) {
-        const int32_t step = (hi - lo + 63) >> 6;
-        const long long last = (long long)hi - 1;
-        const int32_t idx = (int32_t)min((long long)lo + (long long)(lane + 1) * step - 1, last);   // ascending over the lanes; lane 63 probes hi - 1
-        const int k = __popcll(__ballot(a[idx] <= v));                        // a is sorted: the probes <= v are the first k
-        if (k == 64) return hi;
-        hi = (int32_t)min((long long)lo + (long long)(k + 1) * step - 1, last);   // the first probe > v: the answer is at or before it
-        if (k) lo = lo + k * step;                                            // the last probe <= v (never the clamped one): the answer is behind it
-    }
-    const int32_t idx = lo + lane;
-    return lo + __popcll(__ballot(idx < hi && a[idx] <= v));
-}
 
 __global__ __launch_bounds__(IV_B) void k_pairs_intervals(const IvArgs a) {
     __shared__ int32_t s_start[IV_LDS];
@@ -164,9 +139,6 @@ __global__ __launch_bounds__(IV_B) void k_pairs_intervals(const IvArgs a) {
     }
 }
 
-// an interval as the rows of one domain see it
-struct IvEntry { int32_t start, end; uint32_t out; };
-
 }  // namespace mth
 
 using namespace mth;
@@ -185,51 +157,18 @@ int mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, con
     const TileRowTable &t = ctx->pairs;
     hipStream_t s = ctx->stream;
 
-    // ---- the intervals per domain and length class, sorted by start ----
-    std::unordered_map<int32_t, std::vector<uint32_t>> by_tid;
-    for (uint64_t i = 0; i < n; ++i)
-        if (beg[i] < end[i]) by_tid[tid[i]].push_back((uint32_t)i);
-    std::vector<int32_t> s_beg, s_end, e_start, e_end, e_maxend;
-    std::vector<uint32_t> e_out;
-    std::unordered_map<int32_t, std::pair<uint32_t, uint32_t>> dom_slices;     // a batch tid -> its slices
+    // ---- the intervals per domain and length class, sorted by start (mth_regions_host.h) ----
+    IvDomains dm(n, tid, beg, end);
+    const std::vector<int32_t> &s_beg = dm.s_beg, &s_end = dm.s_end, &e_start = dm.e_start, &e_end = dm.e_end, &e_maxend = dm.e_maxend;
+    const std::vector<uint32_t> &e_out = dm.e_out;
+    auto &dom_slices = dm.dom_slices;
     auto add_domain = [&](int32_t dom) -> int {
-        constexpr int NCLS = 17;
-        std::vector<IvEntry> cls[NCLS];
-        auto put = [&](int64_t vb, int64_t ve, uint32_t out) {
-            if (vb >= ve) return;
-            const int bits = 64 - __builtin_clzll((unsigned long long)(ve - vb));     // 1 .. 31
-            cls[(bits + 1) / 2].push_back(IvEntry{(int32_t)vb, (int32_t)ve, out});
-        };
-        if (dom >= 0) {
-            const auto f = by_tid.find(dom);
-            if (f != by_tid.end())
-                for (uint32_t i : f->second) put(beg[i], end[i], i);
-        } else {
-            const size_t gi = (size_t)(-2 - (int64_t)dom);
-            if (dom > -2 || gi >= ctx->groups.size())
-                return fail(ctx, MTH_ERR_STATE, "intervals: a batch of the pairs table carries the handle of a contig group that is not defined (any more)");
-            const mth_ctx::ContigGroup &g = ctx->groups[gi];
-            for (size_t k = 0; k < g.tids.size(); ++k) {
-                const auto f = by_tid.find(g.tids[k]);
-                if (f == by_tid.end()) continue;
-                // contig k lies at [voff[k], ...); the next contig's position -1 at voff[k + 1] - 1 is the first word that is not contig k's
-                const int64_t limit = k + 1 < g.tids.size() ? g.voff[k + 1] - 1 : (int64_t)INT32_MAX;
-                for (uint32_t i : f->second) put(g.voff[k] + beg[i], std::min<int64_t>(g.voff[k] + end[i], limit), i);
-            }
-        }
-        const uint32_t first = (uint32_t)s_beg.size();
-        for (auto &v : cls) {
-            if (v.empty()) continue;
-            std::sort(v.begin(), v.end(), [](const IvEntry &x, const IvEntry &y) { return x.start != y.start ? x.start < y.start : x.out < y.out; });
-            s_beg.push_back((int32_t)e_start.size());
-            int32_t mx = 0;
-            for (const IvEntry &e : v) {
-                mx = std::max(mx, e.end);
-                e_start.push_back(e.start); e_end.push_back(e.end); e_maxend.push_back(mx); e_out.push_back(e.out);
-            }
-            s_end.push_back((int32_t)e_start.size());
-        }
-        dom_slices[dom] = {first, (uint32_t)s_beg.size()};
+        if (dom >= 0) { dm.add_domain(dom); return MTH_OK; }
+        const size_t gi = (size_t)(-2 - (int64_t)dom);
+        if (dom > -2 || gi >= ctx->groups.size())
+            return fail(ctx, MTH_ERR_STATE, "intervals: a batch of the pairs table carries the handle of a contig group that is not defined (any more)");
+        const mth_ctx::ContigGroup &g = ctx->groups[gi];
+        dm.add_domain(dom, g.tids.size(), g.tids.data(), g.voff.data());
         return MTH_OK;
     };
 

@@ -62,6 +62,17 @@ inline MhlKnobs mhl_knobs_from_env() {
     return kn;
 }
 
+// ---- MHL per interval (mth_mhl_regions.hip) ----
+// lengths a dense per-interval row holds (kept calls of a read, methylated runs): 64 covers short reads on 1 kbp windows; longer ones
+// take the overflow list
+constexpr int MHL_REGIONS_BINS = 64;
+// MTH_MHL_REGIONS_LIST (tests: force the second run of a batch): the overflow list's first size in entries, at least 1
+inline unsigned long long mhl_regions_list_knob() {
+    const char *e = getenv("MTH_MHL_REGIONS_LIST");
+    const unsigned long long k = e ? strtoull(e, nullptr, 10) : 0;
+    return k ? k : (1ull << 16);
+}
+
 // ---- the tile-row measures (ME / PM: MTH_QUARTET_*, LPMD pairs: MTH_PAIRS_*): each read per call, where it is used ----
 inline const char *tile_rows_knob(const char *prefix, const char *suffix) {
     char name[48];

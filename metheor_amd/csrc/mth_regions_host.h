@@ -1,0 +1,120 @@
+// mth_regions_host.h -- the host-only pieces of the per-interval measures (`lpmd --intervals`, `mhl-regions`): the intervals of a BED
+// file as one batch's domain sees them, and the finaliser of MHL per interval.  Plain C++, nothing of HIP, no environment: the library
+// (mth_intervals.hip, mth_mhl_regions.hip) and the command line share this one copy, and it is tested without a device.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+namespace mth {
+
+// ---- interval domains ----------------------------------------------------------------------------------------------------------------
+// A batch's tid names its domain: a contig, or a contig group whose contig k lies at [voff[k], ...) of one virtual coordinate space.
+// Per domain the intervals are split into length classes (two bit lengths per class: lengths within a factor 4) and each class is
+// sorted by start with a running maximum of the ends -- a SLICE.  A pass finds the last entry of a slice with start <= x by search
+// and walks back while the running maximum is still beyond what it looks for: an entry k steps back starts at least k / depth
+// interval lengths earlier, so a walk passes at most ~4x the intervals that hold its target, whatever other lengths the BED mixes in
+// (a chromosome-long interval sits in a class of its own and costs one step).
+struct IvEntry { int32_t start, end; uint32_t out; };
+
+struct IvDomains {
+    static constexpr int NCLS = 17;
+    const int32_t *tid, *beg, *end;                // the caller's intervals (not owned)
+    std::unordered_map<int32_t, std::vector<uint32_t>> by_tid;
+    std::vector<int32_t> s_beg, s_end;             // per slice: its entries [s_beg, s_end)
+    std::vector<int32_t> e_start, e_end, e_maxend; // per entry, sorted by start within its slice; maxend: running maximum of e_end
+    std::vector<uint32_t> e_out;                   // the interval (caller's index) the entry belongs to
+    std::unordered_map<int32_t, std::pair<uint32_t, uint32_t>> dom_slices;     // a batch tid -> its slices [first, second)
+
+    IvDomains(uint64_t n, const int32_t *tid_, const int32_t *beg_, const int32_t *end_) : tid(tid_), beg(beg_), end(end_) {
+        for (uint64_t i = 0; i < n; ++i)
+            if (beg[i] < end[i]) by_tid[tid[i]].push_back((uint32_t)i);       // an empty interval holds nothing
+    }
+    bool has(int32_t dom) const { return dom_slices.count(dom) != 0; }
+    size_t entries() const { return e_start.size(); }
+
+    // the slices of a domain: a contig (n_contigs == 0: `dom` is its tid), or a group of n_contigs contigs (tids, voff ascending).  A
+    // group shifts an interval by its contig's voff and cuts it at the word before the next contig: contig k + 1's position -1 lies
+    // at voff[k + 1] - 1 and is the first word that is not contig k's.
+    void add_domain(int32_t dom, size_t n_contigs = 0, const int32_t *g_tids = nullptr, const int64_t *g_voff = nullptr) {
+        std::vector<IvEntry> cls[NCLS];
+        auto put = [&](int64_t vb, int64_t ve, uint32_t out) {
+            if (vb >= ve) return;
+            const int bits = 64 - __builtin_clzll((unsigned long long)(ve - vb));     // 1 .. 31
+            cls[(bits + 1) / 2].push_back(IvEntry{(int32_t)vb, (int32_t)ve, out});
+        };
+        if (n_contigs == 0) {
+            const auto f = by_tid.find(dom);
+            if (f != by_tid.end())
+                for (uint32_t i : f->second) put(beg[i], end[i], i);
+        } else {
+            for (size_t k = 0; k < n_contigs; ++k) {
+                const auto f = by_tid.find(g_tids[k]);
+                if (f == by_tid.end()) continue;
+                const int64_t limit = k + 1 < n_contigs ? g_voff[k + 1] - 1 : (int64_t)INT32_MAX;
+                for (uint32_t i : f->second) put(g_voff[k] + beg[i], std::min<int64_t>(g_voff[k] + end[i], limit), i);
+            }
+        }
+        const uint32_t first = (uint32_t)s_beg.size();
+        for (auto &v : cls) {
+            if (v.empty()) continue;
+            std::sort(v.begin(), v.end(), [](const IvEntry &x, const IvEntry &y) { return x.start != y.start ? x.start < y.start : x.out < y.out; });
+            s_beg.push_back((int32_t)e_start.size());
+            int32_t mx = 0;
+            for (const IvEntry &e : v) {
+                mx = std::max(mx, e.end);
+                e_start.push_back(e.start); e_end.push_back(e.end); e_maxend.push_back(mx); e_out.push_back(e.out);
+            }
+            s_end.push_back((int32_t)e_start.size());
+        }
+        dom_slices[dom] = {first, (uint32_t)s_beg.size()};
+    }
+};
+
+// ---- MHL per interval: the finaliser --------------------------------------------------------------------------------------------------
+// compute_mhl (mhl.rs:43-73) of the AssociatedReads an interval collects (mhl.rs:75-80 add_num_cpgs, mhl.rs:36-41 add_stretch_info with
+// readutil.rs:147-164 get_stretch_info), from the interval's two histograms, given as k sparse rows of ascending, distinct length:
+//   runs[i]  = R[length[i]]: maximal methylated runs of that length among the kept calls of the contributing reads
+//   reads[i] = C[length[i]]: contributing reads with that many kept calls
+// stretch_info[l] = sum over r >= l of R[r] (r - l + 1), the denominator of l = sum over n >= l of C[n] (n - l + 1), max_num_cpgs = the
+// largest n with C[n] > 0.  Terms in ascending l, l_sum as the running f32 sum, every operation a single f32 one (no a * b + c to
+// contract), as the per-CpG MHL does it (mth_sites.hip).  Both sums are exact 64-bit integers converted to f32 once: the same bits as
+// the reference's read-by-read f32 denominator whenever the interval's sum of n is below 2^24 (beyond that the reference's own value
+// depends on the record order).  Fewer than max(min_depth, 1) contributing reads: NaN.
+inline float mhl_regions_finalise(size_t k, const uint32_t *length, const uint64_t *runs, const uint64_t *reads, uint32_t min_depth,
+                                  uint64_t *n_reads_out, uint32_t *max_cpgs_out) {
+    uint64_t n_reads = 0;
+    uint32_t maxn = 0, maxr = 0;
+    for (size_t i = 0; i < k; ++i) {
+        if (reads[i]) { n_reads += reads[i]; maxn = std::max(maxn, length[i]); }
+        if (runs[i]) maxr = std::max(maxr, length[i]);
+    }
+    if (n_reads_out) *n_reads_out = n_reads;
+    if (max_cpgs_out) *max_cpgs_out = maxn;
+    if (n_reads < std::max<uint64_t>(min_depth, 1)) return std::nanf("");
+    // suffix sums twice, from the longest length down: cnt = entries of length >= l, sum = their (length - l + 1) added up
+    const uint32_t top = std::max(maxn, maxr);
+    std::vector<uint64_t> S((size_t)top + 2, 0), D((size_t)top + 2, 0);
+    {
+        uint64_t cr = 0, sr = 0, cn = 0, sn = 0;
+        size_t i = k;
+        for (uint32_t l = top; l >= 1; --l) {
+            while (i > 0 && length[i - 1] >= l) { --i; cr += runs[i]; cn += reads[i]; }
+            sr += cr; sn += cn;
+            S[l] = sr; D[l] = sn;
+        }
+    }
+    float l_sum = 0.0f;
+    for (uint32_t l = 1; l < maxn + 1; ++l) l_sum = l_sum + (float)l;
+    float mhl = 0.0f;
+    for (uint32_t l = 1; l <= top; ++l)
+        if (S[l] > 0) { const float t = ((float)l * (float)S[l]) / (float)D[l]; mhl = mhl + t; }
+    return mhl / l_sum;
+}
+
+}  // namespace mth
