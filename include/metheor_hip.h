@@ -331,6 +331,37 @@ float mth_mhl_regions_finalise(uint64_t k, const uint32_t *length, const uint64_
 int  mth_mhl_regions_fetch(mth_ctx_t *ctx, uint32_t min_depth, float *mhl, uint64_t *n_reads, uint32_t *max_cpgs);
 int  mth_mhl_regions_stats(mth_ctx_t *ctx, uint64_t out[4]);
 
+/* ---- PDR per interval (`pdr-regions`; pdr.rs:47-49, 147-157, readutil.rs:87-94, 134-145) -------------------------------
+ * The proportion of discordant reads of a REGION: one value per interval [beg, end) of contig tid, from every read taken once.
+ * Per record: BismarkRead (readutil.rs:24-53); the calls with beg <= abspos < end are kept -- filter_isin (readutil.rs:87-94)
+ * with the set "every position of the interval", a call at position -1 lies in no interval --; with n calls kept the read
+ * contributes if mapq >= min_qual and n >= max(min_cpgs, 1) (pdr.rs:147-157, applied after the filter as the reference applies
+ * them); a contributing read is methylated (every kept call is Z), unmethylated (none is) or discordant (anything else):
+ * get_concordance_state() (readutil.rs:134-145) of the kept calls.  n_concordant = methylated + unmethylated; the value is
+ * n_discordant as f32 / (n_concordant as f32 + n_discordant as f32) (pdr.rs:47-49), NaN below max(min_depth, 1) contributing
+ * reads.  No flush: the counts do not depend on the record order or on how the reads are split over batches and contexts.
+ * The counters are 64-bit integers, each converted to f32 once: the reference's bits whenever the counts fit its u32.
+ *   begin       declares the n intervals (host arrays, copied; 0-based, half-open, 0 <= beg <= end; any order, overlap, nesting
+ *               and duplicates; fewer than 2^31) and clears the sums.  mth_reset clears the sums and keeps the intervals.
+ *   accumulate  one batch (host, device-resident or prepared; a contig or a contig group, whose intervals are shifted by their
+ *               contig's voff).  Only the reads the batch OWNS count (region_beg <= read_start < region_end): with several
+ *               batches or contexts over one contig every read is owned once.  params: min_cpgs and min_qual; min_depth is not
+ *               used here.  NOT synchronous: the pass is queued on the context's stream and the call returns; a device-resident
+ *               batch's arrays stay untouched until the next counts / fetch (or any call that waits for the stream).  Data
+ *               errors -- a batch that carries the word of position -1: MTH_ERR_RANGE -- are the return value of that call.
+ *   counts      per interval, in the caller's order: contributing reads that are methylated, unmethylated, discordant (pdr.rs:185-
+ *               193's two counters, the concordant one split).  Dense arrays of n; any may be NULL.  Several contexts (shards):
+ *               add their arrays and finalise once.
+ *   finalise    host only, no context: pdr.rs:47-49 of ONE interval's counters, NaN when n_concordant + n_discordant is below
+ *               max(min_depth, 1).
+ *   fetch       finalise of every declared interval, in the caller's order; n_methylated: the methylated among the concordant
+ *               reads.  Arrays of n, any may be NULL.  Another min_depth needs no new pass. */
+int  mth_pdr_regions_begin(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, const int32_t *beg, const int32_t *end);
+int  mth_pdr_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_mhl_params_t *params);
+int  mth_pdr_regions_counts(mth_ctx_t *ctx, uint64_t *methylated, uint64_t *unmethylated, uint64_t *discordant);
+float mth_pdr_regions_finalise(uint64_t n_concordant, uint64_t n_discordant, uint32_t min_depth);
+int  mth_pdr_regions_fetch(mth_ctx_t *ctx, uint32_t min_depth, float *pdr, uint64_t *n_concordant, uint64_t *n_discordant, uint64_t *n_methylated);
+
 /* ---- FDRP and qFDRP (fdrp.rs:176-246, qfdrp.rs:188-258): both from one pass ---------------------
  * Exact stream semantics (strict '<' flush by reads passing mapq with >= 1 CpG, +-201-bp window
  * drop, fill to max_depth in file order).  Beyond max_depth the reference replaces stored reads at

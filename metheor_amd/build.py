@@ -17,12 +17,12 @@ ARCH = "gfx950"
 # a*b+c); hipcc's default is contract=fast
 HIP_FLAGS = os.environ.get("MTH_EXTRA_HIPFLAGS", "").split() + ["-O3", "-std=c++17", "-fPIC", "-Wall", "-ffp-contract=off", "-Wno-unused-result"]
 
-HIP_SOURCES = ["mth_api.hip", "mth_pdr_lpmd.hip", "mth_pdr_wide.hip", "mth_quartet.hip", "mth_scan.hip", "mth_sites.hip", "mth_mhl_tile.hip", "mth_fdrp.hip", "mth_fdrp_wtile.hip", "mth_pairs.hip", "mth_intervals.hip", "mth_mhl_regions.hip", "mth_tile_rows.hip", "mth_decode.hip", "mth_decode_genome.hip", "mth_decode_mm.hip", "mth_sort.hip", "mth_fileorder.hip", "mth_inflate.hip", "mth_rccl.hip", "mth_tag.hip", "mth_multi.hip", "mth_fasta.hip", "mth_deflate.hip", "mth_bai.hip"]
+HIP_SOURCES = ["mth_api.hip", "mth_pdr_lpmd.hip", "mth_pdr_wide.hip", "mth_quartet.hip", "mth_scan.hip", "mth_sites.hip", "mth_mhl_tile.hip", "mth_fdrp.hip", "mth_fdrp_wtile.hip", "mth_pairs.hip", "mth_intervals.hip", "mth_mhl_regions.hip", "mth_pdr_regions.hip", "mth_tile_rows.hip", "mth_decode.hip", "mth_decode_genome.hip", "mth_decode_mm.hip", "mth_sort.hip", "mth_fileorder.hip", "mth_inflate.hip", "mth_rccl.hip", "mth_tag.hip", "mth_multi.hip", "mth_fasta.hip", "mth_deflate.hip", "mth_bai.hip"]
 HOST_LIB = os.path.join(HERE, "libmetheor_host.so")
 HOST_SOURCES = [os.path.join("host", "bam_reader.cpp"), os.path.join("host", "host_api.cpp"),
                 os.path.join("host", "parallel_decode.cpp"), os.path.join("host", "synth_bam.cpp"), os.path.join("host", "bai_index.cpp"), os.path.join("host", "sam_text.cpp")]
 HOST_HEADERS = [os.path.join("host", "bam_reader.h"), os.path.join("host", "parallel_decode.h"), os.path.join("host", "bai_internal.h"), os.path.join("host", "sam_text.h"), os.path.join("..", "..", "include", "metheor_host.h")]
-HEADERS = ["mth_common.h", "mth_plan.h", "mth_regions_host.h", "mth_intervals_dev.h", "mth_bgzf_cuts.h", "mth_knobs.h", "mth_ctx.h", "mth_inflate.h", "mth_decode_dev.h", "mth_modtags_dev.h", "mth_tag_dev.h", "mth_quartet_dev.h", "mth_scan.h", "mth_tile_dev.h", "mth_lpmd_bytes.h", "mth_wave_tile.h", os.path.join("..", "..", "include", "metheor_hip.h")]
+HEADERS = ["mth_common.h", "mth_plan.h", "mth_regions_host.h", "mth_intervals_dev.h", "mth_pdr_regions_dev.h", "mth_bgzf_cuts.h", "mth_knobs.h", "mth_ctx.h", "mth_inflate.h", "mth_decode_dev.h", "mth_modtags_dev.h", "mth_tag_dev.h", "mth_quartet_dev.h", "mth_scan.h", "mth_tile_dev.h", "mth_lpmd_bytes.h", "mth_wave_tile.h", os.path.join("..", "..", "include", "metheor_hip.h")]
 
 
 def _hipcc():

@@ -17,6 +17,7 @@ SYMBOLS = [
     "mth_lpmd_export_device", "mth_device_count", "mth_allreduce_lpmd", "mth_rccl_unique_id", "mth_rccl_init_rank",
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch", "mth_lpmd_intervals_fetch",
     "mth_mhl_regions_begin", "mth_mhl_regions_accumulate", "mth_mhl_regions_counts", "mth_mhl_regions_finalise", "mth_mhl_regions_fetch", "mth_mhl_regions_stats",
+    "mth_pdr_regions_begin", "mth_pdr_regions_accumulate", "mth_pdr_regions_counts", "mth_pdr_regions_finalise", "mth_pdr_regions_fetch",
     "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome", "mth_decode_set_modtags",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
@@ -197,6 +198,12 @@ def lib():
         L.mth_mhl_regions_finalise.argtypes = [C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.mth_mhl_regions_fetch.argtypes = [vp, C.c_uint32] + [vp] * 3
         L.mth_mhl_regions_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
+        L.mth_pdr_regions_begin.argtypes = [vp, C.c_uint64] + [vp] * 3
+        L.mth_pdr_regions_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_mhl_params_t)]
+        L.mth_pdr_regions_counts.argtypes = [vp] + [vp] * 3
+        L.mth_pdr_regions_finalise.restype = C.c_float
+        L.mth_pdr_regions_finalise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+        L.mth_pdr_regions_fetch.argtypes = [vp, C.c_uint32] + [vp] * 4
         L.mth_decode_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_decoded_t)]
         L.mth_decode_set_cpg_filter.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mth_decode_set_xm_min_mapq.argtypes = [vp, C.c_uint32]
@@ -248,6 +255,12 @@ def mhl_regions_finalise(length, runs, reads, min_depth=10):
     n, mx = C.c_uint64(0), C.c_uint32(0)
     v = lib().mth_mhl_regions_finalise(len(ln), *[x.ctypes.data_as(C.c_void_p) for x in (ln, ru, re_)], min_depth, C.byref(n), C.byref(mx))
     return np.float32(v), int(n.value), int(mx.value)
+
+
+def pdr_regions_finalise(n_concordant, n_discordant, min_depth=10):
+    """the host finaliser (mth_regions_host.h) of ONE interval's counters: pdr.rs:47-49 as float32, NaN below max(min_depth, 1)
+    contributing reads; no context, no device"""
+    return np.float32(lib().mth_pdr_regions_finalise(int(n_concordant), int(n_discordant), min_depth))
 
 
 class PdrLpmdParams:
@@ -592,6 +605,40 @@ class Engine:
         out = (C.c_uint64 * 4)()
         self._check(self.L.mth_mhl_regions_stats(self.h, C.byref(out)))
         return [int(x) for x in out]
+
+    # ---- PDR per interval (mth_pdr_regions.hip) ----
+    def pdr_regions_begin(self, tid, beg, end):
+        """declare the intervals [beg, end) of contig tid (0-based, half-open; any order, overlap, nesting, duplicates) and clear the sums"""
+        t, b, e = (np.ascontiguousarray(x, np.int32) for x in (tid, beg, end))
+        assert t.ndim == 1 and t.shape == b.shape == e.shape
+        self._pr_n = len(t)
+        self._check(self.L.mth_pdr_regions_begin(self.h, len(t), *[x.ctypes.data_as(C.c_void_p) for x in (t, b, e)]))
+        self._settled()
+
+    def pdr_regions_accumulate(self, batch, min_cpgs=4, min_qual=10):
+        """the batch's OWNED reads (region_beg <= read_start < region_end) into the three counters of every declared interval
+        (pdr.rs:147-157 after readutil.rs:87-94 with the interval's positions, then readutil.rs:134-145); queued, not waited for:
+        data errors surface at the counts / fetch"""
+        p = mth_mhl_params_t(0, min_cpgs, min_qual)
+        self._hold(batch)
+        self._check(self.L.mth_pdr_regions_accumulate(self.h, C.byref(batch.c), C.byref(p)))
+
+    def pdr_regions_counts(self):
+        """per declared interval: contributing reads that are methylated, unmethylated, discordant.  Shards add these."""
+        k = self._pr_n
+        out = dict(methylated=np.empty(k, np.uint64), unmethylated=np.empty(k, np.uint64), discordant=np.empty(k, np.uint64))
+        self._check(self.L.mth_pdr_regions_counts(self.h, *[out[c].ctypes.data_as(C.c_void_p) for c in ("methylated", "unmethylated", "discordant")]))
+        self._settled()
+        return out
+
+    def pdr_regions_fetch(self, min_depth=10):
+        """per declared interval: pdr (pdr.rs:47-49; NaN below max(min_depth, 1) contributing reads), n_concordant, n_discordant,
+        n_methylated (the methylated among the concordant)"""
+        k = self._pr_n
+        out = dict(pdr=np.empty(k, np.float32), n_concordant=np.empty(k, np.uint64), n_discordant=np.empty(k, np.uint64), n_methylated=np.empty(k, np.uint64))
+        self._check(self.L.mth_pdr_regions_fetch(self.h, min_depth, *[out[c].ctypes.data_as(C.c_void_p) for c in ("pdr", "n_concordant", "n_discordant", "n_methylated")]))
+        self._settled()
+        return out
 
     # ---- device-side BAM record decode (mth_decode.hip) ----
     def decode_records(self, raw, rec_off, append=False):

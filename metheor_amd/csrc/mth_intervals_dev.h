@@ -1,5 +1,5 @@
 // mth_intervals_dev.h -- the searches over a slice of sorted intervals (mth_regions_host.h) that the per-interval passes share
-// (mth_intervals.hip, mth_mhl_regions.hip).
+// (mth_intervals.hip, mth_mhl_regions.hip, mth_pdr_regions.hip).
 #pragma once
 #include "mth_common.h"
 

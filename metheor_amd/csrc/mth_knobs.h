@@ -73,6 +73,17 @@ inline unsigned long long mhl_regions_list_knob() {
     return k ? k : (1ull << 16);
 }
 
+// ---- PDR per interval (mth_pdr_regions.hip): read once per context, when it first declares intervals ----
+// entries of a length class a workgroup sums in LDS rows of four 32-bit words (16 KiB); a class with more candidates adds to memory
+constexpr int PDR_REGIONS_LDS_CAP = 1024;
+// MTH_PDR_REGIONS_LDS_CAP (tests: the differential forms): that cap, 0 .. PDR_REGIONS_LDS_CAP; 0: every add goes to memory directly
+inline int pdr_regions_lds_cap_knob() {
+    const char *e = getenv("MTH_PDR_REGIONS_LDS_CAP");
+    return e ? std::min(PDR_REGIONS_LDS_CAP, std::max(0, atoi(e))) : PDR_REGIONS_LDS_CAP;
+}
+// MTH_PDR_REGIONS_SPAN=0 (tests, A/B): no span route -- an interval that holds a workgroup's whole span is counted read by read
+inline bool pdr_regions_span_knob() { const char *e = getenv("MTH_PDR_REGIONS_SPAN"); return !(e && atoi(e) == 0); }
+
 // ---- the tile-row measures (ME / PM: MTH_QUARTET_*, LPMD pairs: MTH_PAIRS_*): each read per call, where it is used ----
 inline const char *tile_rows_knob(const char *prefix, const char *suffix) {
     char name[48];

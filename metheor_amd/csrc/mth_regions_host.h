@@ -1,6 +1,7 @@
-// mth_regions_host.h -- the host-only pieces of the per-interval measures (`lpmd --intervals`, `mhl-regions`): the intervals of a BED
-// file as one batch's domain sees them, and the finaliser of MHL per interval.  Plain C++, nothing of HIP, no environment: the library
-// (mth_intervals.hip, mth_mhl_regions.hip) and the command line share this one copy, and it is tested without a device.
+// mth_regions_host.h -- the host-only pieces of the per-interval measures (`lpmd --intervals`, `mhl-regions`, `pdr-regions`): the intervals of a BED
+// file as one batch's domain sees them, and the finalisers of MHL and of PDR per interval.  Plain C++, nothing of HIP, no environment: the
+// library (mth_intervals.hip, mth_mhl_regions.hip, mth_pdr_regions.hip) and the command line share this one copy, and it is tested
+// without a device.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -115,6 +116,17 @@ inline float mhl_regions_finalise(size_t k, const uint32_t *length, const uint64
     for (uint32_t l = 1; l <= top; ++l)
         if (S[l] > 0) { const float t = ((float)l * (float)S[l]) / (float)D[l]; mhl = mhl + t; }
     return mhl / l_sum;
+}
+
+// ---- PDR per interval: the finaliser --------------------------------------------------------------------------------------------------
+// compute_pdr (pdr.rs:47-49) of the interval's counters: n_concordant = the contributing reads whose kept calls are all methylated or
+// all unmethylated, n_discordant = the others.  Each 64-bit counter is converted to f32 once, then one f32 add and one f32 divide: the
+// reference's bits whenever the counts fit its u32.  Fewer than max(min_depth, 1) contributing reads: NaN.
+inline float pdr_regions_finalise(uint64_t n_concordant, uint64_t n_discordant, uint32_t min_depth) {
+    if (n_concordant + n_discordant < std::max<uint64_t>(min_depth, 1)) return std::nanf("");
+    const float c = (float)n_concordant, d = (float)n_discordant;
+    const float den = c + d;
+    return d / den;
 }
 
 }  // namespace mth
