@@ -1292,6 +1292,19 @@ struct Intervals {
     bool on() const { return !out_path.empty(); }
     bool mhl_on() const { return !mhl_path.empty(); }
     bool pdr_on() const { return !pdr_path.empty(); }
+    // one of the three tables, a row per BED line: chrom, start, end, name, then the measure's own columns (`header`; row(w, i) writes them)
+    template <class Row>
+    void table(const std::string &table_path, const char *header, Row &&row) const {
+        FILE *f = open_file(table_path);
+        fprintf(f, "chrom\tstart\tend\tname\t%s\n", header);
+        LineWriter w(f);
+        for (size_t i = 0; i < tid.size(); ++i) {
+            w.str(chrom[i].c_str()); w.ch('\t'); w.i32(beg[i]); w.ch('\t'); w.i32(end[i]); w.ch('\t'); w.str(name[i].c_str()); w.ch('\t');
+            row(w, i); w.eol();
+        }
+        w.flush();
+        if (fclose(f) != 0) die("Error writing to output file.");
+    }
 } g_intervals;
 
 // BED: tab-separated, chrom start end [name [...]], 0-based half-open; empty lines and '#' / track / browser lines are skipped
@@ -1337,18 +1350,11 @@ void intervals_read(const mth_host_t *h) {
     }
 }
 
-// chrom, start, end, name, lpmd (lpmd.rs:51-55 over the interval's own counters), n_concordant, n_discordant: one row per BED line
+// lpmd (lpmd.rs:51-55 over the interval's own counters), n_concordant, n_discordant
 void intervals_write(const std::vector<int64_t> &nc, const std::vector<int64_t> &nd) {
-    const Intervals &iv = g_intervals;
-    FILE *f = open_file(iv.out_path);
-    fprintf(f, "chrom\tstart\tend\tname\tlpmd\tn_concordant\tn_discordant\n");
-    LineWriter w(f);
-    for (size_t i = 0; i < iv.tid.size(); ++i) {
-        w.str(iv.chrom[i].c_str()); w.ch('\t'); w.i32(iv.beg[i]); w.ch('\t'); w.i32(iv.end[i]); w.ch('\t'); w.str(iv.name[i].c_str()); w.ch('\t');
-        w.f32(mth_lpmd_from_counts(nc[i], nd[i])); w.ch('\t'); w.i64(nc[i]); w.ch('\t'); w.i64(nd[i]); w.eol();
-    }
-    w.flush();
-    if (fclose(f) != 0) die("Error writing to output file.");
+    g_intervals.table(g_intervals.out_path, "lpmd\tn_concordant\tn_discordant", [&](LineWriter &w, size_t i) {
+        w.f32(mth_lpmd_from_counts(nc[i], nd[i])); w.ch('\t'); w.i64(nc[i]); w.ch('\t'); w.i64(nd[i]);
+    });
 }
 
 // the pairs table accumulated on this context, reduced by interval on the device (a shard of several: its sums go to main(), which
@@ -1366,26 +1372,19 @@ void lpmd_intervals_write(mth_ctx_t *ctx) {
 }
 
 // ---- mhl-regions: MHL per interval of a BED file ---------------------------------------------------------------
-// chrom, start, end, name, mhl (compute_mhl, mhl.rs:43-73, of the interval's own histograms), n_reads, max_cpgs: one row per BED line.
+// mhl (compute_mhl, mhl.rs:43-73, of the interval's own histograms), n_reads, max_cpgs.
 // The rows are the sparse histograms (interval, length, runs, reads) sorted by (interval, length): one context's, or the shards' added.
 void mhl_regions_write(const std::vector<uint32_t> &r_iv, const std::vector<uint32_t> &r_len, const std::vector<uint64_t> &r_runs,
                        const std::vector<uint64_t> &r_reads, uint32_t min_depth) {
-    const Intervals &iv = g_intervals;
-    FILE *f = open_file(iv.mhl_path);
-    fprintf(f, "chrom\tstart\tend\tname\tmhl\tn_reads\tmax_cpgs\n");
-    LineWriter w(f);
     size_t o = 0;
-    for (size_t i = 0; i < iv.tid.size(); ++i) {
+    g_intervals.table(g_intervals.mhl_path, "mhl\tn_reads\tmax_cpgs", [&](LineWriter &w, size_t i) {
         const size_t o0 = o;
         while (o < r_iv.size() && r_iv[o] == (uint32_t)i) ++o;
         uint64_t n_reads = 0;
         uint32_t max_cpgs = 0;
         const float v = mth::mhl_regions_finalise(o - o0, r_len.data() + o0, r_runs.data() + o0, r_reads.data() + o0, min_depth, &n_reads, &max_cpgs);
-        w.str(iv.chrom[i].c_str()); w.ch('\t'); w.i32(iv.beg[i]); w.ch('\t'); w.i32(iv.end[i]); w.ch('\t'); w.str(iv.name[i].c_str()); w.ch('\t');
-        w.f32(v); w.ch('\t'); w.i64((long long)n_reads); w.ch('\t'); w.u32(max_cpgs); w.eol();
-    }
-    w.flush();
-    if (fclose(f) != 0) die("Error writing to output file.");
+        w.f32(v); w.ch('\t'); w.i64((long long)n_reads); w.ch('\t'); w.u32(max_cpgs);
+    });
 }
 
 // the histograms counted on this context (a shard of several: its rows go to main(), which adds the shards' -- a read is owned by the
@@ -1401,21 +1400,14 @@ void mhl_regions_finish(mth_ctx_t *ctx, uint32_t min_depth) {
 }
 
 // ---- pdr-regions: PDR per interval of a BED file ---------------------------------------------------------------
-// chrom, start, end, name, pdr (pdr.rs:47-49 of the interval's own counters), n_concordant, n_discordant, n_methylated: one row per BED
-// line.  The three arrays are the contributing reads per class: one context's, or the shards' added.
+// pdr (pdr.rs:47-49 of the interval's own counters), n_concordant, n_discordant, n_methylated.
+// The three arrays are the contributing reads per class: one context's, or the shards' added.
 void pdr_regions_write(const std::vector<uint64_t> &m, const std::vector<uint64_t> &u, const std::vector<uint64_t> &d, uint32_t min_depth) {
-    const Intervals &iv = g_intervals;
-    FILE *f = open_file(iv.pdr_path);
-    fprintf(f, "chrom\tstart\tend\tname\tpdr\tn_concordant\tn_discordant\tn_methylated\n");
-    LineWriter w(f);
-    for (size_t i = 0; i < iv.tid.size(); ++i) {
+    g_intervals.table(g_intervals.pdr_path, "pdr\tn_concordant\tn_discordant\tn_methylated", [&](LineWriter &w, size_t i) {
         const uint64_t conc = m[i] + u[i];
-        w.str(iv.chrom[i].c_str()); w.ch('\t'); w.i32(iv.beg[i]); w.ch('\t'); w.i32(iv.end[i]); w.ch('\t'); w.str(iv.name[i].c_str()); w.ch('\t');
         w.f32(mth::pdr_regions_finalise(conc, d[i], min_depth)); w.ch('\t'); w.i64((long long)conc); w.ch('\t'); w.i64((long long)d[i]); w.ch('\t');
-        w.i64((long long)m[i]); w.eol();
-    }
-    w.flush();
-    if (fclose(f) != 0) die("Error writing to output file.");
+        w.i64((long long)m[i]);
+    });
 }
 
 // the counters of this context (a shard of several: its arrays go to main(), which adds the shards' -- a read is owned by the shard
@@ -1555,13 +1547,19 @@ int run_quartet(const Args &a, bool want_me) {
     return finish(ctx, in.h);
 }
 
-int run_mhl(const Args &a) {
-    Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
-    mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
+// -d / -p / -q of mhl and of the two per-interval measures
+mth_mhl_params_t regions_params(const Args &a) {
     mth_mhl_params_t p;
     p.min_depth = (uint32_t)a.n.at("min-depth");
     p.min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
     p.min_qual = (uint8_t)a.n.at("min-qual");
+    return p;
+}
+
+int run_mhl(const Args &a) {
+    Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
+    mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
+    const mth_mhl_params_t p = regions_params(a);
     if (in.file_order) {
         mth_fileorder_params_t fp;
         memset(&fp, 0, sizeof fp);
@@ -1576,48 +1574,24 @@ int run_mhl(const Args &a) {
     return finish(ctx, in.h);
 }
 
-// every read counts once, whatever the order of the records: input that is not coordinate-sorted is routed as lpmd routes it
-int run_mhl_regions(const Args &a) {
+// mhl-regions / pdr-regions: every read counts once, whatever the order of the records, so input that is not coordinate-sorted is
+// routed as lpmd routes it
+int run_regions(const Args &a, bool pdr) {
     g_shard.order_free = true;
     Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
     mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
-    mth_mhl_params_t p;
-    p.min_depth = (uint32_t)a.n.at("min-depth");
-    p.min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
-    p.min_qual = (uint8_t)a.n.at("min-qual");
+    const mth_mhl_params_t p = regions_params(a);
     const Intervals &iv = g_intervals;
     {
         Phase ph("H2D + kernels (sync)");
-        check(ctx, mth_mhl_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
+        check(ctx, (pdr ? mth_pdr_regions_begin : mth_mhl_regions_begin)(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
         for (const Contig &c : in.contigs) {
             const mth_batch_t b = make_batch(in, c);
-            check(ctx, mth_mhl_regions_accumulate(ctx, &b, &p));
+            check(ctx, (pdr ? mth_pdr_regions_accumulate : mth_mhl_regions_accumulate)(ctx, &b, &p));
         }
+        if (pdr) check(ctx, mth_ctx_sync(ctx));           // (PDR's passes are queued: the phase's time is theirs only if it waits for them)
     }
-    mhl_regions_finish(ctx, p.min_depth);
-    return finish(ctx, in.h);
-}
-
-// ... and so is PDR per interval: three counters per interval, every read once
-int run_pdr_regions(const Args &a) {
-    g_shard.order_free = true;
-    Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
-    mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
-    mth_mhl_params_t p;
-    p.min_depth = (uint32_t)a.n.at("min-depth");
-    p.min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
-    p.min_qual = (uint8_t)a.n.at("min-qual");
-    const Intervals &iv = g_intervals;
-    {
-        Phase ph("H2D + kernels (sync)");
-        check(ctx, mth_pdr_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
-        for (const Contig &c : in.contigs) {
-            const mth_batch_t b = make_batch(in, c);
-            check(ctx, mth_pdr_regions_accumulate(ctx, &b, &p));
-        }
-        check(ctx, mth_ctx_sync(ctx));                    // (the passes are queued: the phase's time is theirs only if it waits for them)
-    }
-    pdr_regions_finish(ctx, p.min_depth);
+    if (pdr) pdr_regions_finish(ctx, p.min_depth); else mhl_regions_finish(ctx, p.min_depth);
     return finish(ctx, in.h);
 }
 
@@ -1996,8 +1970,8 @@ int main(int argc, char **argv) {
         if (sub == "pdr") return run_pdr(a);
         if (sub == "lpmd") return run_lpmd(a);
         if (sub == "mhl") return run_mhl(a);
-        if (sub == "mhl-regions") return run_mhl_regions(a);
-        if (sub == "pdr-regions") return run_pdr_regions(a);
+        if (sub == "mhl-regions") return run_regions(a, false);
+        if (sub == "pdr-regions") return run_regions(a, true);
         if (sub == "fdrp") return run_fdrp(a, false);
         if (sub == "qfdrp") return run_fdrp(a, true);
         if (sub == "me") return run_quartet(a, true);

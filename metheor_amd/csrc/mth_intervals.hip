@@ -20,11 +20,9 @@
 // workgroup then adds each interval it touched to memory once: a 1 Mbp interval takes two 64-bit atomics per tile, not per row.
 // Rows that can touch more than IV_ACC intervals of a class (windows nested thousands deep) add to memory directly: slower, never
 // a capacity error.
-#include <algorithm>
-
-#include "mth_ctx.h"
-#include "mth_intervals_dev.h"
-#include "mth_regions_host.h"
+// The sorted intervals and their packed table (mth_regions_host.h), a batch's domain (mth_regions_table.h) and the searches for the
+// candidates of a class (mth_intervals_dev.h) are the frame this pass shares with the two read x interval passes.
+#include "mth_regions_table.h"
 
 namespace mth {
 
@@ -42,9 +40,7 @@ struct IvArgs {
     const uint32_t *b_slice;                       // per batch: its domain's slices [b_slice[2b], b_slice[2b + 1])
     const unsigned long long *c_row0;              // work items [n_tiles, n_tiles + n_chunks): rows of the global path
     const uint32_t *c_n, *c_batch;
-    const int32_t *s_beg, *s_end;                  // per slice (one domain, one length class): its entries
-    const int32_t *e_start, *e_end, *e_maxend;     // per entry, sorted by start within the slice; maxend: running maximum of e_end
-    const uint32_t *e_out;                         // the interval (caller's index) the entry adds to
+    IvTab tab;                                     // the sorted intervals of the batches' domains
     unsigned long long *acc;                       // per interval: concordant, discordant
     unsigned long long n_tiles;
     uint32_t n_chunks, n_batches;
@@ -92,18 +88,14 @@ __global__ __launch_bounds__(IV_B) void k_pairs_intervals(const IvArgs a) {
 #pragma unroll
         for (int w = 0; w < IV_B / 64; ++w) { mn1 = min(mn1, s_red[0][w]); mx1 = max(mx1, s_red[1][w]); mn2 = min(mn2, s_red[2][w]); }
         for (uint32_t s = sl0; s < sl1; ++s) {                  // everything up to the row loop is block-uniform
-            const int32_t lo = a.s_beg[s], hi = a.s_end[s];
-            const int32_t w_hi = iv_upper_wave(a.e_start, lo, hi, mx1, lane);
-            if (w_hi == lo) continue;                           // every interval starts beyond the rows
-            // the running maximum ascends: below w_min no interval reaches the rows' smallest cpg2, and no walk gets there
-            const int32_t w_min = iv_upper_wave(a.e_maxend, lo, w_hi, mn2, lane);
-            if (w_min == w_hi) continue;                        // every interval that starts in time ends before the rows
-            const int32_t w_lo = iv_upper_wave(a.e_start, lo, w_hi, mn1, lane);
+            int32_t w_min, w_hi;                                // start <= the rows' largest cpg1, and an end > their smallest cpg2 at or after w_min
+            if (!iv_candidates(a.tab, s, mn2, mx1, lane, w_min, w_hi)) continue;
+            const int32_t w_lo = iv_upper_wave(a.tab.e_start, a.tab.s_beg[s], w_hi, mn1, lane);
             const int32_t w_n = w_hi - w_lo, acc_n = w_hi - w_min;
             const bool in_lds = w_n <= IV_LDS, acc_lds = acc_n <= IV_ACC;
             __syncthreads();                                    // the previous slice's searches and its flush are done
             if (in_lds)
-                for (int32_t i = tid; i < w_n; i += IV_B) s_start[i] = a.e_start[w_lo + i];
+                for (int32_t i = tid; i < w_n; i += IV_B) s_start[i] = a.tab.e_start[w_lo + i];
             if (acc_lds)
                 for (int32_t i = tid; i < 2 * acc_n; i += IV_B) s_acc[i] = 0ull;
             __syncthreads();
@@ -113,14 +105,14 @@ __global__ __launch_bounds__(IV_B) void k_pairs_intervals(const IvArgs a) {
                 const uint2 c = a.cnt[r0 + i];
                 // the last interval of the slice with start <= cpg1 (every one before the window starts at or before the rows' smallest
                 // cpg1), then back while the running maximum says that an end beyond cpg2 is still ahead
-                int32_t j = (in_lds ? w_lo + iv_upper(s_start, 0, w_n, p1) : iv_upper(a.e_start, w_lo, w_hi, p1)) - 1;
-                for (; j >= w_min && a.e_maxend[j] > p2; --j) {
-                    if (a.e_end[j] <= p2) continue;                     // start <= cpg1 and cpg2 < end: the row is the interval's
+                int32_t j = (in_lds ? w_lo + iv_upper(s_start, 0, w_n, p1) : iv_upper(a.tab.e_start, w_lo, w_hi, p1)) - 1;
+                for (; j >= w_min && a.tab.e_maxend[j] > p2; --j) {
+                    if (a.tab.e_end[j] <= p2) continue;                     // start <= cpg1 and cpg2 < end: the row is the interval's
                     if (acc_lds) {
                         if (c.x) atomicAdd(&s_acc[2 * (j - w_min)], (unsigned long long)c.x);
                         if (c.y) atomicAdd(&s_acc[2 * (j - w_min) + 1], (unsigned long long)c.y);
                     } else {
-                        const unsigned long long t = a.e_out[j];
+                        const unsigned long long t = a.tab.e_out[j];
                         if (c.x) atomicAdd(&a.acc[2ull * t], (unsigned long long)c.x);
                         if (c.y) atomicAdd(&a.acc[2ull * t + 1], (unsigned long long)c.y);
                     }
@@ -131,7 +123,7 @@ __global__ __launch_bounds__(IV_B) void k_pairs_intervals(const IvArgs a) {
             for (int32_t i = tid; i < acc_n; i += IV_B) {       // one pair of global atomics per interval the workgroup's rows touched
                 const unsigned long long nc = s_acc[2 * i], nd = s_acc[2 * i + 1];
                 if (!(nc | nd)) continue;
-                const unsigned long long t = a.e_out[w_min + i];
+                const unsigned long long t = a.tab.e_out[w_min + i];
                 if (nc) atomicAdd(&a.acc[2ull * t], nc);
                 if (nd) atomicAdd(&a.acc[2ull * t + 1], nd);
             }
@@ -150,8 +142,7 @@ int mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, con
     if (!ctx) return MTH_ERR_INVALID;
     if (n && (!tid || !beg || !end || !n_concordant || !n_discordant)) return fail(ctx, MTH_ERR_INVALID, "intervals: an array is missing");
     if (n >= (1ull << 31)) return fail(ctx, MTH_ERR_CAPACITY, "intervals: 2^31 or more intervals in one call");
-    for (uint64_t i = 0; i < n; ++i)
-        if (tid[i] < 0 || beg[i] < 0 || end[i] < beg[i]) return fail(ctx, MTH_ERR_INVALID, "intervals: want tid >= 0 and 0 <= beg <= end");
+    if (const char *bad = iv_check_intervals(n, tid, beg, end)) return iv_fail(ctx, MTH_ERR_INVALID, "intervals:", bad);
     MTH_ENTER(ctx);                                       // settles the queued batches of the table: its metas are exact from here
     if (n == 0) return sync_and_check(ctx);
     const TileRowTable &t = ctx->pairs;
@@ -159,18 +150,6 @@ int mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, con
 
     // ---- the intervals per domain and length class, sorted by start (mth_regions_host.h) ----
     IvDomains dm(n, tid, beg, end);
-    const std::vector<int32_t> &s_beg = dm.s_beg, &s_end = dm.s_end, &e_start = dm.e_start, &e_end = dm.e_end, &e_maxend = dm.e_maxend;
-    const std::vector<uint32_t> &e_out = dm.e_out;
-    auto &dom_slices = dm.dom_slices;
-    auto add_domain = [&](int32_t dom) -> int {
-        if (dom >= 0) { dm.add_domain(dom); return MTH_OK; }
-        const size_t gi = (size_t)(-2 - (int64_t)dom);
-        if (dom > -2 || gi >= ctx->groups.size())
-            return fail(ctx, MTH_ERR_STATE, "intervals: a batch of the pairs table carries the handle of a contig group that is not defined (any more)");
-        const mth_ctx::ContigGroup &g = ctx->groups[gi];
-        dm.add_domain(dom, g.tids.size(), g.tids.data(), g.voff.data());
-        return MTH_OK;
-    };
 
     // ---- the work items: every tile of the table, and the global path's rows of every batch in chunks ----
     const size_t nb = t.meta.size();
@@ -179,12 +158,12 @@ int mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, con
     uint64_t rows_end = 0;
     for (size_t b = 0; b < nb; ++b) {
         const TileBatch &mb = t.meta[b];
-        if (!dom_slices.count(mb.tid)) {
-            const int rc = add_domain(mb.tid);
-            if (rc) return rc;
-            if (e_start.size() >= (size_t)INT32_MAX) return fail(ctx, MTH_ERR_CAPACITY, "intervals: 2^31 or more interval entries");
-        }
-        const auto sl = dom_slices[mb.tid];
+        if (mb.tid < 0 && (mb.tid > -2 || (size_t)(-2 - (int64_t)mb.tid) >= ctx->groups.size()))
+            return fail(ctx, MTH_ERR_STATE, "intervals: a batch of the pairs table carries the handle of a contig group that is not defined (any more)");
+        std::pair<uint32_t, uint32_t> sl;
+        bool added;
+        const int rc = iv_slices_for(ctx, dm, "intervals:", mb.tid, sl, &added);
+        if (rc) return rc;
         b_tile_end[b] = mb.tile_end; b_slice[2 * b] = sl.first; b_slice[2 * b + 1] = sl.second;
         rows_end += mb.rows;
         if (sl.first != sl.second)
@@ -197,34 +176,26 @@ int mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, con
 
     MTH_HIP(ctx, ctx->iv_acc.reserve((size_t)n * 16, s));
     MTH_HIP(ctx, hipMemsetAsync(ctx->iv_acc.p, 0, (size_t)n * 16, s));
-    std::vector<unsigned long long> tab;                  // everything the kernel reads besides the table, as one upload (8-byte words first)
-    if (!e_start.empty() && n_items && t.rows) {
-        size_t off_w = 0;
-        auto place = [&](const void *src, size_t bytes) {
-            const size_t at = off_w;
-            const size_t words = (bytes + 7) / 8;
-            tab.resize(off_w + words);
-            if (bytes) memcpy(tab.data() + at, src, bytes);
-            off_w += words;
+    std::vector<uint32_t> tab;                            // everything the kernel reads besides the table, as one upload (8-byte words first)
+    if (dm.entries() && n_items && t.rows) {
+        auto place = [&](const void *src, size_t words) {
+            const size_t at = tab.size();
+            tab.resize(at + words);
+            if (words) memcpy(tab.data() + at, src, words * 4);
             return at;
         };
-        const size_t o_bte = place(b_tile_end.data(), nb * 8), o_cr0 = place(c_row0.data(), c_row0.size() * 8);
-        const size_t o_bsl = place(b_slice.data(), b_slice.size() * 4), o_cn = place(c_n.data(), c_n.size() * 4), o_cb = place(c_batch.data(), c_batch.size() * 4);
-        const size_t o_sb = place(s_beg.data(), s_beg.size() * 4), o_se = place(s_end.data(), s_end.size() * 4);
-        const size_t o_es = place(e_start.data(), e_start.size() * 4), o_ee = place(e_end.data(), e_end.size() * 4);
-        const size_t o_em = place(e_maxend.data(), e_maxend.size() * 4), o_eo = place(e_out.data(), e_out.size() * 4);
-        MTH_HIP(ctx, ctx->iv_tab.reserve(tab.size() * 8, s));
-        MTH_HIP(ctx, hipMemcpyAsync(ctx->iv_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-        const unsigned long long *base = ctx->iv_tab.as<unsigned long long>();
+        const size_t o_bte = place(b_tile_end.data(), nb * 2), o_cr0 = place(c_row0.data(), c_row0.size() * 2);
+        const size_t o_bsl = place(b_slice.data(), b_slice.size()), o_cn = place(c_n.data(), c_n.size()), o_cb = place(c_batch.data(), c_batch.size());
+        const IvTabOffsets o_tab = dm.pack(tab);
+        MTH_HIP(ctx, ctx->iv_tab.reserve(tab.size() * 4, s));
+        MTH_HIP(ctx, hipMemcpyAsync(ctx->iv_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+        const uint32_t *base = ctx->iv_tab.as<uint32_t>();
         IvArgs a;
         a.key = ctx->p_out_key.as<unsigned long long>(); a.cnt = ctx->p_out_cnt.as<uint2>();
         a.tile_row0 = t.tile_row0.as<unsigned long long>(); a.tile_rows = t.tile_rows.as<uint32_t>();
-        a.b_tile_end = base + o_bte; a.c_row0 = base + o_cr0;
-        a.b_slice = reinterpret_cast<const uint32_t *>(base + o_bsl);
-        a.c_n = reinterpret_cast<const uint32_t *>(base + o_cn); a.c_batch = reinterpret_cast<const uint32_t *>(base + o_cb);
-        a.s_beg = reinterpret_cast<const int32_t *>(base + o_sb); a.s_end = reinterpret_cast<const int32_t *>(base + o_se);
-        a.e_start = reinterpret_cast<const int32_t *>(base + o_es); a.e_end = reinterpret_cast<const int32_t *>(base + o_ee);
-        a.e_maxend = reinterpret_cast<const int32_t *>(base + o_em); a.e_out = reinterpret_cast<const uint32_t *>(base + o_eo);
+        a.b_tile_end = reinterpret_cast<const unsigned long long *>(base + o_bte); a.c_row0 = reinterpret_cast<const unsigned long long *>(base + o_cr0);
+        a.b_slice = base + o_bsl; a.c_n = base + o_cn; a.c_batch = base + o_cb;
+        a.tab = o_tab.at(base);
         a.acc = ctx->iv_acc.as<unsigned long long>();
         a.n_tiles = n_tiles; a.n_chunks = (uint32_t)c_row0.size(); a.n_batches = (uint32_t)nb;
         LaunchTimer lt(ctx, K_PAIRS_INTERVALS);

@@ -29,100 +29,67 @@
 // kind) behind an atomic cursor, merged by the host.  An entry that does not fit is counted, not written: the batch is then run again
 // with a list of the counted size, in a form that only appends, so nothing is added twice and nothing is dropped.
 // No cross-lane operation happens inside a lane's walk: the searches and reductions that use the whole wave sit in block-uniform code.
-#include <algorithm>
-#include <memory>
-
-#include "mth_ctx.h"
-#include "mth_intervals_dev.h"
-#include "mth_regions_host.h"
+// The frame -- owned-read test, span, candidate searches, the walk, the LDS rows' zeroing and flush -- is mth_intervals_dev.h's, shared
+// with k_pdr_regions; the declared intervals and their table on the device are a RegionsTable (mth_regions_table.h).
+#include "mth_regions_table.h"
 
 namespace mth {
 
-constexpr int MR_B = 256;                       // threads of a workgroup = reads of a work item
 constexpr int MR_ACC = 32;                      // entries of a class a workgroup sums in LDS (16 KiB)
 constexpr int MR_BINS = MHL_REGIONS_BINS;       // lengths of a dense row
 constexpr int MR_ROW = 2 * MR_BINS;             // a row: C[1 .. BINS], then R[1 .. BINS]
 constexpr uint32_t MR_MAX_CPGS = 16384;         // kept calls of a read (the limit MHL has: mth_sites.hip)
 
 struct MrArgs {
-    const int32_t *read_start;
-    const uint8_t *read_mapq;
-    const uint32_t *cpg_off, *cpg_pos;
-    const int32_t *s_beg, *s_end;                  // per slice (one domain, one length class): its entries
-    const int32_t *e_start, *e_end, *e_maxend;     // per entry, sorted by start within the slice; maxend: running maximum of e_end
-    const uint32_t *e_out;                         // the interval (caller's index) the entry adds to
+    RgReadArgs rd;
     unsigned long long *dense;                     // per interval: a row
     uint2 *list;                                   // overflow entries: interval, length | kind << 31 (0: a read of that many kept calls, 1: a run)
     unsigned long long *state;                     // [0] the list's cursor
-    DevState *st;
     unsigned long long list_cap;
-    uint32_t n_reads, n_cpgs, min_cpgs, sl0, sl1;
-    int32_t region_beg, region_end;
-    uint8_t min_qual, list_only;
+    uint8_t list_only;
 };
 
-__global__ __launch_bounds__(MR_B) void k_mhl_regions(const MrArgs a) {
+__global__ __launch_bounds__(RG_B) void k_mhl_regions(const MrArgs a) {
     __shared__ uint32_t s_rows[MR_ACC * MR_ROW];
-    __shared__ int32_t s_red[2][MR_B / 64];
+    __shared__ int32_t s_red[2][RG_B / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t n_chunks = (a.n_reads + MR_B - 1) / MR_B;
-    const uint32_t need = max(a.min_cpgs, 1u);
+    const RgReadArgs &rd = a.rd;
+    const uint32_t n_chunks = (rd.n_reads + RG_B - 1) / RG_B;
+    const uint32_t need = max(rd.min_cpgs, 1u);
     for (uint32_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
-        const uint32_t r = ch * MR_B + (uint32_t)tid;
         bool elig = false;
         uint32_t k0 = 0, k1 = 0;
         int32_t first = INT32_MAX, last = -1;
-        if (r < a.n_reads) {
-            const int32_t rs = a.read_start[r];
-            if (rs >= a.region_beg && rs < a.region_end && a.read_mapq[r] >= a.min_qual) {
-                k0 = a.cpg_off[r]; k1 = a.cpg_off[r + 1];
-                if (k1 > k0 && k1 <= a.n_cpgs && k1 - k0 >= need) {
-                    const uint32_t w0 = a.cpg_pos[k0] & 0x7fffffffu, w1 = a.cpg_pos[k1 - 1] & 0x7fffffffu;
-                    // the word of position -1: no batch may carry it (include/metheor_hip.h, mth_batch_t.cpg_pos)
-                    if (w0 == 0x7fffffffu || w1 == 0x7fffffffu) atomicOr(&a.st->err, (uint32_t)ERRB_RANGE);
-                    else { first = (int32_t)min(w0, w1); last = (int32_t)max(w0, w1); elig = true; }
-                }
-            }
+        if (rg_owned_read(rd, ch * RG_B + (uint32_t)tid, k0, k1)) {
+            const uint32_t w0 = rd.cpg_pos[k0] & 0x7fffffffu, w1 = rd.cpg_pos[k1 - 1] & 0x7fffffffu;
+            // the word of position -1: no batch may carry it (include/metheor_hip.h, mth_batch_t.cpg_pos)
+            if (w0 == 0x7fffffffu || w1 == 0x7fffffffu) atomicOr(&rd.st->err, (uint32_t)ERRB_RANGE);
+            else { first = (int32_t)min(w0, w1); last = (int32_t)max(w0, w1); elig = true; }
         }
         // the reads' smallest first and largest last call: what of a slice the workgroup can touch
         int32_t wmin = first, wmax = last;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { wmin = min(wmin, __shfl_xor(wmin, o, 64)); wmax = max(wmax, __shfl_xor(wmax, o, 64)); }
-        __syncthreads();                                        // the previous item's readers of s_red and s_rows are done
-        if (lane == 0) { s_red[0][wave] = wmin; s_red[1][wave] = wmax; }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < MR_B / 64; ++w) { wmin = min(wmin, s_red[0][w]); wmax = max(wmax, s_red[1][w]); }
+        rg_span(s_red, wmin, wmax, lane, wave, [](int) {}, [](int) {});
         if (wmax < 0) continue;                                 // no eligible read (block-uniform, as everything up to the lanes' walks)
-        for (uint32_t s = a.sl0; s < a.sl1; ++s) {
-            const int32_t lo = a.s_beg[s], hi = a.s_end[s];
-            const int32_t w_hi = iv_upper_wave(a.e_start, lo, hi, wmax, lane);
-            if (w_hi == lo) continue;                           // every interval starts beyond the reads
-            // the running maximum ascends: below w_min no interval reaches the reads' smallest first call, and no walk gets there
-            const int32_t w_min = iv_upper_wave(a.e_maxend, lo, w_hi, wmin, lane);
-            if (w_min == w_hi) continue;                        // every interval that starts in time ends before the reads
+        for (uint32_t s = rd.sl0; s < rd.sl1; ++s) {
+            int32_t w_min, w_hi;
+            if (!iv_candidates(rd.tab, s, wmin, wmax, lane, w_min, w_hi)) continue;
             const int32_t acc_n = w_hi - w_min;
             const bool use_lds = !a.list_only && acc_n <= MR_ACC;
             __syncthreads();                                    // the previous slice's flush is done
-            if (use_lds)
-                for (int32_t i = tid; i < acc_n * MR_ROW; i += MR_B) s_rows[i] = 0u;
+            if (use_lds) iv_rows_zero<MR_ROW>(s_rows, acc_n, tid);
             __syncthreads();
-            if (elig) {
-                // the last entry with start <= the read's last call, then back while an end beyond its first call is still ahead
-                for (int32_t j = iv_upper(a.e_start, w_min, w_hi, last) - 1; j >= w_min && a.e_maxend[j] > first; --j) {
-                    const int32_t ie = a.e_end[j];
-                    if (ie <= first) continue;
-                    const int32_t ib = a.e_start[j];
+            if (elig)
+                iv_walk(rd.tab, w_min, w_hi, first, last, [&](const int32_t j, const int32_t ib, const int32_t ie) {
                     uint32_t n = 0;
                     if (ib <= first && last < ie) n = k1 - k0;                                   // the interval holds the read whole
                     else
                         for (uint32_t k = k0; k < k1; ++k) {
-                            const int32_t p = (int32_t)(a.cpg_pos[k] & 0x7fffffffu);
+                            const int32_t p = (int32_t)(rd.cpg_pos[k] & 0x7fffffffu);
                             n += (p >= ib && p < ie) ? 1u : 0u;
                         }
-                    if (n < need) continue;
-                    if (n > MR_MAX_CPGS) { atomicOr(&a.st->err, (uint32_t)ERRB_CAPACITY); continue; }
-                    const uint32_t out = a.e_out[j];
+                    if (n < need) return;
+                    if (n > MR_MAX_CPGS) { atomicOr(&rd.st->err, (uint32_t)ERRB_CAPACITY); return; }
+                    const uint32_t out = rd.tab.e_out[j];
                     auto add = [&](const uint32_t kind, const uint32_t len) {
                         if (len <= (uint32_t)MR_BINS) {
                             if (a.list_only) return;
@@ -137,21 +104,17 @@ __global__ __launch_bounds__(MR_B) void k_mhl_regions(const MrArgs a) {
                     add(0u, n);
                     uint32_t run = 0;                                                            // get_stretch_info, readutil.rs:147-164
                     for (uint32_t k = k0; k < k1; ++k) {
-                        const uint32_t w = a.cpg_pos[k];
+                        const uint32_t w = rd.cpg_pos[k];
                         const int32_t p = (int32_t)(w & 0x7fffffffu);
                         if (p < ib || p >= ie) continue;                                         // filter_isin: not a call of this read here
                         if (w >> 31) ++run;
                         else if (run) { add(1u, run); run = 0; }
                     }
                     if (run) add(1u, run);
-                }
-            }
+                });
             if (!use_lds) continue;
             __syncthreads();
-            for (int32_t i = tid; i < acc_n * MR_ROW; i += MR_B) {      // one atomic per bin the workgroup's reads filled
-                const uint32_t v = s_rows[i];
-                if (v) atomicAdd(&a.dense[(unsigned long long)a.e_out[w_min + i / MR_ROW] * MR_ROW + (uint32_t)(i % MR_ROW)], (unsigned long long)v);
-            }
+            iv_rows_flush<MR_ROW>(s_rows, rd.tab, w_min, acc_n, a.dense, tid);
         }
     }
 }
@@ -159,11 +122,8 @@ __global__ __launch_bounds__(MR_B) void k_mhl_regions(const MrArgs a) {
 // what a context keeps between mth_mhl_regions_begin and the fetches
 struct MhlRegions {
     bool on = false;
-    std::vector<int32_t> tid, beg, end;
-    std::unique_ptr<IvDomains> dm;
-    bool tab_dirty = true;                                 // a domain was added since the table went up
-    size_t o_sb = 0, o_se = 0, o_es = 0, o_ee = 0, o_em = 0, o_eo = 0;      // the table's parts (32-bit words)
-    DevBuf tab, dense, list, state;
+    RegionsTable iv;                                       // the declared intervals and their table
+    DevBuf dense, list, state;
     uint64_t list_cap = 0, list_used = 0;
     uint64_t stats[4] = {0, 0, 0, 0};                      // overflow entries, batches run again, batches, reads of the batches
     // the sparse rows (interval, length, runs, reads) as of the latest counts / fetch; valid until the next accumulate
@@ -175,7 +135,8 @@ struct MhlRegions {
 void mhl_regions_release(mth_ctx *ctx) {
     MhlRegions *mr = ctx->mhl_regions;
     if (!mr) return;
-    for (DevBuf *b : {&mr->tab, &mr->dense, &mr->list, &mr->state}) b->release();
+    mr->iv.release();
+    for (DevBuf *b : {&mr->dense, &mr->list, &mr->state}) b->release();
     delete mr;
     ctx->mhl_regions = nullptr;
 }
@@ -184,31 +145,12 @@ void mhl_regions_release(mth_ctx *ctx) {
 int mhl_regions_clear(mth_ctx *ctx) {
     MhlRegions *mr = ctx->mhl_regions;
     if (!mr || !mr->on) return MTH_OK;
-    const size_t n = mr->tid.size();
+    const size_t n = mr->iv.size();
     if (n) MTH_HIP(ctx, hipMemsetAsync(mr->dense.p, 0, n * MR_ROW * 8, ctx->stream));
     MTH_HIP(ctx, hipMemsetAsync(mr->state.p, 0, 16, ctx->stream));
     mr->list_used = 0;
     for (uint64_t &k : mr->stats) k = 0;
     mr->rows_valid = false;
-    return MTH_OK;
-}
-
-static int mr_upload_table(mth_ctx *ctx, MhlRegions &mr) {
-    const IvDomains &dm = *mr.dm;
-    std::vector<uint32_t> tab;
-    auto place = [&](const void *src, size_t words) {
-        const size_t at = tab.size();
-        tab.resize(at + words);
-        if (words) memcpy(tab.data() + at, src, words * 4);
-        return at;
-    };
-    mr.o_sb = place(dm.s_beg.data(), dm.s_beg.size()); mr.o_se = place(dm.s_end.data(), dm.s_end.size());
-    mr.o_es = place(dm.e_start.data(), dm.e_start.size()); mr.o_ee = place(dm.e_end.data(), dm.e_end.size());
-    mr.o_em = place(dm.e_maxend.data(), dm.e_maxend.size()); mr.o_eo = place(dm.e_out.data(), dm.e_out.size());
-    // (every accumulate ends with a synchronisation: no kernel reads the table that is replaced here, and `tab` may go after the copy)
-    MTH_HIP(ctx, mr.tab.reserve(std::max<size_t>(tab.size(), 1) * 4, ctx->stream));
-    if (!tab.empty()) MTH_HIP(ctx, hipMemcpy(mr.tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-    mr.tab_dirty = false;
     return MTH_OK;
 }
 
@@ -233,7 +175,7 @@ static int mr_build_rows(mth_ctx *ctx, MhlRegions &mr) {
             if (e.y >> 31) ov.back().runs += 1; else ov.back().reads += 1;
         }
     }
-    const size_t n = mr.tid.size();
+    const size_t n = mr.iv.size();
     constexpr size_t STEP = 65536;                         // intervals per download (64 MiB)
     std::vector<unsigned long long> rows;
     size_t o = 0;
@@ -266,17 +208,13 @@ extern "C" {
 
 int mth_mhl_regions_begin(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, const int32_t *beg, const int32_t *end) {
     if (!ctx) return MTH_ERR_INVALID;
-    if (n && (!tid || !beg || !end)) return fail(ctx, MTH_ERR_INVALID, "mhl regions: an array is missing");
-    if (n >= (1ull << 31)) return fail(ctx, MTH_ERR_CAPACITY, "mhl regions: 2^31 or more intervals");
-    for (uint64_t i = 0; i < n; ++i)
-        if (tid[i] < 0 || beg[i] < 0 || end[i] < beg[i]) return fail(ctx, MTH_ERR_INVALID, "mhl regions: want tid >= 0 and 0 <= beg <= end");
+    const int bad = regions_check(ctx, "mhl regions:", n, tid, beg, end);
+    if (bad) return bad;
     MTH_ENTER(ctx);
     MTH_HIP(ctx, hipStreamSynchronize(ctx->stream));      // nothing of an earlier set is in flight when its buffers are reused
     if (!ctx->mhl_regions) ctx->mhl_regions = new MhlRegions;
     MhlRegions &mr = *ctx->mhl_regions;
-    mr.tid.assign(tid, tid + n); mr.beg.assign(beg, beg + n); mr.end.assign(end, end + n);
-    mr.dm.reset(new IvDomains(n, mr.tid.data(), mr.beg.data(), mr.end.data()));
-    mr.tab_dirty = true;
+    mr.iv.declare(n, tid, beg, end);
     MTH_HIP(ctx, mr.dense.reserve(std::max<size_t>((size_t)n, 1) * MR_ROW * 8, ctx->stream));
     MTH_HIP(ctx, mr.state.reserve(16, ctx->stream));
     mr.on = true;
@@ -292,40 +230,25 @@ int mth_mhl_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const m
     int rc = stage_batch(ctx, *batch, d);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    if (!mr.dm->has(d.tid)) {
-        if (d.tid >= 0) mr.dm->add_domain(d.tid);
-        else {
-            if (d.tid > -2) return fail(ctx, MTH_ERR_INVALID, "mhl regions: batch.tid");
-            const mth_ctx::ContigGroup &g = ctx->groups[(size_t)(-2 - (int64_t)d.tid)];      // (stage_batch has checked the handle)
-            mr.dm->add_domain(d.tid, g.tids.size(), g.tids.data(), g.voff.data());
-        }
-        if (mr.dm->entries() >= (size_t)INT32_MAX) return fail(ctx, MTH_ERR_CAPACITY, "mhl regions: 2^31 or more interval entries");
-        mr.tab_dirty = true;
-    }
+    std::pair<uint32_t, uint32_t> sl;
+    if ((rc = mr.iv.slices_for(ctx, "mhl regions:", d.tid, &sl))) return rc;
     mr.rows_valid = false;
     mr.stats[2] += 1; mr.stats[3] += d.n_reads;
-    const auto sl = mr.dm->dom_slices[d.tid];
     if (sl.first == sl.second || d.n_reads == 0 || d.n_cpgs == 0) return sync_and_check(ctx);     // no interval on the batch's contig(s), or no call
-    if (mr.tab_dirty && (rc = mr_upload_table(ctx, mr))) return rc;
+    if ((rc = mr.iv.upload(ctx))) return rc;
     if (!mr.list_cap) {
         const uint64_t cap = mhl_regions_list_knob();
         MTH_HIP(ctx, mr.list.reserve(cap * sizeof(uint2), s));
         mr.list_cap = cap;
     }
-    const uint32_t *tab = mr.tab.as<uint32_t>();
     MrArgs a;
-    a.read_start = d.read_start; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
-    a.s_beg = reinterpret_cast<const int32_t *>(tab + mr.o_sb); a.s_end = reinterpret_cast<const int32_t *>(tab + mr.o_se);
-    a.e_start = reinterpret_cast<const int32_t *>(tab + mr.o_es); a.e_end = reinterpret_cast<const int32_t *>(tab + mr.o_ee);
-    a.e_maxend = reinterpret_cast<const int32_t *>(tab + mr.o_em); a.e_out = tab + mr.o_eo;
+    a.rd = rg_read_args(ctx, d, *params, mr.iv.dev, sl);
     a.dense = mr.dense.as<unsigned long long>(); a.list = mr.list.as<uint2>(); a.state = mr.state.as<unsigned long long>();
-    a.st = ctx->d_state; a.list_cap = mr.list_cap;
-    a.n_reads = d.n_reads; a.n_cpgs = d.n_cpgs; a.min_cpgs = params->min_cpgs; a.sl0 = sl.first; a.sl1 = sl.second;
-    a.region_beg = d.region_beg; a.region_end = d.region_end; a.min_qual = params->min_qual; a.list_only = 0;
-    const uint32_t grid = std::min<uint32_t>((d.n_reads + MR_B - 1) / MR_B, 8192u);
+    a.list_cap = mr.list_cap; a.list_only = 0;
+    const uint32_t grid = std::min<uint32_t>((d.n_reads + RG_B - 1) / RG_B, 8192u);
     {
         LaunchTimer lt(ctx, K_MHL_REGIONS);
-        hipLaunchKernelGGL(k_mhl_regions, dim3(grid), dim3(MR_B), 0, s, a);
+        hipLaunchKernelGGL(k_mhl_regions, dim3(grid), dim3(RG_B), 0, s, a);
     }
     MTH_HIP(ctx, hipGetLastError());
     if ((rc = sync_and_check(ctx))) return rc;            // the batch's data errors are this call's return value
@@ -342,7 +265,7 @@ int mth_mhl_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const m
         a.list = mr.list.as<uint2>(); a.list_cap = mr.list_cap; a.list_only = 1;
         {
             LaunchTimer lt(ctx, K_MHL_REGIONS);
-            hipLaunchKernelGGL(k_mhl_regions, dim3(grid), dim3(MR_B), 0, s, a);
+            hipLaunchKernelGGL(k_mhl_regions, dim3(grid), dim3(RG_B), 0, s, a);
         }
         MTH_HIP(ctx, hipGetLastError());
         if ((rc = sync_and_check(ctx))) return rc;
@@ -382,7 +305,7 @@ int mth_mhl_regions_fetch(mth_ctx_t *ctx, uint32_t min_depth, float *mhl, uint64
     if (!mr || !mr->on) return fail(ctx, MTH_ERR_STATE, "mhl regions: mth_mhl_regions_begin has not declared the intervals");
     const int rc = mr_build_rows(ctx, *mr);
     if (rc) return rc;
-    const size_t n = mr->tid.size(), k = mr->r_iv.size();
+    const size_t n = mr->iv.size(), k = mr->r_iv.size();
     size_t o = 0;
     for (size_t i = 0; i < n; ++i) {
         const size_t o0 = o;

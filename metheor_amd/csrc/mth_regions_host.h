@@ -1,10 +1,11 @@
 // mth_regions_host.h -- the host-only pieces of the per-interval measures (`lpmd --intervals`, `mhl-regions`, `pdr-regions`): the intervals of a BED
-// file as one batch's domain sees them, and the finalisers of MHL and of PDR per interval.  Plain C++, nothing of HIP, no environment: the
+// file as one batch's domain sees them, their packed table, and the finalisers of MHL and of PDR per interval.  Plain C++, nothing of HIP, no environment: the
 // library (mth_intervals.hip, mth_mhl_regions.hip, mth_pdr_regions.hip) and the command line share this one copy, and it is tested
 // without a device.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -22,6 +23,28 @@ namespace mth {
 // interval lengths earlier, so a walk passes at most ~4x the intervals that hold its target, whatever other lengths the BED mixes in
 // (a chromosome-long interval sits in a class of its own and costs one step).
 struct IvEntry { int32_t start, end; uint32_t out; };
+
+// The slices of every domain met so far as a pass reads them on the device: six arrays in one buffer of 32-bit words.
+struct IvTab {
+    const int32_t *s_beg, *s_end;                  // per slice (one domain, one length class): its entries [s_beg, s_end)
+    const int32_t *e_start, *e_end, *e_maxend;     // per entry, sorted by start within the slice; maxend: running maximum of e_end
+    const uint32_t *e_out;                         // the interval (caller's index) the entry adds to
+};
+// where IvDomains::pack put the six arrays (32-bit words from the buffer's start), and the table at a buffer that holds them
+struct IvTabOffsets {
+    size_t s_beg, s_end, e_start, e_end, e_maxend, e_out;
+    IvTab at(const uint32_t *base) const {
+        auto i32 = [&](size_t o) { return reinterpret_cast<const int32_t *>(base + o); };
+        return IvTab{i32(s_beg), i32(s_end), i32(e_start), i32(e_end), i32(e_maxend), base + e_out};
+    }
+};
+
+// what a set of intervals must satisfy; nullptr, or the tail of the message (the caller's prefix names the measure)
+inline const char *iv_check_intervals(uint64_t n, const int32_t *tid, const int32_t *beg, const int32_t *end) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (tid[i] < 0 || beg[i] < 0 || end[i] < beg[i]) return "want tid >= 0 and 0 <= beg <= end";
+    return nullptr;
+}
 
 struct IvDomains {
     static constexpr int NCLS = 17;
@@ -74,6 +97,18 @@ struct IvDomains {
             s_end.push_back((int32_t)e_start.size());
         }
         dom_slices[dom] = {first, (uint32_t)s_beg.size()};
+    }
+
+    // the six arrays appended to `words` (the one place that knows the table's layout)
+    IvTabOffsets pack(std::vector<uint32_t> &words) const {
+        auto place = [&](const void *src, size_t n) {
+            const size_t at = words.size();
+            words.resize(at + n);
+            if (n) memcpy(words.data() + at, src, n * 4);
+            return at;
+        };
+        return IvTabOffsets{place(s_beg.data(), s_beg.size()), place(s_end.data(), s_end.size()), place(e_start.data(), e_start.size()),      // (in this order)
+                            place(e_end.data(), e_end.size()), place(e_maxend.data(), e_maxend.size()), place(e_out.data(), e_out.size())};
     }
 };
 
