@@ -12,7 +12,7 @@
 //                   compares).  <1>, for every other kernel: "first read starting at or after q*32 bp", four reads a thread.
 //   k_pdr_lpmd_tile one workgroup per 4096-bp tile of the contig: 128 threads for pipelined batches with 8-bit relative positions (two waves, each
 //                   taking two chunks of 64 reads per loop trip on two register sets whose loads travel half a trip apart; a thread
-//                   compacts 32 positions; no counter margins, 17.8 KB of LDS, NINE workgroups on a CU -- with four waves per
+//                   compacts 32 positions; no counter margins, 17.0 KB of LDS, NINE workgroups on a CU -- with four waves per
 //                   workgroup a SIMD's 8 wave slots allow 8), 256 threads for 16-bit ones and for a batch outside a pipelined run, where
 //                   the kernel has the chip to itself (MTH_TILE_B=128|256 forces either; profiles/tile_two_waves.md).  The tile's site
 //                   accumulators are DENSE in LDS (one 32-bit word per reference position holding both
@@ -467,7 +467,7 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
     constexpr bool MARGIN = MG > 0 && !WIDE;
     const RelT *__restrict__ rel = reinterpret_cast<const RelT *>(a.cpg_rel);
     constexpr bool PACKED = sizeof(RelT) == 1 && NB == 8;      // the table / packed-field forms below (8-bit relpos)
-    // (the caller has cleared the counters and built the slot tables)
+    // (the caller has cleared the counters and, where the launch's window needs it, built dtab)
 
     uint32_t lp_c = 0, lp_d = 0, n_read = 0, n_valid = 0, bad = 0;
     // PF (the plain-load instantiation with 8-bit relpos): ONE round trip per iteration.  Only the read's two call offsets are
@@ -547,13 +547,12 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
         // dead call word: a position 2^28 bp past the tile (clamped to the trash word by the scatter), or -- with margins -- the
         // lane's own word at the start of the low margin; the first call's state either way (concordant)
         const uint32_t dead_w = ((MARGIN ? (uint32_t)(P0 - MG + (tid & 63)) : (uint32_t)T0 + (1u << 28)) & 0x7fffffffu) | (v[0] & 0x80000000u);
-        const uint32_t n_lp = lp_ok ? min(n, (uint32_t)NB) : 0u;       // calls whose pairs are evaluated from the registers
         uint32_t acc = 0, xmax = (v[0] & 0x7fffffffu) - sm1;
+        [[maybe_unused]] LpMask lb = {0u, 0u};
         if constexpr (PACKED) {
-            // masks of the live slots from the table row of n (rows 8.. are all-live): and / sub / and / bfi / xor per slot
-            const uint32_t nrow = min(n, 8u);
-            const uint4 ma = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[0], mb = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[1];
-            const uint32_t mk[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
+            // masks of the live slots from the live bytes of n (no LDS: mth_tile_dev.h): bfe / sub / and / bfi / xor per slot
+            __builtin_assume(n != 0u);                           // (work)
+            lb = lpmd_live_bytes(n);
             uint32_t xs[8];
             xs[0] = xmax;
 #pragma unroll
@@ -562,8 +561,9 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
                 // into not / and / and / or for six of the seven slots).  The state bit rides through the subtraction (no
                 // borrow for a call at or after start - 1; a call before it leaves a huge value either way) and is masked
                 // together with the liveness.
-                xs[k] = __builtin_amdgcn_bitop3_b32(v[k] - sm1, mk[k], 0x7fffffffu, 0x80);       // a & b & c
-                v[k] = __builtin_amdgcn_bitop3_b32(v[k], dead_w, mk[k], 0xe4);                    // c ? a : b
+                const uint32_t mk = slot_mask(lb, k);
+                xs[k] = __builtin_amdgcn_bitop3_b32(v[k] - sm1, mk, 0x7fffffffu, 0x80);          // a & b & c
+                v[k] = __builtin_amdgcn_bitop3_b32(v[k], dead_w, mk, 0xe4);                       // c ? a : b
                 acc = __builtin_amdgcn_bitop3_b32(acc, v[k], v[0], 0xf6);                         // a | (b ^ c)
             }
             xmax = max(max(max(xs[0], xs[1]), max(xs[2], xs[3])), max(max(xs[4], xs[5]), max(xs[6], xs[7])));
@@ -577,6 +577,7 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
                 acc |= v[k] ^ v[0];
             }
             if (any_lp) {
+                const uint32_t n_lp = lp_ok ? min(n, (uint32_t)NB) : 0u;       // calls whose pairs are evaluated from the registers
 #pragma unroll
                 for (int k = 0; k < NB; ++k) r[k] = ((uint32_t)k < n_lp) ? r[k] : (int32_t)((k + 1) << 24);
             }
@@ -595,10 +596,11 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
         bad |= bad_it;
         // windowed pair counts (readutil.rs:166-224): pairs (j<k) with min <= rel_k - rel_j <= max.
         // The calls are sorted by relpos, so the distance at call-index gap g+1 is >= the distance at gap g:
-        // walk the pair matrix by diagonals g = 1, 2, .. and stop once NO lane of the wave has a pair
-        // within max_distance on the current diagonal (wave-uniform break).
+        // walk the pair matrix by diagonals g = 1, 2, .. with a wave-uniform break.  8-bit relpos (lpmd_pairs8): once NO lane of the
+        // wave has two ADJACENT pairs within max_distance on the current diagonal, which a pair on the next one needs (mth_lpmd_bytes.h);
+        // 16-bit relpos (the loop below): once no lane has a pair within max_distance on it.
         if constexpr (PACKED) {
-            if (any_lp) lpmd_pairs8(v, rraw0, rraw1, n_lp, tabs, mind, maxd, lp_c, lp_d);
+            if (any_lp) lpmd_pairs8(v, rraw0, rraw1, n, lp_ok, lb, tabs, mind, maxd, lp_c, lp_d);
         } else if (any_lp) {
             const uint32_t span_ok = (uint32_t)(maxd - a.min_dist);
             uint32_t lp_n = 0, lp_dd = 0;
@@ -782,7 +784,7 @@ __device__ __forceinline__ uint32_t tile_pass(const TileArgs &a, const uint32_t 
 #define MTH_TILE_OCC 8      // workgroups per CU the kernel is compiled for (7 / 6 / 5: 72 / 80 / 96 VGPRs -- A/B in round 5)
 #endif
 // (the second launch bound is waves per SIMD.  Four waves per workgroup: 8 workgroups are the 8 waves a SIMD holds, 64 VGPRs each, whatever the
-// LDS would admit.  Two waves per workgroup, B = 128: the LDS decides -- without the counter margins a workgroup takes 17.8 KB and NINE fit a
+// LDS would admit.  Two waves per workgroup, B = 128: the LDS decides -- without the counter margins a workgroup takes 17.0 KB and NINE fit a
 // CU's 160 KB, 18 waves, 5 on a SIMD at most and up to 102 VGPRs each; that ninth workgroup is what the two-wave form is for)
 template <int W, int B, int NB, typename RelT, int MG>
 __global__ __launch_bounds__(B, B == 128 ? 5 : MTH_TILE_OCC) void k_pdr_lpmd_tile(const TileArgs a, const uint32_t ntiles) {
@@ -823,7 +825,7 @@ __global__ __launch_bounds__(B, B == 128 ? 5 : MTH_TILE_OCC) void k_pdr_lpmd_til
         for (int i = threadIdx.x; i < W / 4; i += B) reinterpret_cast<uint4 *>(cnt + MG)[i] = make_uint4(0, 0, 0, 0);
     };
     clear();
-    slot_tabs_init<B>(tabs, threadIdx.x);
+    if constexpr (sizeof(RelT) == 1) slot_tabs_init(tabs, threadIdx.x, slot_tabs_wanted(a));      // (16-bit relpos: no packed form, no table)
     MTH_TK(1);
     __syncthreads();
     MTH_TK(2);
@@ -975,7 +977,7 @@ __global__ __launch_bounds__(256, MTH_RUNS_OCC) void k_pdr_lpmd_runs(const TileA
     [[maybe_unused]] const unsigned long long rt_beg = RT_NOW();
     [[maybe_unused]] unsigned long long rt_loop = 0, rt_b1 = 0, rt_comp = 0, rt_b2 = 0, rt_pre = 0, rt_t = rt_beg, rt_ntile = 0, rt_wait = 0, rt_iters = 0;
     for (int i = tid; i < W / 4; i += B) reinterpret_cast<uint4 *>(cnt)[i] = make_uint4(0, 0, 0, 0);
-    slot_tabs_init(tabs, tid);
+    slot_tabs_init(tabs, tid, slot_tabs_wanted(a));
     if (tid < 2) { s_lon[tid] = 0; s_more[tid] = 0; }
     if (tid < 4) s_rows[tid] = 0;
     if (tid < 16) s_lp[tid >> 2][tid & 3] = 0ull;
@@ -1118,18 +1120,17 @@ __global__ __launch_bounds__(256, MTH_RUNS_OCC) void k_pdr_lpmd_runs(const TileA
                 if (work) {
                     const uint32_t sm1 = (uint32_t)(s - 1);
                     const uint32_t dead_w = ((MARGIN ? (uint32_t)(P0 - MG + lane) : (uint32_t)T0 + (1u << 28)) & 0x7fffffffu) | (v[0] & 0x80000000u);
-                    const uint32_t n_lp = lp_ok ? min(n, (uint32_t)NB) : 0u;
                     uint32_t acc = 0, xmax;
+                    __builtin_assume(n != 0u);                           // (work)
+                    const LpMask lb = lpmd_live_bytes(n);
                     {
-                        const uint32_t nrow = min(n, 8u);
-                        const uint4 ma = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[0], mb = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[1];
-                        const uint32_t mk[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
                         uint32_t xs[8];
                         xs[0] = (v[0] & 0x7fffffffu) - sm1;
 #pragma unroll
                         for (int k = 1; k < 8; ++k) {
-                            xs[k] = __builtin_amdgcn_bitop3_b32(v[k] - sm1, mk[k], 0x7fffffffu, 0x80);       // a & b & c
-                            v[k] = __builtin_amdgcn_bitop3_b32(v[k], dead_w, mk[k], 0xe4);                    // c ? a : b
+                            const uint32_t mk = slot_mask(lb, k);
+                            xs[k] = __builtin_amdgcn_bitop3_b32(v[k] - sm1, mk, 0x7fffffffu, 0x80);          // a & b & c
+                            v[k] = __builtin_amdgcn_bitop3_b32(v[k], dead_w, mk, 0xe4);                       // c ? a : b
                             acc = __builtin_amdgcn_bitop3_b32(acc, v[k], v[0], 0xf6);                         // a | (b ^ c)
                         }
                         xmax = max(max(max(xs[0], xs[1]), max(xs[2], xs[3])), max(max(xs[4], xs[5]), max(xs[6], xs[7])));
@@ -1158,7 +1159,7 @@ __global__ __launch_bounds__(256, MTH_RUNS_OCC) void k_pdr_lpmd_runs(const TileA
                                 }
                             }
                         }
-                        lpmd_pairs8(v, rraw0, rraw1, n_lp, tabs, mind, maxd, lp_c, lp_d);
+                        lpmd_pairs8(v, rraw0, rraw1, n, lp_ok, lb, tabs, mind, maxd, lp_c, lp_d);
                     }
                     if (any_long && lp_ok && n > (uint32_t)NB) {      // pairs whose later call is the 9th or beyond: from memory (rare)
                         const uint8_t *__restrict__ rel = reinterpret_cast<const uint8_t *>(a.cpg_rel);

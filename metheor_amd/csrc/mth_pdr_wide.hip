@@ -25,6 +25,7 @@
 //
 // The pass is ONE device body, tile_pass, behind two kernels: k_pdr_lpmd_wide (the above) and k_multi_tile, the same body with the
 // ME / PM quartet side on (the fused pass of `metheor all`; what it adds and when a tile is handed back: mth_multi.hip).
+#include <type_traits>
 #include "mth_ctx.h"
 #include "mth_quartet_dev.h"
 #include "mth_tile_dev.h"
@@ -44,9 +45,14 @@ constexpr uint32_t PW_EMPTY = 0xffffffffu;
 // the fused form (k_multi_tile): a 512-slot quartet table and a 2048-read queue.  LDS per workgroup ~37.7 KiB (site table 12, quartet
 // table 20, queue 4) -> four workgroups per CU
 constexpr int FQ_S = 512, FQ_OCC = 4, FQ_QCAP = 2048;
+// Slot masks and LPMD masks of the body: from the 9-row LDS tables (true) or from the live-byte mask of the call count in registers, as in
+// the dense tile kernel (false).  Both kernels here take the tables: with the register form k_pdr_lpmd_wide<.., u8> spilled a second
+// register and ran 1.7 % slower at WGBS depth (roofline_wgbs 0.4335-0.4370 of peak against 0.4390-0.4473), and every sample of the fused
+// pass lay in the upper half of its spread (profiles/tile_loop_lds.md) -- seven / four waves a SIMD cover the reads the dense form waits for
+constexpr bool PW_TABLE_MASKS = true;
 
 // One tile of the pass.  QUARTET: the ME / PM side (k_multi_tile) on top of PDR + LPMD; QCAP: candidate reads per fill of the queue.
-template <int SHIFT, typename RelT, bool QUARTET, int QCAP>
+template <int SHIFT, typename RelT, bool QUARTET, int QCAP, bool TABLE_MASKS>
 __device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet &q, const uint32_t ntiles) {
     constexpr int W = 1 << SHIFT;
     constexpr bool PACKED = sizeof(RelT) == 1;                 // 8-bit relpos: the packed pair form
@@ -58,7 +64,7 @@ __device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet 
     uint16_t *const rq = reinterpret_cast<uint16_t *>(q_or_sort);
     uint32_t *const bbase = q_or_sort;
     __shared__ uint32_t red[4][PW_B / 64], ws[PW_B / 64 + 1];
-    __shared__ __attribute__((aligned(16))) SlotTabs tabs;
+    __shared__ __attribute__((aligned(16))) std::conditional_t<TABLE_MASKS, SlotTabsMasks, SlotTabs> tabs;
     __shared__ uint32_t s_over, s_qn;
     // QUARTET: the quartet table (k_quartet_tile's: 64-bit key, sixteen 16-bit bins in 8 words); it lives for the whole tile.  (Without
     // QUARTET nothing refers to these arrays and they take no LDS.)
@@ -78,7 +84,8 @@ __device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet 
     const int32_t T1 = (int32_t)min((int64_t)T0 + Wt, (int64_t)a.region_end);
     const RelT *__restrict__ rel = reinterpret_cast<const RelT *>(a.cpg_rel);
     SiteRec *__restrict__ out = a.scratch + (size_t)t * W;
-    slot_tabs_init(tabs, tid);
+    if constexpr (TABLE_MASKS) slot_tabs_init(tabs, tid);
+    else if constexpr (PACKED) slot_tabs_init(tabs, tid, slot_tabs_wanted(a));
     if constexpr (QUARTET) {
         for (int i = tid; i < FQ_S; i += PW_B) qkeys[i] = QKEY_EMPTY;
         for (int i = tid; i < FQ_S * 8; i += PW_B) qbins[i] = 0u;
@@ -200,10 +207,18 @@ __device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet 
                 const bool lp_ok = lp_possible && owned && mq >= a.lpmd_min_qual && n > 1;
                 const bool pdr_ok = act && a.want_pdr && n >= a.min_cpgs && mq >= a.pdr_min_qual;
                 const uint32_t sm1 = (uint32_t)(s - 1);
-                // slot liveness, span check, concordance state (pdr.rs:37-45 via readutil.rs:226-251): the tile kernel's table form
-                const uint32_t nrow = min(n, 8u);
-                const uint4 ma = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[0], mb = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[1];
-                const uint32_t mk[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
+                // slot liveness, span check, concordance state (pdr.rs:37-45 via readutil.rs:226-251): the tile kernel's form, masks from the tables or from the live bytes of n
+                uint32_t mk[8];
+                [[maybe_unused]] LpMask lb = {0u, 0u};
+                if constexpr (TABLE_MASKS) {
+                    const uint32_t nrow = min(n, 8u);
+                    const uint4 ma = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[0], mb = reinterpret_cast<const uint4 *>(&tabs.mtab[nrow][0])[1];
+                    mk[0] = ma.x; mk[1] = ma.y; mk[2] = ma.z; mk[3] = ma.w; mk[4] = mb.x; mk[5] = mb.y; mk[6] = mb.z; mk[7] = mb.w;
+                } else {
+                    lb = lpmd_live_bytes(n);                     // (a lane without a read: n = 0, no live slot)
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) mk[k] = slot_mask(lb, k);
+                }
                 uint32_t acc = 0, xmax = act ? (v[0] & 0x7fffffffu) - sm1 : 0u;
 #pragma unroll
                 for (int k = 1; k < PW_NB; ++k) {
@@ -225,10 +240,12 @@ __device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet 
                 bad |= act ? bad_it : 0u;
                 // windowed pair counts (readutil.rs:166-224): pairs (j < k) with min <= rel_k - rel_j <= max, diagonal by diagonal
                 if (__any(lp_ok)) {
-                    const uint32_t n_lp = lp_ok ? min(n, (uint32_t)PW_NB) : 0u;
-                    if constexpr (PACKED) {
-                        lpmd_pairs8(v, rraw0, rraw1, n_lp, tabs, mind, maxd, a_c, a_d);
+                    if constexpr (PACKED && TABLE_MASKS) {
+                        lpmd_pairs8(v, rraw0, rraw1, lp_ok ? min(n, (uint32_t)PW_NB) : 0u, tabs, mind, maxd, a_c, a_d);
+                    } else if constexpr (PACKED) {
+                        lpmd_pairs8(v, rraw0, rraw1, n, lp_ok, lb, tabs, mind, maxd, a_c, a_d);
                     } else {
+                        const uint32_t n_lp = lp_ok ? min(n, (uint32_t)PW_NB) : 0u;
 #pragma unroll
                         for (int k = 0; k < PW_NB; ++k) r[k] = ((uint32_t)k < n_lp) ? r[k] : (int32_t)((k + 1) << 24);
                         const uint32_t span_ok = (uint32_t)(maxd - a.min_dist);
@@ -396,11 +413,11 @@ __device__ __forceinline__ void tile_pass(const TileArgs &a, const FusedQuartet 
 
 template <int SHIFT, typename RelT>
 __global__ __launch_bounds__(PW_B, MTH_PW_OCC) void k_pdr_lpmd_wide(const TileArgs a, const uint32_t ntiles) {
-    tile_pass<SHIFT, RelT, false, PW_QCAP>(a, FusedQuartet{}, ntiles);
+    tile_pass<SHIFT, RelT, false, PW_QCAP, PW_TABLE_MASKS>(a, FusedQuartet{}, ntiles);
 }
 template <int SHIFT, typename RelT>
 __global__ __launch_bounds__(PW_B, FQ_OCC) void k_multi_tile(const TileArgs a, const FusedQuartet q, const uint32_t ntiles) {
-    tile_pass<SHIFT, RelT, true, FQ_QCAP>(a, q, ntiles);
+    tile_pass<SHIFT, RelT, true, FQ_QCAP, PW_TABLE_MASKS>(a, q, ntiles);
 }
 
 // the shift x rel8 switch of both forms (q: the fused form's quartet side)

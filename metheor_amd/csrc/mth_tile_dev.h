@@ -59,11 +59,16 @@ typedef uint32_t u32x4_a2 __attribute__((ext_vector_type(4), aligned(2)));
 
 // ---- per-slot liveness without compare + select (profiles/r02_ubench_valu.md: v_cmp, v_cndmask, v_min/max are half rate) ----
 // The live call slots of a read are a PREFIX (k < n), so everything that depends on "slot k is dead" is a function of n
-// alone and comes from two 9-row LDS tables (n = 0..8; built once per pass, 576 bytes):
-//   mtab[n][k]   0xffffffff if k < n else 0                       -> masks for the span check / dead-word insertion
+// alone.  It lives in two registers, not in LDS: LB(n) = 0x80 in byte k of 64 bits iff k < min(n, 8) (lpmd_live_bytes, mth_lpmd_bytes.h:
+// a shift of a constant by the call count).  From it, each where it is used,
+//   slot_mask(LB, k)   0xffffffff if k < n else 0 (v_bfe_i32)     -> masks for the span check / dead-word insertion
+//   LB >> 8 g          0x80 in byte j iff the pair (j, j + g) is live: the byte form's mask of diagonal g (mth_lpmd_bytes.h)
+// (These were 9-row LDS tables, mtab and m8, read at the top of every chunk of 64 reads and once per diagonal: LDS round trips queued
+// behind the previous chunk's scatter atomics with nothing of the wave's own to cover them; profiles/tile_loop_lds.md.  The hashed-site
+// and fused kernels keep them: SlotTabsMasks below.)
+// One table is left in the dense tile and run kernels, for the windows the byte form does not take, and only a launch with such a window builds it (slot_tabs_init):
 //   dtab[n][c]   relpos offsets of the packed fields (below) that push every dead slot 0x400 * (k + 1) past the live
 //                ones, so that any distance involving a dead slot is >= 0x400 - 255 and all distances stay >= 0
-//   m8[n][g]     mth_lpmd_bytes.h: 0x80 in byte j of the two words iff the pair (j, j + g) is live
 // ---- windowed pair counts on 8-bit relpos ----
 // Four pairs per instruction on the bytes as loaded (mth_lpmd_bytes.h) while the window allows it (min <= 128, max <= 127: the
 // command line's 2 / 16 and anything near it); two pairs per instruction on 16-bit fields otherwise (lpmd_pairs_fields16 below).
@@ -92,22 +97,38 @@ struct FusedQuartet {
 void launch_tile_fused(const TileArgs &a, const FusedQuartet &q, uint32_t ntiles, int shift, bool rel8, hipStream_t s);
 
 struct SlotTabs {
-    uint32_t mtab[9][8];
     uint32_t dtab[9][8];
-    LpMask   m8[9][8];
 };
-// B = threads of the workgroup: 144 or more fill the tables in one step each (the loops fold into the guards they were), the dense
-// kernel's 128-thread form takes two for the mask table
-template <int B = 256>
-__device__ __forceinline__ void slot_tabs_init(SlotTabs &T, const int tid0) {
-    for (int tid = tid0; tid < 144; tid += B) (&T.m8[0][0].w0)[tid] = lpmd_bytes_mask((uint32_t)tid >> 4, ((uint32_t)tid >> 1) & 7u, (uint32_t)tid & 1u);
-    for (int tid = tid0; tid < 72; tid += B) {
+// does this launch count its pairs on 16-bit fields (and read dtab)?  The window as the kernels clamp it for 8-bit relpos; wave-uniform
+__device__ __forceinline__ bool slot_tabs_wanted(const TileArgs &a) {
+    return a.want_lpmd && !lpmd_bytes_domain(max(a.min_dist, 0), min(a.max_dist, 255));
+}
+// Before the workgroup's first barrier.  A launch whose window the byte form takes issues nothing here.  (72 threads fill the table in one step.)
+__device__ __forceinline__ void slot_tabs_init(SlotTabs &T, const int tid, const bool wanted) {
+    if (wanted && tid < 72) {
         const uint32_t nn = (uint32_t)tid >> 3, c = (uint32_t)tid & 7u;
-        T.mtab[nn][c] = c < nn ? 0xffffffffu : 0u;
         auto dead = [&](uint32_t k) { return k >= 8u ? 0x2400u : (k >= nn ? 0x400u * (k + 1u) : 0u); };
         const uint32_t lo = c < 4 ? 2u * c : 2u * (c - 4u) + 1u;       // first slot of the packed register Q_c / O_(c-4)
         T.dtab[nn][c] = dead(lo) | (dead(lo + 1u) << 16);
     }
+}
+// The table form of the same masks, for the hashed-site and fused kernels (mth_pdr_wide.hip, PW_TABLE_MASKS): seven waves a SIMD cover
+// an LDS read there, and the dozen vector instructions a read that replace it cost 1.7 % of the hashed-site kernel (profiles/tile_loop_lds.md)
+//   mtab[n][k]   0xffffffff if k < n else 0
+//   m8[n][g]     LB(n) >> 8 g, the two words of the byte form's mask of diagonal g
+struct SlotTabsMasks : SlotTabs {
+    uint32_t mtab[9][8];
+    LpMask   m8[9][8];
+};
+// (256 threads: every table in one step, built by every launch)
+__device__ __forceinline__ void slot_tabs_init(SlotTabsMasks &T, const int tid) {
+    slot_tabs_init(static_cast<SlotTabs &>(T), tid, true);
+    if (tid < 144) (&T.m8[0][0].w0)[tid] = lpmd_bytes_mask((uint32_t)tid >> 4, ((uint32_t)tid >> 1) & 7u, (uint32_t)tid & 1u);
+    if (tid < 72) T.mtab[(uint32_t)tid >> 3][(uint32_t)tid & 7u] = ((uint32_t)tid & 7u) < ((uint32_t)tid >> 3) ? 0xffffffffu : 0u;
+}
+// 0xffffffff if slot k is live else 0: the sign extension of bit 8 k + 7 of LB (one v_bfe_i32 where the mask is used)
+__device__ __forceinline__ uint32_t slot_mask(const LpMask lb, const int k) {
+    return (uint32_t)((int32_t)((k < 4 ? lb.w0 : lb.w1) << (24 - 8 * (k & 3))) >> 31);
 }
 __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }   // v_bfi_b32
 
@@ -139,7 +160,10 @@ __device__ __forceinline__ void lpmd_pairs_fields16(const uint32_t (&v)[8], cons
     uint32_t accIN = 0, accDD = 0;
 #pragma unroll
     for (int g = 1; g < 8; ++g) {
-        uint32_t orB = 0;
+        // The fields of the registers m = 0, 1, .. are the pairs (0, g), (1, 1 + g), .. in order, so two adjacent pairs within max are
+        // two neighbouring fields with bit 15 of Bw set: the exit rule of mth_lpmd_bytes.h (a pair on diagonal g + 1 needs two adjacent
+        // ones on g), with v_alignbit_b32 bringing the next register's low field beside this one's high field
+        uint32_t adjB = 0, prevB = 0;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int li = (g & 1) ? (g - 1) / 2 + m : g / 2 + m;      // index of the later operand in O (g odd) / Q (g even)
@@ -151,19 +175,31 @@ __device__ __forceinline__ void lpmd_pairs_fields16(const uint32_t (&v)[8], cons
             const uint32_t DD = IN & (sl ^ SQ[m]);
             accIN += __builtin_popcount(IN);        // v_bcnt_u32_b32 adds its second operand: one instruction per count
             accDD += __builtin_popcount(DD);
-            orB |= Bw;
+            if (m > 0) adjB |= prevB & __builtin_amdgcn_alignbit(Bw, prevB, 16);
+            prevB = Bw;
         }
-        if (!__any((orB & 0x80008000u) != 0u)) break;      // no lane has a pair within max_distance on this diagonal
+        adjB |= prevB & (prevB >> 16);
+        if (!__any((adjB & 0x80008000u) != 0u)) break;      // no lane has two adjacent pairs within max_distance on this diagonal
     }
     lp_c += accIN - accDD;
     lp_d += accDD;
 }
 
 // The pairs among a read's first 8 calls (readutil.rs:166-224): v = its call words (dead slots: any word), rraw0 / rraw1 = its 8
-// relpos bytes as loaded (dead slots: any byte), n_lp = live slots (0: count nothing), [mind, maxd] = the window, 0 <= mind,
-// mind <= maxd <= 255 (the callers have excluded an empty window).  The lanes of a wave that have a read call it together: the early exit is a vote among them.
+// relpos bytes as loaded (dead slots: any byte), lb = LB(n) of its n calls, lp_ok = its pairs count (false: count nothing), [mind, maxd] =
+// the window, 0 <= mind, mind <= maxd <= 255 (the callers have excluded an empty window).  The lanes of a wave that have a read call it
+// together: the early exit is a vote among them.
+__device__ __forceinline__ void lpmd_pairs8(const uint32_t (&v)[8], const uint32_t rraw0, const uint32_t rraw1, const uint32_t n, const bool lp_ok,
+                                            const LpMask lb, const SlotTabs &T, const int32_t mind, const int32_t maxd, uint32_t &lp_c, uint32_t &lp_d) {
+    if (lpmd_bytes_domain(mind, maxd))
+        lpmd_pairs_bytes(rraw0, rraw1, lpmd_state_bytes(v[0], v[1], v[2], v[3]), lpmd_state_bytes(v[4], v[5], v[6], v[7]), lp_ok ? lb.w0 : 0u,
+                         lp_ok ? lb.w1 : 0u, (uint32_t)mind, (uint32_t)maxd, lp_c, lp_d);
+    else
+        lpmd_pairs_fields16(v, rraw0, rraw1, &T.dtab[lp_ok ? min(n, 8u) : 0u][0], (uint32_t)mind, (uint32_t)maxd, lp_c, lp_d);      // (slot_tabs_wanted: built)
+}
+// the table form: n_lp = live slots whose pairs count (0: count nothing), the row of either table
 __device__ __forceinline__ void lpmd_pairs8(const uint32_t (&v)[8], const uint32_t rraw0, const uint32_t rraw1, const uint32_t n_lp,
-                                            const SlotTabs &T, const int32_t mind, const int32_t maxd, uint32_t &lp_c, uint32_t &lp_d) {
+                                            const SlotTabsMasks &T, const int32_t mind, const int32_t maxd, uint32_t &lp_c, uint32_t &lp_d) {
     if (lpmd_bytes_domain(mind, maxd))
         lpmd_pairs_bytes(rraw0, rraw1, lpmd_state_bytes(v[0], v[1], v[2], v[3]), lpmd_state_bytes(v[4], v[5], v[6], v[7]), &T.m8[n_lp][0],
                          (uint32_t)mind, (uint32_t)maxd, lp_c, lp_d);
