@@ -362,6 +362,39 @@ int  mth_pdr_regions_counts(mth_ctx_t *ctx, uint64_t *methylated, uint64_t *unme
 float mth_pdr_regions_finalise(uint64_t n_concordant, uint64_t n_discordant, uint32_t min_depth);
 int  mth_pdr_regions_fetch(mth_ctx_t *ctx, uint32_t min_depth, float *pdr, uint64_t *n_concordant, uint64_t *n_discordant, uint64_t *n_methylated);
 
+/* ---- ME and PM per interval (`me-regions`, `pm-regions`; me.rs:42-55, 82, 115-125, pm.rs:42-51, readutil.rs:87-132) ----------------
+ * The methylation entropy and the epipolymorphism of a REGION: one value each per interval [beg, end) of contig tid, from every read
+ * taken once.  Per record: BismarkRead (readutil.rs:24-53); the calls with beg <= abspos < end are kept, in the read's call order --
+ * filter_isin (readutil.rs:87-94) with the set "every position of the interval", a call at position -1 lies in no interval --; the
+ * read contributes if mapq >= min_qual (me.rs:115) and at least 4 calls are kept (readutil.rs:101); a contributing read adds
+ * get_cpg_quartets_and_patterns() (readutil.rs:97-132) of the kept calls, one pattern 8*m1 + 4*m2 + 2*m3 + m4 per window of four
+ * consecutive kept calls (n - 3 patterns for n kept calls), all into ONE 16-bin histogram for the interval (me.rs:121-125 with
+ * every quartet mapped to the same QuartetStat).  n_patterns = the sum of the bins (the pooled stat's get_read_depth()), n_reads =
+ * the contributing reads.  ME = compute_me (me.rs:42-55), PM = compute_pm (pm.rs:42-51) of the histogram, each NaN when
+ * n_patterns < max(min_depth, 1) (me.rs:82 applied to the pooled stat); the counts are reported either way.  No flush: the counts
+ * do not depend on the record order or on how the reads are split over batches and contexts.  The counters are 64-bit integers;
+ * each counter and the total are converted to f32 once: the reference's bits whenever they fit its u32.
+ *   begin       declares the n intervals (host arrays, copied; 0-based, half-open, 0 <= beg <= end; any order, overlap, nesting
+ *               and duplicates; fewer than 2^31) and clears the sums.  mth_reset clears the sums and keeps the intervals.
+ *   accumulate  one batch (host, device-resident or prepared; a contig or a contig group, whose intervals are shifted by their
+ *               contig's voff).  Only the reads the batch OWNS count (region_beg <= read_start < region_end).  The calls of a
+ *               read may come in any order of position: the windows follow the call order (me.rs:120).  NOT synchronous: the pass
+ *               is queued on the context's stream and the call returns; a device-resident batch's arrays stay untouched until the
+ *               next counts / fetch (or any call that waits for the stream).  Data errors -- a batch that carries the word of
+ *               position -1: MTH_ERR_RANGE -- are the return value of that call.
+ *   counts      per interval, in the caller's order: bins[i * 16 + p] = windows of pattern p (me.rs:38-40), reads[i] = contributing
+ *               reads.  Either may be NULL.  Several contexts (shards): add their arrays and finalise once.
+ *   finalise    host only, no context: me.rs:42-55 and pm.rs:42-51 of ONE interval's sixteen bins, in the reference's operation
+ *               order (bins ascending, me *= -0.25 last, pm -= p * p for every bin), NaN below max(min_depth, 1) patterns;
+ *               *n_patterns = the sum of the bins.  Any output may be NULL.
+ *   fetch       finalise of every declared interval, in the caller's order.  Arrays of n, any may be NULL.  Another min_depth
+ *               needs no new pass. */
+int  mth_quartet_regions_begin(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, const int32_t *beg, const int32_t *end);
+int  mth_quartet_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const mth_quartet_params_t *params);
+int  mth_quartet_regions_counts(mth_ctx_t *ctx, uint64_t *bins, uint64_t *reads);
+void mth_quartet_regions_finalise(const uint64_t *bins, uint32_t min_depth, float *me, float *pm, uint64_t *n_patterns);
+int  mth_quartet_regions_fetch(mth_ctx_t *ctx, uint32_t min_depth, float *me, float *pm, uint64_t *n_patterns, uint64_t *n_reads);
+
 /* ---- FDRP and qFDRP (fdrp.rs:176-246, qfdrp.rs:188-258): both from one pass ---------------------
  * Exact stream semantics (strict '<' flush by reads passing mapq with >= 1 CpG, +-201-bp window
  * drop, fill to max_depth in file order).  Beyond max_depth the reference replaces stored reads at

@@ -18,6 +18,7 @@ SYMBOLS = [
     "mth_allreduce_lpmd_rank", "mth_quartet_accumulate", "mth_quartet_fetch", "mth_mhl_accumulate", "mth_mhl_fetch", "mth_fdrp_accumulate", "mth_fdrp_fetch", "mth_multi_accumulate", "mth_multi_stats", "mth_lpmd_pairs_accumulate", "mth_lpmd_pairs_fetch", "mth_lpmd_intervals_fetch",
     "mth_mhl_regions_begin", "mth_mhl_regions_accumulate", "mth_mhl_regions_counts", "mth_mhl_regions_finalise", "mth_mhl_regions_fetch", "mth_mhl_regions_stats",
     "mth_pdr_regions_begin", "mth_pdr_regions_accumulate", "mth_pdr_regions_counts", "mth_pdr_regions_finalise", "mth_pdr_regions_fetch",
+    "mth_quartet_regions_begin", "mth_quartet_regions_accumulate", "mth_quartet_regions_counts", "mth_quartet_regions_finalise", "mth_quartet_regions_fetch",
     "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome", "mth_decode_set_modtags",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
@@ -204,6 +205,12 @@ def lib():
         L.mth_pdr_regions_finalise.restype = C.c_float
         L.mth_pdr_regions_finalise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
         L.mth_pdr_regions_fetch.argtypes = [vp, C.c_uint32] + [vp] * 4
+        L.mth_quartet_regions_begin.argtypes = [vp, C.c_uint64] + [vp] * 3
+        L.mth_quartet_regions_accumulate.argtypes = [vp, C.POINTER(mth_batch_t), C.POINTER(mth_quartet_params_t)]
+        L.mth_quartet_regions_counts.argtypes = [vp] + [vp] * 2
+        L.mth_quartet_regions_finalise.restype = None
+        L.mth_quartet_regions_finalise.argtypes = [vp, C.c_uint32] + [vp] * 3
+        L.mth_quartet_regions_fetch.argtypes = [vp, C.c_uint32] + [vp] * 4
         L.mth_decode_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(mth_decoded_t)]
         L.mth_decode_set_cpg_filter.argtypes = [vp, vp, C.c_uint64, C.c_int]
         L.mth_decode_set_xm_min_mapq.argtypes = [vp, C.c_uint32]
@@ -261,6 +268,16 @@ def pdr_regions_finalise(n_concordant, n_discordant, min_depth=10):
     """the host finaliser (mth_regions_host.h) of ONE interval's counters: pdr.rs:47-49 as float32, NaN below max(min_depth, 1)
     contributing reads; no context, no device"""
     return np.float32(lib().mth_pdr_regions_finalise(int(n_concordant), int(n_discordant), min_depth))
+
+
+def quartet_regions_finalise(bins, min_depth=10):
+    """the host finaliser (mth_regions_host.h) of ONE interval's sixteen bins: me.rs:42-55 and pm.rs:42-51 as float32, NaN below
+    max(min_depth, 1) patterns -> (me, pm, n_patterns); no context, no device"""
+    b = np.ascontiguousarray(bins, np.uint64)
+    assert b.shape == (16,)
+    me, pm, n = C.c_float(0), C.c_float(0), C.c_uint64(0)
+    lib().mth_quartet_regions_finalise(b.ctypes.data_as(C.c_void_p), min_depth, C.byref(me), C.byref(pm), C.byref(n))
+    return np.float32(me.value), np.float32(pm.value), int(n.value)
 
 
 class PdrLpmdParams:
@@ -637,6 +654,40 @@ class Engine:
         k = self._pr_n
         out = dict(pdr=np.empty(k, np.float32), n_concordant=np.empty(k, np.uint64), n_discordant=np.empty(k, np.uint64), n_methylated=np.empty(k, np.uint64))
         self._check(self.L.mth_pdr_regions_fetch(self.h, min_depth, *[out[c].ctypes.data_as(C.c_void_p) for c in ("pdr", "n_concordant", "n_discordant", "n_methylated")]))
+        self._settled()
+        return out
+
+    # ---- ME / PM per interval (mth_quartet_regions.hip) ----
+    def quartet_regions_begin(self, tid, beg, end):
+        """declare the intervals [beg, end) of contig tid (0-based, half-open; any order, overlap, nesting, duplicates) and clear the sums"""
+        t, b, e = (np.ascontiguousarray(x, np.int32) for x in (tid, beg, end))
+        assert t.ndim == 1 and t.shape == b.shape == e.shape
+        self._qr_n = len(t)
+        self._check(self.L.mth_quartet_regions_begin(self.h, len(t), *[x.ctypes.data_as(C.c_void_p) for x in (t, b, e)]))
+        self._settled()
+
+    def quartet_regions_accumulate(self, batch, min_qual=10):
+        """the batch's OWNED reads (region_beg <= read_start < region_end) into the sixteen bins and the reads word of every declared
+        interval (me.rs:115-125 after readutil.rs:87-94 with the interval's positions, then readutil.rs:97-132); queued, not waited
+        for: data errors surface at the counts / fetch"""
+        p = mth_quartet_params_t(min_qual)
+        self._hold(batch)
+        self._check(self.L.mth_quartet_regions_accumulate(self.h, C.byref(batch.c), C.byref(p)))
+
+    def quartet_regions_counts(self):
+        """per declared interval: bins[i, p] = windows of pattern p, reads[i] = contributing reads.  Shards add these."""
+        k = self._qr_n
+        out = dict(bins=np.empty((k, 16), np.uint64), reads=np.empty(k, np.uint64))
+        self._check(self.L.mth_quartet_regions_counts(self.h, *[out[c].ctypes.data_as(C.c_void_p) for c in ("bins", "reads")]))
+        self._settled()
+        return out
+
+    def quartet_regions_fetch(self, min_depth=10):
+        """per declared interval: me (me.rs:42-55) and pm (pm.rs:42-51) of its pooled histogram, NaN below max(min_depth, 1)
+        patterns; n_patterns, n_reads"""
+        k = self._qr_n
+        out = dict(me=np.empty(k, np.float32), pm=np.empty(k, np.float32), n_patterns=np.empty(k, np.uint64), n_reads=np.empty(k, np.uint64))
+        self._check(self.L.mth_quartet_regions_fetch(self.h, min_depth, *[out[c].ctypes.data_as(C.c_void_p) for c in ("me", "pm", "n_patterns", "n_reads")]))
         self._settled()
         return out
 

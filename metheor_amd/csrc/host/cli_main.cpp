@@ -62,9 +62,11 @@ const Opt O_MMTHR = {"mm-threshold", 0, "MM_THRESHOLD", "(MI355X extension) With
 const Opt O_INTERVALS = {"intervals", 0, "INTERVALS", "(MI355X extension) BED file of intervals: LPMD of each one, as `-c` with all of the interval's positions would give it", nullptr, false, 's'};
 // ... and MHL per interval, counted on the device from the reads; on `all` the BED is shared by the two tables
 const Opt O_INTERVALS_MHL = {"intervals", 0, "INTERVALS", "BED file of intervals: MHL of each one, from the reads' calls inside it, as `-c` with all of the interval's positions would keep them", nullptr, true, 's'};
-const Opt O_INTERVALS_ALL = {"intervals", 0, "INTERVALS", "(MI355X extension) BED file of intervals for --lpmd-intervals, --mhl-intervals and / or --pdr-intervals: each measure restricted to an interval's positions, as `-c` with all of them would", nullptr, false, 's'};
+const Opt O_INTERVALS_ALL = {"intervals", 0, "INTERVALS", "(MI355X extension) BED file of intervals for --lpmd-intervals, --mhl-intervals, --pdr-intervals, --me-intervals and / or --pm-intervals: each measure restricted to an interval's positions, as `-c` with all of them would", nullptr, false, 's'};
 // ... and PDR per interval, counted on the device from the reads
 const Opt O_INTERVALS_PDR = {"intervals", 0, "INTERVALS", "BED file of intervals: PDR of each one, from the reads' calls inside it, as `-c` with all of the interval's positions would keep them", nullptr, true, 's'};
+// ... and ME / PM per interval, from sixteen counters per interval counted on the device
+const Opt O_INTERVALS_QR = {"intervals", 0, "INTERVALS", "BED file of intervals: the value of each one, from the windows of four consecutive calls of every read inside it, as `-c` with all of the interval's positions would keep them", nullptr, true, 's'};
 const Opt O_BAI = {"bai", 'b', "BAI", "(MI355X extension) BAM index for --region [default: <input>.bai]", nullptr, false, 's'};
 
 // lib.rs:24-231
@@ -132,7 +134,9 @@ const std::vector<Cmd> &commands() {
           O_CPG, O_REGION, O_BAI, O_GENOME, O_MMTAGS, O_MMTHR,
           O_INTERVALS_ALL, {"lpmd-intervals", 0, "LPMD_INTERVALS", "(MI355X extension) Output table of the per-interval LPMD (needs --lpmd and the BED)", nullptr, false, 's'},
           {"mhl-intervals", 0, "MHL_INTERVALS", "(MI355X extension) Output table of the per-interval MHL, one row per line of the BED (needs the BED; an output of its own, --mhl is not needed)", nullptr, false, 's'},
-          {"pdr-intervals", 0, "PDR_INTERVALS", "(MI355X extension) Output table of the per-interval PDR, one row per line of the BED (needs the BED; an output of its own, --pdr is not needed)", nullptr, false, 's'}}},
+          {"pdr-intervals", 0, "PDR_INTERVALS", "(MI355X extension) Output table of the per-interval PDR, one row per line of the BED (needs the BED; an output of its own, --pdr is not needed)", nullptr, false, 's'},
+          {"me-intervals", 0, "ME_INTERVALS", "(MI355X extension) Output table of the per-interval methylation entropy, one row per line of the BED (needs the BED; an output of its own, --me is not needed)", nullptr, false, 's'},
+          {"pm-intervals", 0, "PM_INTERVALS", "(MI355X extension) Output table of the per-interval epipolymorphism, one row per line of the BED (needs the BED; an output of its own, --pm is not needed)", nullptr, false, 's'}}},
         // not in the reference: MHL of a region, as Guo et al. (2017) define it, for every interval of a BED file
         {"mhl-regions", "(MI355X extension) Compute methylation haplotype load (MHL) per interval of a BED file",
          {O_IN, {"output", 'o', "OUTPUT", "Path to output table: chrom, start, end, name, mhl, n_reads, max_cpgs, one row per line of the BED", nullptr, true, 's'},
@@ -146,6 +150,18 @@ const std::vector<Cmd> &commands() {
           O_INTERVALS_PDR,
           {"min-depth", 'd', "MIN_DEPTH", "Minimum number of contributing reads of an interval (fewer: NaN)", "10", false, 'U'},
           {"min-cpgs", 'p', "MIN_CPGS", "Minimum number of CpGs of a read inside an interval for the read to contribute", "4", false, 'Z'},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_GENOME, O_MMTAGS, O_MMTHR}},
+        // not in the reference: ME (Xie et al. 2011) and PM (Landan et al. 2012) of a region, every window of four consecutive calls inside
+        // an interval pooled into one histogram, for every interval of a BED file
+        {"me-regions", "(MI355X extension) Compute methylation entropy per interval of a BED file",
+         {O_IN, {"output", 'o', "OUTPUT", "Path to output table: chrom, start, end, name, me, n_patterns, n_reads, one row per line of the BED", nullptr, true, 's'},
+          O_INTERVALS_QR,
+          {"min-depth", 'd', "MIN_DEPTH", "Minimum number of patterns (windows of four CpGs) of an interval (fewer: NaN)", "10", false, 'U'},
+          {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_GENOME, O_MMTAGS, O_MMTHR}},
+        {"pm-regions", "(MI355X extension) Compute epipolymorphism per interval of a BED file",
+         {O_IN, {"output", 'o', "OUTPUT", "Path to output table: chrom, start, end, name, pm, n_patterns, n_reads, one row per line of the BED", nullptr, true, 's'},
+          O_INTERVALS_QR,
+          {"min-depth", 'd', "MIN_DEPTH", "Minimum number of patterns (windows of four CpGs) of an interval (fewer: NaN)", "10", false, 'U'},
           {"min-qual", 'q', "MIN_QUAL", "Minimum quality for a read to be considered", "10", false, 'B'}, O_CPG, O_GPUS, O_GENOME, O_MMTAGS, O_MMTHR}},
         {"tag", "Add bismark XM tag to BAM file",
          {{"input", 'i', "INPUT", "", nullptr, true, 's'}, {"output", 'o', "OUTPUT", "", nullptr, true, 's'},
@@ -311,7 +327,8 @@ thread_local Shard g_shard;
 // what one shard contributes to the output files (filled through open_memstream when world > 1)
 struct Part { char *out = nullptr; size_t out_len = 0; char *pairs = nullptr; size_t pairs_len = 0; std::vector<int64_t> iv_c, iv_d;
               std::vector<uint32_t> mr_iv, mr_len; std::vector<uint64_t> mr_runs, mr_reads;
-              std::vector<uint64_t> pr_m, pr_u, pr_d; };
+              std::vector<uint64_t> pr_m, pr_u, pr_d;
+              std::vector<uint64_t> qr_bins, qr_reads; };
 thread_local Part *g_part = nullptr;
 
 // the shards' threads meet here once: the last to arrive runs the collective for all of them
@@ -1287,12 +1304,14 @@ void lpmd_pairs_write(mth_ctx_t *ctx, const Input &in, const std::string &path) 
 // Read by main() before any device or output is touched; every shard of a --gpus N run reduces its own rows for all of them.
 struct Intervals {
     std::string path, out_path, mhl_path, pdr_path;      // out_path: the per-interval LPMD table, mhl_path / pdr_path: the per-interval MHL / PDR table
+    std::string me_path, pm_path;                        // the per-interval ME / PM table (one pass counts for both)
     std::vector<std::string> chrom, name;
     std::vector<int32_t> tid, beg, end;
     bool on() const { return !out_path.empty(); }
     bool mhl_on() const { return !mhl_path.empty(); }
     bool pdr_on() const { return !pdr_path.empty(); }
-    // one of the three tables, a row per BED line: chrom, start, end, name, then the measure's own columns (`header`; row(w, i) writes them)
+    bool quartet_on() const { return !me_path.empty() || !pm_path.empty(); }
+    // one of the tables, a row per BED line: chrom, start, end, name, then the measure's own columns (`header`; row(w, i) writes them)
     template <class Row>
     void table(const std::string &table_path, const char *header, Row &&row) const {
         FILE *f = open_file(table_path);
@@ -1419,6 +1438,33 @@ void pdr_regions_finish(mth_ctx_t *ctx, uint32_t min_depth) {
     check(ctx, mth_pdr_regions_counts(ctx, m.data(), u.data(), d.data()));
     if (g_shard.world > 1) { g_part->pr_m.swap(m); g_part->pr_u.swap(u); g_part->pr_d.swap(d); return; }
     pdr_regions_write(m, u, d, min_depth);
+}
+
+// ---- me-regions / pm-regions: ME and PM per interval of a BED file ------------------------------------------------
+// me (me.rs:42-55) or pm (pm.rs:42-51) of the interval's own pooled histogram, n_patterns, n_reads.
+// bins: sixteen per interval, reads: one -- one context's, or the shards' added.  Either table, or both, from the same counters.
+void quartet_regions_write(const std::vector<uint64_t> &bins, const std::vector<uint64_t> &reads, uint32_t min_depth) {
+    for (const bool want_me : {true, false}) {
+        const std::string &path = want_me ? g_intervals.me_path : g_intervals.pm_path;
+        if (path.empty()) continue;
+        g_intervals.table(path, want_me ? "me\tn_patterns\tn_reads" : "pm\tn_patterns\tn_reads", [&](LineWriter &w, size_t i) {
+            float me = 0.0f, pm = 0.0f;
+            uint64_t n_patterns = 0;
+            mth::quartet_regions_finalise(bins.data() + i * 16, min_depth, &me, &pm, &n_patterns);
+            w.f32(want_me ? me : pm); w.ch('\t'); w.i64((long long)n_patterns); w.ch('\t'); w.i64((long long)reads[i]);
+        });
+    }
+}
+
+// the counters of this context (a shard of several: its arrays go to main(), which adds the shards' -- a read is owned by the shard
+// that holds its start -- finalises once and writes the file).  The first call that waits for the queued passes: their data errors
+// surface here
+void quartet_regions_finish(mth_ctx_t *ctx, uint32_t min_depth) {
+    const size_t n = g_intervals.tid.size();
+    std::vector<uint64_t> bins(n * 16), reads(n);
+    check(ctx, mth_quartet_regions_counts(ctx, bins.data(), reads.data()));
+    if (g_shard.world > 1) { g_part->qr_bins.swap(bins); g_part->qr_reads.swap(reads); return; }
+    quartet_regions_write(bins, reads, min_depth);
 }
 
 // me.rs:68-88 / pm.rs:63-83: one line per quartet with depth >= min_depth,
@@ -1595,6 +1641,27 @@ int run_regions(const Args &a, bool pdr) {
     return finish(ctx, in.h);
 }
 
+// me-regions / pm-regions: one function for both (the path main() has set says which table is written); order-free as the two above
+int run_quartet_regions(const Args &a) {
+    g_shard.order_free = true;
+    Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
+    mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
+    mth_quartet_params_t p;
+    p.min_qual = (uint8_t)a.n.at("min-qual");
+    const Intervals &iv = g_intervals;
+    {
+        Phase ph("H2D + kernels (sync)");
+        check(ctx, mth_quartet_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
+        for (const Contig &c : in.contigs) {
+            const mth_batch_t b = make_batch(in, c);
+            check(ctx, mth_quartet_regions_accumulate(ctx, &b, &p));
+        }
+        check(ctx, mth_ctx_sync(ctx));                        // (the passes are queued: the phase's time is theirs only if it waits for them)
+    }
+    quartet_regions_finish(ctx, (uint32_t)a.n.at("min-depth"));
+    return finish(ctx, in.h);
+}
+
 int run_fdrp(const Args &a, bool quantitative) {
     Input in = load(a.s.at("input"), a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr);
     mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
@@ -1637,7 +1704,7 @@ int run_fdrp(const Args &a, bool quantitative) {
 int run_all(const Args &a) {
     const std::string input = a.s.at("input");
     const char *cpg_set = a.has("cpg-set") ? a.s.at("cpg-set").c_str() : nullptr;
-    const bool w_pdr = a.has("pdr"), w_lpmd = a.has("lpmd"), w_pairs = a.has("lpmd-pairs"), w_iv = g_intervals.on(), w_mr = g_intervals.mhl_on(), w_pr = g_intervals.pdr_on(), w_mhl = a.has("mhl"), w_me = a.has("me"),
+    const bool w_pdr = a.has("pdr"), w_lpmd = a.has("lpmd"), w_pairs = a.has("lpmd-pairs"), w_iv = g_intervals.on(), w_mr = g_intervals.mhl_on(), w_pr = g_intervals.pdr_on(), w_qr = g_intervals.quartet_on(), w_mhl = a.has("mhl"), w_me = a.has("me"),
                w_pm = a.has("pm"), w_fdrp = a.has("fdrp"), w_qfdrp = a.has("qfdrp");
     const uint32_t min_depth = (uint32_t)a.n.at("min-depth");
     const uint32_t min_cpgs = (uint32_t)std::min<int64_t>(a.n.at("min-cpgs"), UINT32_MAX);
@@ -1646,8 +1713,8 @@ int run_all(const Args &a) {
     if (w_lpmd)   // lpmd.rs:161-164
         fprintf(stderr, "Computing subset-LPMD with parameters input=%s, min_distance=%d, max_distance=%d\n", input.c_str(), mind, maxd);
     const bool any_flush = w_pdr || w_mhl || w_fdrp || w_qfdrp;          // the measures whose result depends on the record order
-    const bool any_free = w_lpmd || w_me || w_pm || w_mr || w_pr;
-    g_shard.xm_min_mapq = (any_flush || w_me || w_pm || w_mr || w_pr) ? 0 : (int)min_qual;
+    const bool any_free = w_lpmd || w_me || w_pm || w_mr || w_pr || w_qr;
+    g_shard.xm_min_mapq = (any_flush || w_me || w_pm || w_mr || w_pr || w_qr) ? 0 : (int)min_qual;
     g_shard.order_free = !any_flush;
     Input in = load(input, cpg_set);
     mth_ctx_t *ctx = in.ctx ? in.ctx : make_ctx();
@@ -1713,6 +1780,7 @@ int run_all(const Args &a) {
         const Intervals &iv = g_intervals;
         if (w_mr) check(ctx, mth_mhl_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
         if (w_pr) check(ctx, mth_pdr_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
+        if (w_qr) check(ctx, mth_quartet_regions_begin(ctx, iv.tid.size(), iv.tid.data(), iv.beg.data(), iv.end.data()));
         for (const Contig &c : bin->contigs) {
             const mth_batch_t b = make_batch(*bin, c);
             mth_batch_t pb;
@@ -1720,6 +1788,7 @@ int run_all(const Args &a) {
             if (mp.want) check(ctx, mth_multi_accumulate(ctx, &pb, &mp));
             if (w_mr) check(ctx, mth_mhl_regions_accumulate(ctx, &pb, &mp.mhl));      // the per-interval MHL, on the batch as it is prepared
             if (w_pr) check(ctx, mth_pdr_regions_accumulate(ctx, &pb, &mp.mhl));      // ... and the per-interval PDR (queued; the release waits)
+            if (w_qr) check(ctx, mth_quartet_regions_accumulate(ctx, &pb, &mp.quartet));      // ... and the per-interval ME / PM (queued as well)
             check(ctx, mth_batch_release(ctx, &pb));
         }
     }
@@ -1729,6 +1798,7 @@ int run_all(const Args &a) {
     if (w_iv) lpmd_intervals_write(ctx);
     if (w_mr) mhl_regions_finish(ctx, min_depth);
     if (w_pr) pdr_regions_finish(ctx, min_depth);
+    if (w_qr) quartet_regions_finish(ctx, min_depth);
     if (w_me) quartet_write(ctx, *bin, min_depth, true, a.s.at("me"));
     if (w_pm) quartet_write(ctx, *bin, min_depth, false, a.s.at("pm"));
     if (mp.want & MTH_MULTI_MHL) mhl_write(ctx, *bin, a.s.at("mhl"));
@@ -1972,6 +2042,7 @@ int main(int argc, char **argv) {
         if (sub == "mhl") return run_mhl(a);
         if (sub == "mhl-regions") return run_regions(a, false);
         if (sub == "pdr-regions") return run_regions(a, true);
+        if (sub == "me-regions" || sub == "pm-regions") return run_quartet_regions(a);
         if (sub == "fdrp") return run_fdrp(a, false);
         if (sub == "qfdrp") return run_fdrp(a, true);
         if (sub == "me") return run_quartet(a, true);
@@ -1988,21 +2059,24 @@ int main(int argc, char **argv) {
         return run_tag(a);
     }
     if (sub == "all") {      // clap-style: an ArgGroup of the outputs (required, multiple) and `requires` on --lpmd-pairs
-        static const char *outs[] = {"pdr", "lpmd", "mhl", "me", "pm", "fdrp", "qfdrp", "mhl-intervals", "pdr-intervals"};
+        static const char *outs[] = {"pdr", "lpmd", "mhl", "me", "pm", "fdrp", "qfdrp", "mhl-intervals", "pdr-intervals", "me-intervals", "pm-intervals"};
         bool any = false;
         for (const char *o : outs) any |= a.has(o);
         if (!any)
-            usage_error(cmd, "the following required arguments were not provided:\n  <--pdr <PDR>|--lpmd <LPMD>|--mhl <MHL>|--me <ME>|--pm <PM>|--fdrp <FDRP>|--qfdrp <QFDRP>|--mhl-intervals <MHL_INTERVALS>|--pdr-intervals <PDR_INTERVALS>>");
+            usage_error(cmd, "the following required arguments were not provided:\n  <--pdr <PDR>|--lpmd <LPMD>|--mhl <MHL>|--me <ME>|--pm <PM>|--fdrp <FDRP>|--qfdrp <QFDRP>|--mhl-intervals <MHL_INTERVALS>|--pdr-intervals <PDR_INTERVALS>|--me-intervals <ME_INTERVALS>|--pm-intervals <PM_INTERVALS>>");
         if (a.has("lpmd-pairs") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
-        // the BED comes with at least one of its three tables and each table with the BED; the LPMD table is LPMD's, the MHL and the PDR
-        // table stand alone
-        if (a.has("intervals") && !a.has("lpmd-intervals") && !a.has("mhl-intervals") && !a.has("pdr-intervals"))
-            usage_error(cmd, "the following required arguments were not provided:\n  <--lpmd-intervals <LPMD_INTERVALS>|--mhl-intervals <MHL_INTERVALS>|--pdr-intervals <PDR_INTERVALS>>");
-        if ((a.has("lpmd-intervals") || a.has("mhl-intervals") || a.has("pdr-intervals")) && !a.has("intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals <INTERVALS>");
+        // the BED comes with at least one of its tables and each table with the BED; the LPMD table is LPMD's, the MHL, the PDR, the ME and
+        // the PM table stand alone
+        const bool own_table = a.has("mhl-intervals") || a.has("pdr-intervals") || a.has("me-intervals") || a.has("pm-intervals");
+        if (a.has("intervals") && !a.has("lpmd-intervals") && !own_table)
+            usage_error(cmd, "the following required arguments were not provided:\n  <--lpmd-intervals <LPMD_INTERVALS>|--mhl-intervals <MHL_INTERVALS>|--pdr-intervals <PDR_INTERVALS>|--me-intervals <ME_INTERVALS>|--pm-intervals <PM_INTERVALS>>");
+        if ((a.has("lpmd-intervals") || own_table) && !a.has("intervals")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals <INTERVALS>");
         if (a.has("lpmd-intervals") && !a.has("lpmd")) usage_error(cmd, "the following required arguments were not provided:\n  --lpmd <LPMD>");
         // a region owns reads by their start: an interval at its left edge would see part of its reads
         if (a.has("mhl-intervals") && a.has("region")) usage_error(cmd, "the argument '--mhl-intervals <MHL_INTERVALS>' cannot be used with '--region <REGION>'");
         if (a.has("pdr-intervals") && a.has("region")) usage_error(cmd, "the argument '--pdr-intervals <PDR_INTERVALS>' cannot be used with '--region <REGION>'");
+        if (a.has("me-intervals") && a.has("region")) usage_error(cmd, "the argument '--me-intervals <ME_INTERVALS>' cannot be used with '--region <REGION>'");
+        if (a.has("pm-intervals") && a.has("region")) usage_error(cmd, "the argument '--pm-intervals <PM_INTERVALS>' cannot be used with '--region <REGION>'");
     }
     if (sub == "lpmd") {     // `requires`, both ways
         if (a.has("intervals") && !a.has("intervals-output")) usage_error(cmd, "the following required arguments were not provided:\n  --intervals-output <INTERVALS_OUTPUT>");
@@ -2038,11 +2112,15 @@ int main(int argc, char **argv) {
         g_intervals.path = a.s.at("intervals");
         if (sub == "mhl-regions") g_intervals.mhl_path = a.s.at("output");
         else if (sub == "pdr-regions") g_intervals.pdr_path = a.s.at("output");
+        else if (sub == "me-regions") g_intervals.me_path = a.s.at("output");
+        else if (sub == "pm-regions") g_intervals.pm_path = a.s.at("output");
         else if (sub == "lpmd") g_intervals.out_path = a.s.at("intervals-output");
         else {
             if (a.has("lpmd-intervals")) g_intervals.out_path = a.s.at("lpmd-intervals");
             if (a.has("mhl-intervals")) g_intervals.mhl_path = a.s.at("mhl-intervals");
             if (a.has("pdr-intervals")) g_intervals.pdr_path = a.s.at("pdr-intervals");
+            if (a.has("me-intervals")) g_intervals.me_path = a.s.at("me-intervals");
+            if (a.has("pm-intervals")) g_intervals.pm_path = a.s.at("pm-intervals");
         }
         mth_host_t *h = nullptr;
         char err[1024];
@@ -2086,7 +2164,7 @@ int main(int argc, char **argv) {
         }
         if (fclose(f) != 0) die("Error writing to output file.");
     };
-    if (sub != "mhl-regions" && sub != "pdr-regions") write_parts(a.s.at("output"), false);
+    if (sub != "mhl-regions" && sub != "pdr-regions" && sub != "me-regions" && sub != "pm-regions") write_parts(a.s.at("output"), false);
     if (sub == "lpmd" && a.has("pairs")) write_parts(a.s.at("pairs"), true);
     if (g_intervals.mhl_on()) {  // every shard counted its own reads for all the intervals: the histograms add up, the value is finalised once
         std::map<std::pair<uint32_t, uint32_t>, std::pair<uint64_t, uint64_t>> sum;
@@ -2106,6 +2184,15 @@ int main(int argc, char **argv) {
         for (const Part &p : parts)
             for (size_t i = 0; i < n && i < p.pr_m.size(); ++i) { m[i] += p.pr_m[i]; u[i] += p.pr_u[i]; d[i] += p.pr_d[i]; }
         pdr_regions_write(m, u, d, (uint32_t)a.n.at("min-depth"));
+    }
+    if (g_intervals.quartet_on()) {  // ... and the seventeen of the per-interval ME / PM
+        const size_t n = g_intervals.tid.size();
+        std::vector<uint64_t> bins(n * 16, 0), reads(n, 0);
+        for (const Part &p : parts) {
+            for (size_t i = 0; i < bins.size() && i < p.qr_bins.size(); ++i) bins[i] += p.qr_bins[i];
+            for (size_t i = 0; i < n && i < p.qr_reads.size(); ++i) reads[i] += p.qr_reads[i];
+        }
+        quartet_regions_write(bins, reads, (uint32_t)a.n.at("min-depth"));
     }
     if (g_intervals.on()) {      // every shard reduced its own rows for all the intervals: the sums add up
         const size_t n = g_intervals.tid.size();

@@ -15,7 +15,7 @@ static const char *kKernelNames[K_NUM] = {"k_build_index", "k_pdr_lpmd_tile", "k
                                           "k_fdrp_walk", "k_fdrp_emit", "k_pairs", "k_pairs_tile", "k_decode", "k_inflate", "k_crc32", "k_mhl_tile", "k_pdr_lpmd_wide",
                                           "k_fdrp_tile", "k_fdrp_chain", "k_fdrp_walk4", "k_fdrp_wtile", "k_mhl_rowcheck", "k_decode_genome",
                                           "k_straddle_guess", "k_straddle_walk", "k_straddle_repair", "k_fasta_pack", "k_deflate", "k_tag_assemble", "k_bgzf_compact", "bgzf_d2h",
-                                          "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill", "k_decode_mm", "k_mm_xm", "k_pairs_intervals", "k_mhl_regions", "k_pdr_regions"};
+                                          "k_bai_keys", "k_bai_rows", "bai_sort", "k_bai_fill", "k_decode_mm", "k_mm_xm", "k_pairs_intervals", "k_mhl_regions", "k_pdr_regions", "k_quartet_regions"};
 
 __global__ void k_lpmd_add2(DevState *st, long long n_read, long long n_valid) { st->lpmd[2] += n_read; st->lpmd[3] += n_valid; }
 
@@ -358,6 +358,7 @@ void mth_ctx_destroy(mth_ctx_t *ctx) {
     bai_release(ctx);
     mhl_regions_release(ctx);
     pdr_regions_release(ctx);
+    quartet_regions_release(ctx);
     for (auto &t : ctx->timed) { (void)hipEventDestroy(t.beg); (void)hipEventDestroy(t.end); }
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->d_state) (void)hipFree(ctx->d_state);
@@ -508,6 +509,7 @@ int mth_reset(mth_ctx_t *ctx) {
     {   // MHL and PDR per interval: the sums go, the declared intervals stay
         int rc = mhl_regions_clear(ctx);
         if (!rc) rc = pdr_regions_clear(ctx);
+        if (!rc) rc = quartet_regions_clear(ctx);
         if (rc) return rc;
     }
     ctx->carry_bytes = 0;                  // mth_bgzf_decode_straddle: the unfinished record of the previous call

@@ -45,6 +45,6 @@ struct SiteRec {  // per-tile scratch row
     uint32_t n_conc, n_disc, pad;
 };
 
-enum KernelId { K_INDEX = 0, K_TILE, K_GATHER, K_QBOUND, K_QTILE, K_QINSERT, K_QEMIT, K_MHLWALK, K_MHLWALKBIG, K_MHLEMIT, K_PDRWALK, K_FDRPWALK, K_FDRPEMIT, K_PAIRS, K_PAIRSTILE, K_DECODE, K_INFLATE, K_CRC, K_MHLTILE, K_WIDE, K_FDRPTILE, K_FDRPCHAIN, K_FDRPWALK4, K_FDRPWTILE, K_MHLROWCHK, K_DECODE_GENOME, K_STR_GUESS, K_STR_WALK, K_STR_REPAIR, K_FASTA_PACK, K_DEFLATE, K_TAG_ASSEMBLE, K_BGZF_COMPACT, K_BGZF_D2H, K_BAI_KEYS, K_BAI_ROWS, K_BAI_SORT, K_BAI_FILL, K_DECODE_MM, K_MM_XM, K_PAIRS_INTERVALS, K_MHL_REGIONS, K_PDR_REGIONS, K_NUM };
+enum KernelId { K_INDEX = 0, K_TILE, K_GATHER, K_QBOUND, K_QTILE, K_QINSERT, K_QEMIT, K_MHLWALK, K_MHLWALKBIG, K_MHLEMIT, K_PDRWALK, K_FDRPWALK, K_FDRPEMIT, K_PAIRS, K_PAIRSTILE, K_DECODE, K_INFLATE, K_CRC, K_MHLTILE, K_WIDE, K_FDRPTILE, K_FDRPCHAIN, K_FDRPWALK4, K_FDRPWTILE, K_MHLROWCHK, K_DECODE_GENOME, K_STR_GUESS, K_STR_WALK, K_STR_REPAIR, K_FASTA_PACK, K_DEFLATE, K_TAG_ASSEMBLE, K_BGZF_COMPACT, K_BGZF_D2H, K_BAI_KEYS, K_BAI_ROWS, K_BAI_SORT, K_BAI_FILL, K_DECODE_MM, K_MM_XM, K_PAIRS_INTERVALS, K_MHL_REGIONS, K_PDR_REGIONS, K_QUARTET_REGIONS, K_NUM };
 
 }  // namespace mth

@@ -45,7 +45,7 @@ struct PdrLane {
 }  // namespace mth
 
 struct mth_ctx;
-namespace mth { struct FusedQuartet; struct MhlRegions; struct PdrRegions; }
+namespace mth { struct FusedQuartet; struct MhlRegions; struct PdrRegions; struct QuartetRegions; }
 
 namespace mth {
 // ---- the tile-row table of a tile-kernel measure (ME / PM, LPMD pairs; driver: mth_tile_rows.hip) ----
@@ -265,6 +265,8 @@ struct mth_ctx {
     mth::MhlRegions *mhl_regions = nullptr;
     // PDR per interval (mth_pdr_regions.hip): the declared intervals, their sorted slices, three counters each (nullptr until the first begin)
     mth::PdrRegions *pdr_regions = nullptr;
+    // ME / PM per interval (mth_quartet_regions.hip): the declared intervals, their sorted slices, sixteen bins and the reads each (nullptr until the first begin)
+    mth::QuartetRegions *quartet_regions = nullptr;
 
     // multi-GPU exchange step (mth_rccl.hip): communicator of the one-process-per-GPU form; lpmd_reduced = DevState.lpmd
     // already holds the all-reduced totals (cleared by the next batch that adds to them)
@@ -356,6 +358,9 @@ int mhl_regions_clear(mth_ctx *ctx);
 // mth_pdr_regions.hip: the same two for the per-interval PDR state
 void pdr_regions_release(mth_ctx *ctx);
 int pdr_regions_clear(mth_ctx *ctx);
+// mth_quartet_regions.hip: ... and for the per-interval ME / PM state
+void quartet_regions_release(mth_ctx *ctx);
+int quartet_regions_clear(mth_ctx *ctx);
 struct DecArgs;
 // mth_decode_genome.hip: the two passes of the decode with the calls derived from the genome (k_decode_genome); `a` as decode_core
 // fills it for k_decode<false>.  count: ncpg / tid / start / end / mapq / fwd; fill: cpg_pos / cpg_rel at a.cpg_off

@@ -1,4 +1,4 @@
-// mth_intervals_dev.h -- the device frame the per-interval passes share (mth_intervals.hip, mth_mhl_regions.hip, mth_pdr_regions.hip):
+// mth_intervals_dev.h -- the device frame the per-interval passes share (mth_intervals.hip, mth_mhl_regions.hip, mth_pdr_regions.hip, mth_quartet_regions.hip):
 // the searches over a slice of sorted intervals (IvTab, mth_regions_host.h), and for the two read x interval passes the common
 // arguments, the owned-read test, the work item's span, a lane's walk over its candidate entries and the LDS rows.
 //
@@ -59,7 +59,7 @@ __device__ __forceinline__ void iv_walk(const IvTab &t, int32_t w_min, int32_t w
     }
 }
 
-// ---- the read x interval passes (k_mhl_regions, k_pdr_regions) ------------------------------------------------------------------------
+// ---- the read x interval passes (k_mhl_regions, k_pdr_regions, k_quartet_regions) ------------------------------------------------------------------------
 // A batch's reads are sorted by start: a work item is RG_B consecutive reads, one per lane, and its workgroup sums what they add to
 // the candidate entries of a slice in LDS rows of ROW 32-bit words before it adds every non-zero word to memory once.
 constexpr int RG_B = 256;                       // threads of a workgroup = reads of a work item

@@ -84,6 +84,20 @@ inline int pdr_regions_lds_cap_knob() {
 // MTH_PDR_REGIONS_SPAN=0 (tests, A/B): no span route -- an interval that holds a workgroup's whole span is counted read by read
 inline bool pdr_regions_span_knob() { const char *e = getenv("MTH_PDR_REGIONS_SPAN"); return !(e && atoi(e) == 0); }
 
+// ---- ME / PM per interval (mth_quartet_regions.hip): read once per context, when it first declares intervals ----
+// entries of a length class a workgroup sums in LDS rows of seventeen 32-bit words (sixteen bins and the reads: 15.9 KiB); a class with
+// more candidates adds to memory
+constexpr int QUARTET_REGIONS_LDS_CAP = 240;
+// MTH_QUARTET_REGIONS_LDS_CAP (tests: the differential forms): that cap, 0 .. QUARTET_REGIONS_LDS_CAP; 0: every add goes to memory directly
+inline int quartet_regions_lds_cap_knob() {
+    const char *e = getenv("MTH_QUARTET_REGIONS_LDS_CAP");
+    return e ? std::min(QUARTET_REGIONS_LDS_CAP, std::max(0, atoi(e))) : QUARTET_REGIONS_LDS_CAP;
+}
+// MTH_QUARTET_REGIONS_SUMMARY=0 (tests, A/B): no packed histogram -- a read an interval holds whole walks its calls as any other
+inline bool quartet_regions_summary_knob() { const char *e = getenv("MTH_QUARTET_REGIONS_SUMMARY"); return !(e && atoi(e) == 0); }
+// MTH_QUARTET_REGIONS_CARRY=0 (tests, A/B): no carried row -- a class with a single candidate is flushed once per work item
+inline bool quartet_regions_carry_knob() { const char *e = getenv("MTH_QUARTET_REGIONS_CARRY"); return !(e && atoi(e) == 0); }
+
 // ---- the tile-row measures (ME / PM: MTH_QUARTET_*, LPMD pairs: MTH_PAIRS_*): each read per call, where it is used ----
 inline const char *tile_rows_knob(const char *prefix, const char *suffix) {
     char name[48];

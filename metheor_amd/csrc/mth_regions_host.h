@@ -1,6 +1,6 @@
-// mth_regions_host.h -- the host-only pieces of the per-interval measures (`lpmd --intervals`, `mhl-regions`, `pdr-regions`): the intervals of a BED
-// file as one batch's domain sees them, their packed table, and the finalisers of MHL and of PDR per interval.  Plain C++, nothing of HIP, no environment: the
-// library (mth_intervals.hip, mth_mhl_regions.hip, mth_pdr_regions.hip) and the command line share this one copy, and it is tested
+// mth_regions_host.h -- the host-only pieces of the per-interval measures (`lpmd --intervals`, `mhl-regions`, `pdr-regions`, `me-regions` / `pm-regions`): the intervals of a BED
+// file as one batch's domain sees them, their packed table, and the finalisers of MHL, of PDR and of ME / PM per interval.  Plain C++, nothing of HIP, no environment: the
+// library (mth_intervals.hip, mth_mhl_regions.hip, mth_pdr_regions.hip, mth_quartet_regions.hip) and the command line share this one copy, and it is tested
 // without a device.
 #pragma once
 #include <stddef.h>
@@ -162,6 +162,38 @@ inline float pdr_regions_finalise(uint64_t n_concordant, uint64_t n_discordant, 
     const float c = (float)n_concordant, d = (float)n_discordant;
     const float den = c + d;
     return d / den;
+}
+
+// ---- ME / PM per interval: the finaliser -----------------------------------------------------------------------------------------------
+// compute_me (me.rs:42-55) and compute_pm (pm.rs:42-51) of the interval's ONE pooled QuartetStat: bins[p] = windows of four consecutive
+// kept calls with pattern p = 8*m1 + 4*m2 + 2*m3 + m4, over every contributing read.  n_patterns = the sum of the bins, the stat's
+// get_read_depth().  The reference's operation order: bins 0..15 ascending, p = count / total with each converted to f32 once,
+// me += p * log2(p) for the non-zero bins and me *= -0.25 last, pm -= p * p for every bin, zero ones included.  Plain operators, one
+// f32 operation each -- the objects that include this are built with -ffp-contract=off (the note in mth_quartet_dev.h) --: the
+// reference's bits whenever the counts fit its u32 (ME up to what log2 of the two C libraries differ by).  Fewer than max(min_depth, 1)
+// patterns: both NaN (me.rs:82 applied to the pooled stat).
+inline void quartet_regions_finalise(const uint64_t *bins, uint32_t min_depth, float *me_out, float *pm_out, uint64_t *n_patterns_out) {
+    uint64_t total = 0;
+    for (int k = 0; k < 16; ++k) total += bins[k];
+    if (n_patterns_out) *n_patterns_out = total;
+    float me = std::nanf(""), pm = std::nanf("");
+    if (total >= std::max<uint64_t>(min_depth, 1)) {
+        const float tf = (float)total;
+        me = 0.0f;
+        pm = 1.0f;
+        for (int k = 0; k < 16; ++k) {
+            const float p = (float)bins[k] / tf;
+            if (bins[k] > 0) {
+                const float t = p * log2f(p);
+                me = me + t;
+            }
+            const float sq = p * p;
+            pm = pm - sq;
+        }
+        me = me * -0.25f;
+    }
+    if (me_out) *me_out = me;
+    if (pm_out) *pm_out = pm;
 }
 
 }  // namespace mth

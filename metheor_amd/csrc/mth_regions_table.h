@@ -1,5 +1,5 @@
 // mth_regions_table.h -- the declared intervals of a per-interval measure and their table on the device (private): what
-// mth_mhl_regions.hip and mth_pdr_regions.hip keep between a begin and the fetches, and the domain registration mth_intervals.hip
+// mth_mhl_regions.hip, mth_pdr_regions.hip and mth_quartet_regions.hip keep between a begin and the fetches, and the domain registration mth_intervals.hip
 // shares with them.
 #pragma once
 #include <string>
@@ -75,7 +75,7 @@ struct RegionsTable {
     void release() { tab.release(); }
 };
 
-// what both read x interval passes tell their kernel about a staged batch
+// what the read x interval passes tell their kernel about a staged batch
 inline RgReadArgs rg_read_args(const mth_ctx *ctx, const mth_batch_t &d, const mth_mhl_params_t &p, const IvTab &tab, std::pair<uint32_t, uint32_t> slices) {
     RgReadArgs a;
     a.read_start = d.read_start; a.read_mapq = d.read_mapq; a.cpg_off = d.cpg_off; a.cpg_pos = d.cpg_pos;
