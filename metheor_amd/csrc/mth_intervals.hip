@@ -199,7 +199,7 @@ int mth_lpmd_intervals_fetch(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, con
         a.acc = ctx->iv_acc.as<unsigned long long>();
         a.n_tiles = n_tiles; a.n_chunks = (uint32_t)c_row0.size(); a.n_batches = (uint32_t)nb;
         LaunchTimer lt(ctx, K_PAIRS_INTERVALS);
-        hipLaunchKernelGGL(k_pairs_intervals, dim3((uint32_t)std::min<uint64_t>(n_items, 4096)), dim3(IV_B), 0, s, a);
+        hipLaunchKernelGGL(k_pairs_intervals, dim3((uint32_t)std::min<uint64_t>(n_items, regions_grid_knob(4096u))), dim3(IV_B), 0, s, a);
     }
     MTH_HIP(ctx, hipGetLastError());
     std::vector<unsigned long long> acc((size_t)n * 2);

@@ -3,6 +3,7 @@
 // (the I/O path's, METHEOR_TIMING and the debug / trace switches apart); the knob structs themselves are mth_plan.h's, which stays
 // pure.  Test and A/B switches, not an interface: INTEGRATION.md lists them with their lifetimes.
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
@@ -97,6 +98,17 @@ inline int quartet_regions_lds_cap_knob() {
 inline bool quartet_regions_summary_knob() { const char *e = getenv("MTH_QUARTET_REGIONS_SUMMARY"); return !(e && atoi(e) == 0); }
 // MTH_QUARTET_REGIONS_CARRY=0 (tests, A/B): no carried row -- a class with a single candidate is flushed once per work item
 inline bool quartet_regions_carry_knob() { const char *e = getenv("MTH_QUARTET_REGIONS_CARRY"); return !(e && atoi(e) == 0); }
+
+// ---- the per-interval passes (k_pairs_intervals, k_mhl_regions, k_pdr_regions, k_quartet_regions): read where the pass reads its others ----
+// MTH_REGIONS_GRID (tests: several work items per workgroup on a small input): an upper bound, 1 .. dflt, on the workgroups of a
+// launch, so that each comes round its persistent loop again -- with 1, one workgroup takes every work item in order.  Not a tuning
+// switch: unset -- or empty, not a number, or below 1 -- a launch has min(work items, dflt) workgroups as ever, and no smaller grid is
+// faster.
+inline uint32_t regions_grid_knob(const uint32_t dflt) {
+    const char *e = getenv("MTH_REGIONS_GRID");
+    const long long k = e ? atoll(e) : 0;
+    return k >= 1 ? (uint32_t)std::min<long long>(dflt, k) : dflt;
+}
 
 // ---- the tile-row measures (ME / PM: MTH_QUARTET_*, LPMD pairs: MTH_PAIRS_*): each read per call, where it is used ----
 inline const char *tile_rows_knob(const char *prefix, const char *suffix) {

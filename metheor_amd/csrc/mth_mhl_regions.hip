@@ -245,7 +245,7 @@ int mth_mhl_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const m
     a.rd = rg_read_args(ctx, d, *params, mr.iv.dev, sl);
     a.dense = mr.dense.as<unsigned long long>(); a.list = mr.list.as<uint2>(); a.state = mr.state.as<unsigned long long>();
     a.list_cap = mr.list_cap; a.list_only = 0;
-    const uint32_t grid = std::min<uint32_t>((d.n_reads + RG_B - 1) / RG_B, 8192u);
+    const uint32_t grid = std::min<uint32_t>((d.n_reads + RG_B - 1) / RG_B, regions_grid_knob(8192u));      // (both runs of the batch)
     {
         LaunchTimer lt(ctx, K_MHL_REGIONS);
         hipLaunchKernelGGL(k_mhl_regions, dim3(grid), dim3(RG_B), 0, s, a);

@@ -140,8 +140,9 @@ struct PdrRegions {
     bool on = false;
     RegionsTable iv;                                       // the declared intervals and their table
     DevBuf rows;
-    int acc_cap = PR_ACC;                                  // the two knobs (mth_knobs.h), read when the context first declares intervals
+    int acc_cap = PR_ACC;                                  // the three knobs (mth_knobs.h), read when the context first declares intervals
     bool span = true;
+    uint32_t grid_max = 8192;                              // workgroups of a launch at most (MTH_REGIONS_GRID)
 };
 
 void pdr_regions_release(mth_ctx *ctx) {
@@ -187,6 +188,7 @@ int mth_pdr_regions_begin(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, const 
         ctx->pdr_regions = new PdrRegions;
         ctx->pdr_regions->acc_cap = pdr_regions_lds_cap_knob();
         ctx->pdr_regions->span = pdr_regions_span_knob();
+        ctx->pdr_regions->grid_max = regions_grid_knob(8192u);
     }
     PdrRegions &pr = *ctx->pdr_regions;
     pr.iv.declare(n, tid, beg, end);
@@ -211,7 +213,7 @@ int mth_pdr_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, const m
     a.rd = rg_read_args(ctx, d, *params, pr.iv.dev, sl);
     a.rows = pr.rows.as<unsigned long long>(); a.acc_cap = pr.acc_cap;
     a.span = pr.span ? 1 : 0; a.pend = sl.second - sl.first <= (uint32_t)PR_PEND ? 1 : 0;
-    const uint32_t grid = std::min<uint32_t>((d.n_reads + RG_B - 1) / RG_B, 8192u);
+    const uint32_t grid = std::min<uint32_t>((d.n_reads + RG_B - 1) / RG_B, pr.grid_max);
     {
         LaunchTimer lt(ctx, K_PDR_REGIONS);
         hipLaunchKernelGGL(k_pdr_regions, dim3(grid), dim3(RG_B), 0, ctx->stream, a);

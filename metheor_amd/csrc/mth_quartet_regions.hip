@@ -135,8 +135,9 @@ struct QuartetRegions {
     bool on = false;
     RegionsTable iv;                                       // the declared intervals and their table
     DevBuf rows;
-    int acc_cap = QR_ACC;                                  // the three knobs (mth_knobs.h), read when the context first declares intervals
+    int acc_cap = QR_ACC;                                  // the four knobs (mth_knobs.h), read when the context first declares intervals
     bool summary = true, carry = true;
+    uint32_t grid_max = 8192;                              // workgroups of a launch at most (MTH_REGIONS_GRID)
 };
 
 void quartet_regions_release(mth_ctx *ctx) {
@@ -183,6 +184,7 @@ int mth_quartet_regions_begin(mth_ctx_t *ctx, uint64_t n, const int32_t *tid, co
         ctx->quartet_regions->acc_cap = quartet_regions_lds_cap_knob();
         ctx->quartet_regions->summary = quartet_regions_summary_knob();
         ctx->quartet_regions->carry = quartet_regions_carry_knob();
+        ctx->quartet_regions->grid_max = regions_grid_knob(8192u);
     }
     QuartetRegions &qr = *ctx->quartet_regions;
     qr.iv.declare(n, tid, beg, end);
@@ -209,7 +211,7 @@ int mth_quartet_regions_accumulate(mth_ctx_t *ctx, const mth_batch_t *batch, con
     a.rd = rg_read_args(ctx, d, rp, qr.iv.dev, sl);
     a.rows = qr.rows.as<unsigned long long>(); a.acc_cap = qr.acc_cap;
     a.summary = qr.summary ? 1 : 0; a.carry = qr.carry && sl.second - sl.first <= (uint32_t)QR_CARRY ? 1 : 0;
-    const uint32_t grid = std::min<uint32_t>((d.n_reads + RG_B - 1) / RG_B, 8192u);
+    const uint32_t grid = std::min<uint32_t>((d.n_reads + RG_B - 1) / RG_B, qr.grid_max);
     {
         LaunchTimer lt(ctx, K_QUARTET_REGIONS);
         hipLaunchKernelGGL(k_quartet_regions, dim3(grid), dim3(RG_B), 0, ctx->stream, a);

@@ -51,7 +51,16 @@ class Calls:
     """the decoded reads flattened: per call its read, contig, position (-1 for the word of position -1) and state"""
 
     def __init__(self, rec, cpg_set=None):
-        s = pyoracle.Reads.decode(rec, cpg_set=cpg_set).soa()
+        self._fill(pyoracle.Reads.decode(rec, cpg_set=cpg_set).soa())
+
+    @classmethod
+    def from_soa(cls, *soa):
+        """the same of reads that never were records: the argument tuple of pyoracle.Reads.from_soa, through the oracle and back"""
+        c = cls.__new__(cls)
+        c._fill(pyoracle.Reads.from_soa(*soa).soa())
+        return c
+
+    def _fill(self, s):
         off = s["cpg_off"].astype(np.int64)
         self.n_reads = len(s["tid"])
         self.read = np.repeat(np.arange(self.n_reads), np.diff(off))
