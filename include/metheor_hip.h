@@ -587,6 +587,16 @@ int  mth_bgzf_stage(mth_ctx_t *ctx, const void *file, uint64_t n_bytes);
 /* size the decoded arrays for n_reads / n_cpgs in total (what is decoded so far is kept): spares the appending calls their
  * reallocations when the caller can estimate the file's totals */
 int  mth_decode_reserve(mth_ctx_t *ctx, uint64_t n_reads, uint64_t n_cpgs);
+/* Which way the load calls went, since the context's creation or its last mth_reset (read-only, host counters): calls of the inflate
+ * step (mth_bgzf_inflate / mth_bgzf_decode / mth_bgzf_decode_straddle / mth_bgzf_straddle_scan) that took the buffer announced by
+ * mth_bgzf_stage, that copied their bytes in line with one copy, that copied them in pieces (METHEOR_COPY_PIECE_MB), the k_inflate
+ * launches of the pieced calls, announcements whose bytes were copied but not taken (the following call came with another pointer
+ * or size), and growths of the eight decoded arrays (one per array and growth, the first allocation included) by the decode itself
+ * and by mth_decode_reserve. */
+typedef struct {
+    uint64_t staged_calls, inline_calls, pieced_calls, pieced_launches, stage_misses, decode_reallocs;
+} mth_load_stats_t;
+int  mth_load_stats(mth_ctx_t *ctx, mth_load_stats_t *out);
 /* copy the decoded arrays to the host (any pointer may be NULL) */
 int  mth_decoded_fetch(mth_ctx_t *ctx, int32_t *tid, int32_t *start, int32_t *end, uint8_t *mapq, uint8_t *fwd,
                        uint64_t *cpg_off, uint32_t *cpg_pos, uint16_t *cpg_rel);

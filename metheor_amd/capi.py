@@ -19,7 +19,7 @@ SYMBOLS = [
     "mth_mhl_regions_begin", "mth_mhl_regions_accumulate", "mth_mhl_regions_counts", "mth_mhl_regions_finalise", "mth_mhl_regions_fetch", "mth_mhl_regions_stats",
     "mth_pdr_regions_begin", "mth_pdr_regions_accumulate", "mth_pdr_regions_counts", "mth_pdr_regions_finalise", "mth_pdr_regions_fetch",
     "mth_quartet_regions_begin", "mth_quartet_regions_accumulate", "mth_quartet_regions_counts", "mth_quartet_regions_finalise", "mth_quartet_regions_fetch",
-    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome", "mth_decode_set_modtags",
+    "mth_decode_records", "mth_decode_set_cpg_filter", "mth_decode_set_xm_min_mapq", "mth_bgzf_inflate", "mth_bgzf_deflate", "mth_bgzf_decode", "mth_bgzf_decode_straddle", "mth_bgzf_straddle_scan", "mth_bgzf_straddle_rescan", "mth_bgzf_stage", "mth_decode_reserve", "mth_load_stats", "mth_decoded_fetch", "mth_decoded_contigs", "mth_decoded_sort", "mth_decoded_group", "mth_decoded_group_each", "mth_group_define", "mth_group_clear", "mth_fileorder_run", "mth_fileorder_fetch", "mth_decoded_batch", "mth_tag_set_genome", "mth_tag_records", "mth_tag_records_bam", "mth_bai_begin", "mth_bai_add_records", "mth_bai_finish", "mth_tag_set_genome_fasta", "mth_tag_genome_fetch", "mth_decode_set_genome", "mth_decode_set_modtags",
     "mth_timing_enable", "mth_timing_reset", "mth_timing_get", "mth_timing_num_kernels",
     "mth_timing_kernel_name",
 ]
@@ -98,6 +98,10 @@ class mth_multi_params_t(C.Structure):
 
 class mth_straddle_info_t(C.Structure):
     _fields_ = [("rounds", C.c_uint32), ("repaired_blocks", C.c_uint32), ("carry_bytes", C.c_uint64)]
+
+
+class mth_load_stats_t(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("staged_calls", "inline_calls", "pieced_calls", "pieced_launches", "stage_misses", "decode_reallocs")]
 
 
 MTH_STRADDLE_APPEND, MTH_STRADDLE_LAST, MTH_STRADDLE_DROP_TAIL = 1, 2, 4
@@ -224,6 +228,7 @@ def lib():
         L.mth_bgzf_straddle_rescan.argtypes = [vp, C.c_uint64, vp, C.POINTER(mth_straddle_run_t), C.POINTER(mth_straddle_info_t)]
         L.mth_bgzf_stage.argtypes = [vp, vp, C.c_uint64]
         L.mth_decode_reserve.argtypes = [vp, C.c_uint64, C.c_uint64]
+        L.mth_load_stats.argtypes = [vp, C.POINTER(mth_load_stats_t)]
         L.mth_tag_set_genome.argtypes = [vp, C.c_int32, vp, vp, vp]
         L.mth_tag_set_genome_fasta.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, vp, vp]
         L.mth_tag_genome_fetch.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp]
@@ -386,6 +391,7 @@ class Engine:
         # call, so that a caller who drops or recycles a temporary batch right after the accumulate call cannot have the replay read
         # freed memory.  Keyed by id: a loop over one resident batch holds it once.
         self._inflight = {}
+        self._stage_next = self._stage_flying = None     # bgzf_stage: the announced array, and the one a helper thread is reading
 
     def _hold(self, batch):
         self._inflight[id(batch)] = batch
@@ -716,6 +722,7 @@ class Engine:
         coff = np.ascontiguousarray(coff, np.uint64); csize = np.ascontiguousarray(csize, np.uint32); isize = np.ascontiguousarray(isize, np.uint32)
         out = np.zeros(int(isize.astype(np.uint64).sum()), np.uint8)
         n = C.c_uint64(0)
+        self._stage_started()
         self._check(self.L.mth_bgzf_inflate(self.h, fb.ctypes.data, fb.size, coff.ctypes.data, csize.ctypes.data, isize.ctypes.data,
                                             len(coff), out.ctypes.data, C.byref(n)))
         assert n.value == len(out)
@@ -739,10 +746,45 @@ class Engine:
         fb = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(file_bytes, np.uint8)
         coff = np.ascontiguousarray(coff, np.uint64); csize = np.ascontiguousarray(csize, np.uint32); isize = np.ascontiguousarray(isize, np.uint32)
         d = mth_decoded_t()
+        self._stage_started()
         self._check(self.L.mth_bgzf_decode(self.h, fb.ctypes.data, fb.size, coff.ctypes.data, csize.ctypes.data, isize.ctypes.data,
                                            len(coff), int(first_byte), int(bool(append)), C.byref(d)))
         self._decoded = d
         return int(d.n_reads), int(d.n_cpgs)
+
+    def bgzf_stage(self, file_bytes, n_bytes=None):
+        """announce file_bytes as the chunk AFTER the one the next bgzf_decode / bgzf_inflate call is given (mth_bgzf_stage): that
+        call starts a helper thread that copies it to the device on a side stream, and the call after it, given the SAME pointer and
+        size, takes the copy.  file_bytes must be a contiguous np.uint8 array -- a slice of one array keeps base + offset, so pass
+        the very view (or an equal slice of the same array) to the following bgzf_decode; a `bytes` slice is a copy somewhere else
+        and would never match, so bytes are refused.  n_bytes: announce only the first n_bytes of it (default: all); 0, or
+        file_bytes None, withdraws the announcement.  The engine holds the array while the helper thread may read it: from here
+        until the inflating call after next has joined the thread (_stage_started)."""
+        if file_bytes is None:
+            fb, n = None, 0
+        else:
+            if not (isinstance(file_bytes, np.ndarray) and file_bytes.dtype == np.uint8 and file_bytes.flags["C_CONTIGUOUS"]):
+                raise TypeError("bgzf_stage takes a contiguous np.uint8 array (a view of the array the next chunk is decoded from)")
+            fb, n = file_bytes, file_bytes.size if n_bytes is None else int(n_bytes)
+            assert 0 <= n <= fb.size
+        self._stage_next = fb
+        self._check(self.L.mth_bgzf_stage(self.h, fb.ctypes.data if n else None, n))
+
+    def _stage_started(self):
+        """at every call that inflates: the library joins the helper thread of the call before and starts one for the announcement"""
+        self._stage_flying, self._stage_next = self._stage_next, None
+
+    def decode_reserve(self, n_reads, n_cpgs):
+        """size the decoded arrays for n_reads / n_cpgs in total; what is decoded so far is kept (mth_decode_reserve)"""
+        self._check(self.L.mth_decode_reserve(self.h, int(n_reads), int(n_cpgs)))
+
+    def load_stats(self):
+        """which way the load calls went since the engine's creation or the last reset (mth_load_stats): inflate calls that took
+        the staged buffer / copied in line / copied in pieces, k_inflate launches of the pieced calls, announcements copied but not
+        taken, growths of the decoded arrays"""
+        st = mth_load_stats_t()
+        self._check(self.L.mth_load_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in mth_load_stats_t._fields_}
 
     def bgzf_decode_straddle(self, file_bytes, coff, csize, isize, first_byte, append=False, last=False, drop_tail=False):
         """bgzf_decode for a file whose records straddle BGZF blocks (mth_bgzf_decode_straddle).  A call whose stream ends inside a
@@ -754,6 +796,7 @@ class Engine:
         coff = np.ascontiguousarray(coff, np.uint64); csize = np.ascontiguousarray(csize, np.uint32); isize = np.ascontiguousarray(isize, np.uint32)
         flags = (MTH_STRADDLE_APPEND if append else 0) | (MTH_STRADDLE_LAST if last else 0) | (MTH_STRADDLE_DROP_TAIL if drop_tail else 0)
         d, info = mth_decoded_t(), mth_straddle_info_t()
+        self._stage_started()
         rc = self.L.mth_bgzf_decode_straddle(self.h, fb.ctypes.data, fb.size, coff.ctypes.data, csize.ctypes.data, isize.ctypes.data,
                                              len(coff), int(first_byte), flags, C.byref(d), C.byref(info))
         self.straddle_info = dict(rounds=int(info.rounds), repaired_blocks=int(info.repaired_blocks), carry_bytes=int(info.carry_bytes))
@@ -771,6 +814,7 @@ class Engine:
         rows = np.zeros(int(n_run), STRADDLE_ROW)
         run, info = mth_straddle_run_t(), mth_straddle_info_t()
         self._scan_rows = int(n_run)
+        self._stage_started()
         self._check(self.L.mth_bgzf_straddle_scan(self.h, fb.ctypes.data, fb.size, coff.ctypes.data, csize.ctypes.data, isize.ctypes.data, len(coff),
                                                   int(n_run), MTH_STRADDLE_ENTRY_GUESS if entry is None else int(entry), rows.ctypes.data,
                                                   C.byref(run), C.byref(info)))

@@ -617,6 +617,7 @@ int load_chunks(Input &in, const mth_host_bgzf_t &bz, uint64_t blk_beg, bool str
     if (const char *e = getenv("METHEOR_FIRST_CHUNK_MB")) { const long k = atol(e); if (k >= 1 && k <= 65536) chunk_first = (size_t)k << 20; }
     if (const char *e = getenv("METHEOR_CHUNK_GROWTH")) { const long k = atol(e); if (k >= 1 && k <= 64) growth = (size_t)k; }
     const bool stage = !getenv("METHEOR_NO_STAGE");
+    const bool timing = getenv("METHEOR_TIMING") != nullptr;
     struct Chunk { uint64_t b0, b1, base, nbytes, ubytes; };
     std::vector<Chunk> chunks;
     uint64_t total_u = 0;
@@ -636,13 +637,20 @@ int load_chunks(Input &in, const mth_host_bgzf_t &bz, uint64_t blk_beg, bool str
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
         const Chunk &c = chunks[ci];
         const uint64_t first_byte = std::min<uint64_t>(hdr_left, c.ubytes);
-        if (c.b1 > c.b0 && hdr_left > c.ubytes && ci + 1 < chunks.size()) { hdr_left -= c.ubytes; continue; }   // a chunk made of header only
+        if (c.b1 > c.b0 && hdr_left > c.ubytes && ci + 1 < chunks.size()) {       // a chunk made of header only
+            if (timing) fprintf(stderr, "[metheor load] chunk %zu of %zu: %llu blocks, %llu file bytes, header only, not loaded\n", ci + 1, chunks.size(),
+                                (unsigned long long)(c.b1 - c.b0), (unsigned long long)c.nbytes);
+            hdr_left -= c.ubytes;
+            continue;
+        }
         if (stage && ci + 1 < chunks.size() && chunks[ci + 1].nbytes)
             check(in.ctx, mth_bgzf_stage(in.ctx, bz.file + chunks[ci + 1].base, chunks[ci + 1].nbytes));
         std::vector<uint64_t> rel((size_t)(c.b1 - c.b0));
         for (uint64_t k = c.b0; k < c.b1; ++k) rel[(size_t)(k - c.b0)] = bz.coff[k] - c.base;
         mth_decoded_t d;
         int rc;
+        mth_load_stats_t ls0{}, ls1{};
+        if (timing) check(in.ctx, mth_load_stats(in.ctx, &ls0));
         if (straddle) {
             // the next chunk is staged from its planned file offset all the same: the record a chunk ends in travels in the carry
             const unsigned flags = (first ? 0u : MTH_STRADDLE_APPEND) | (ci + 1 < chunks.size() ? 0u : (region_tail ? MTH_STRADDLE_DROP_TAIL : MTH_STRADDLE_LAST));
@@ -653,6 +661,12 @@ int load_chunks(Input &in, const mth_host_bgzf_t &bz, uint64_t blk_beg, bool str
                         (unsigned long long)(c.b1 - c.b0), info.rounds, info.repaired_blocks, (unsigned long long)info.carry_bytes);
         } else {
             rc = mth_bgzf_decode(in.ctx, bz.file + c.base, c.nbytes, rel.data(), bz.csize + c.b0, bz.isize + c.b0, c.b1 - c.b0, first_byte, first ? 0 : 1, &d);
+        }
+        if (timing) {                           // one line per library call, both routes: which way the chunk's file bytes went up
+            check(in.ctx, mth_load_stats(in.ctx, &ls1));
+            const char *how = ls1.staged_calls > ls0.staged_calls ? "staged" : ls1.pieced_calls > ls0.pieced_calls ? "pieced" : "in line";
+            fprintf(stderr, "[metheor load] chunk %zu of %zu: %llu blocks, %llu file bytes, %s, %llu piece launches, %llu records so far\n", ci + 1, chunks.size(), (unsigned long long)(c.b1 - c.b0),
+                    (unsigned long long)c.nbytes, how, (unsigned long long)(ls1.pieced_launches - ls0.pieced_launches), (unsigned long long)(rc == MTH_OK ? d.n_reads : 0));
         }
         hdr_left -= first_byte;
         if (rc == MTH_ERR_UNALIGNED) { check(in.ctx, mth_reset(in.ctx)); return rc; }
@@ -665,6 +679,11 @@ int load_chunks(Input &in, const mth_host_bgzf_t &bz, uint64_t blk_beg, bool str
             check(in.ctx, mth_decode_reserve(in.ctx, (uint64_t)((double)d.n_reads * f) + 4096, (uint64_t)((double)d.n_cpgs * f) + 4096));
         }
         first = false;
+    }
+    if (timing) {
+        mth_load_stats_t ls{};
+        check(in.ctx, mth_load_stats(in.ctx, &ls));
+        fprintf(stderr, "[metheor load] %llu reallocations of the decoded arrays, %llu staged copies not taken\n", (unsigned long long)ls.decode_reallocs, (unsigned long long)ls.stage_misses);
     }
     return MTH_OK;
 }

@@ -506,6 +506,7 @@ int mth_reset(mth_ctx_t *ctx) {
     ctx->f_batches.clear();
     ctx->f_rows_bound = 0;
     for (uint64_t &k : ctx->multi_stats) k = 0;
+    ctx->load_stats = mth_load_stats_t{0, 0, 0, 0, 0, 0};
     {   // MHL and PDR per interval: the sums go, the declared intervals stay
         int rc = mhl_regions_clear(ctx);
         if (!rc) rc = pdr_regions_clear(ctx);

@@ -179,6 +179,7 @@ struct mth_ctx {
     uint64_t next_bytes = 0;
     std::thread stage_thread;
     int stage_rc = 0;
+    mth_load_stats_t load_stats = {0, 0, 0, 0, 0, 0};    // mth_load_stats: which way the load calls went since the last mth_reset
     // mth_bgzf_decode_straddle: per-block entry / exit / count of the record chain (two generations, a round reads one and writes
     // the other), and the bytes of the record the previous call's stream ended in (they come first in the next call's stream)
     mth::DevBuf inf_links, inf_carry;

@@ -385,6 +385,7 @@ int decode_core(mth_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_off, uint6
     const size_t R0 = (size_t)ctx->dec_reads, C0 = (size_t)ctx->dec_cpgs, nr = (size_t)n_rec, R1 = R0 + nr;
     auto grow = [&](DevBuf &b, size_t need, size_t used) -> hipError_t {
         if (need <= b.cap) return hipSuccess;
+        ctx->load_stats.decode_reallocs += 1;
         return b.reserve(std::max(need, b.cap + b.cap / 2), s, used > 0, used);
     };
     MTH_HIP(ctx, grow(ctx->dec_tid, R1 * 4 + 4, R0 * 4));
@@ -512,14 +513,19 @@ int mth_decode_reserve(mth_ctx_t *ctx, uint64_t n_reads, uint64_t n_cpgs) {
     MTH_ENTER(ctx);
     hipStream_t s = ctx->stream;
     const size_t R0 = (size_t)ctx->dec_reads, C0 = (size_t)ctx->dec_cpgs, R = (size_t)n_reads, C = (size_t)n_cpgs;
-    MTH_HIP(ctx, ctx->dec_tid.reserve(R * 4 + 4, s, R0 > 0, R0 * 4));
-    MTH_HIP(ctx, ctx->dec_start.reserve(R * 4 + 4, s, R0 > 0, R0 * 4));
-    MTH_HIP(ctx, ctx->dec_end.reserve(R * 4 + 4, s, R0 > 0, R0 * 4));
-    MTH_HIP(ctx, ctx->dec_mapq.reserve(R + 4, s, R0 > 0, R0));
-    MTH_HIP(ctx, ctx->dec_fwd.reserve(R + 4, s, R0 > 0, R0));
-    MTH_HIP(ctx, ctx->dec_off.reserve((R + 1) * 8, s, R0 > 0, R0 ? (R0 + 1) * 8 : 0));
-    MTH_HIP(ctx, ctx->dec_pos.reserve(C * 4 + 4, s, C0 > 0, C0 * 4));
-    MTH_HIP(ctx, ctx->dec_rel.reserve(C * 2 + 4, s, C0 > 0, C0 * 2));
+    auto grow = [&](DevBuf &b, size_t need, size_t used) -> hipError_t {
+        if (need <= b.cap) return hipSuccess;
+        ctx->load_stats.decode_reallocs += 1;
+        return b.reserve(need, s, used > 0, used);
+    };
+    MTH_HIP(ctx, grow(ctx->dec_tid, R * 4 + 4, R0 * 4));
+    MTH_HIP(ctx, grow(ctx->dec_start, R * 4 + 4, R0 * 4));
+    MTH_HIP(ctx, grow(ctx->dec_end, R * 4 + 4, R0 * 4));
+    MTH_HIP(ctx, grow(ctx->dec_mapq, R + 4, R0));
+    MTH_HIP(ctx, grow(ctx->dec_fwd, R + 4, R0));
+    MTH_HIP(ctx, grow(ctx->dec_off, (R + 1) * 8, R0 ? (R0 + 1) * 8 : 0));
+    MTH_HIP(ctx, grow(ctx->dec_pos, C * 4 + 4, C0 * 4));
+    MTH_HIP(ctx, grow(ctx->dec_rel, C * 2 + 4, C0 * 2));
     return MTH_OK;
 }
 

@@ -724,6 +724,7 @@ int stage_take(mth_ctx *ctx, const void *file, uint64_t n_bytes, bool &staged) {
         if (ctx->stage_rc != MTH_OK) return fail(ctx, MTH_ERR_HIP, "staging the next chunk's file bytes failed");
     }
     staged = ctx->staged_src && ctx->staged_src == file && ctx->staged_bytes == n_bytes;
+    if (ctx->staged_src && !staged) ctx->load_stats.stage_misses += 1;      // copied, and this call came with another pointer or size
     if (staged) {
         // copied on the side stream while the previous chunk was in flight: take that buffer
         std::swap(ctx->inf_file, ctx->inf_file2);
@@ -786,9 +787,11 @@ int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, const uint6
     // of two pieces or more travels on its own stream piece by piece, and the blocks of a piece are inflated as soon as the piece
     // has landed.  Built to hide the first chunk's inflate behind its copy; measured slower (profiles/r02_e2e.md, last section):
     // a pageable copy pins, moves and unpins inside the call, ~2.5 ms of that per call is not overlapped with anything, and the
-    // runtime pipelines one large copy better than the caller can pipeline several small ones.  Kept as a switch, parity-tested.
+    // runtime pipelines one large copy better than the caller can pipeline several small ones.  Kept as a switch, parity-tested
+    // (tests/test_gpu_chunked_load.py: bytes, and the launch count against a restatement of the rule below).
     static const size_t piece_bytes = [] { const char *e = getenv("METHEOR_COPY_PIECE_MB"); const long k = e ? atol(e) : 0; return k > 0 ? (size_t)k << 20 : (size_t)0; }();
     const bool pieced = !staged && piece_bytes && n_bytes >= 2 * (uint64_t)piece_bytes && nb >= 2;
+    (staged ? ctx->load_stats.staged_calls : pieced ? ctx->load_stats.pieced_calls : ctx->load_stats.inline_calls) += 1;
     if (!staged && !pieced) {
         // (copying through own page-locked pieces from 2-8 worker threads was measured: no faster than the runtime's pageable path,
         // profiles/r02_e2e.md -- the page-cache reads bound both)
@@ -851,7 +854,7 @@ int inflate_blocks(mth_ctx *ctx, const void *file, uint64_t n_bytes, const uint6
                 // the blocks whose payload -- and the 64 bytes the bit reader may load past it -- have arrived
                 size_t b1 = bl;
                 while (b1 < nb && (last || coff[b1] + (uint64_t)csize[b1] + 64u <= (uint64_t)off)) ++b1;
-                if (b1 > bl) launch(bl, b1);
+                if (b1 > bl) { launch(bl, b1); ctx->load_stats.pieced_launches += 1; }
                 bl = b1;
             }
         } else {
@@ -996,6 +999,12 @@ int mth_bgzf_stage(mth_ctx_t *ctx, const void *file, uint64_t n_bytes) {
     if (!ctx || (n_bytes && !file)) return MTH_ERR_INVALID;
     ctx->next_src = n_bytes ? file : nullptr;
     ctx->next_bytes = n_bytes;
+    return MTH_OK;
+}
+
+int mth_load_stats(mth_ctx_t *ctx, mth_load_stats_t *out) {
+    if (!ctx || !out) return MTH_ERR_INVALID;
+    *out = ctx->load_stats;
     return MTH_OK;
 }
 
